@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/sec of the batched walker stepper (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--walkers 65536] [--workload canonical]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--walkers 65536] [--workload canonical] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -21,7 +22,16 @@ runs after the barrier that closes the K timed steps (`--gather serial`, the def
 `value_incl_gather` the steps and the gather, and `gather.content_check` compares every rank's checksums of what it
 sent with its shard of the gathered tensors (a failed check exits 3).  `--gather pipelined` gathers the previous
 rollout's observations while this one steps, inside the timed region (slower on one MI355X).
-After the K steps `sustained` times 1,000 steps and a ~2 s run of the same walker ranges (the long-run clock).
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` also writes what the last
+timed step returned, as .npy: the same arguments give the same inputs, so two builds compare output for output.
+Episodes: under random actions the reference's physics diverges for some walkers by step ~90, so warm-up and timed
+steps run as episodes of EPISODE_STEPS = 64 steps from the env's initial state, and every walker returns to that state
+when an episode is full (inside the clock; the line's `episodes` counts the returns).  W + K <= 64, the driver's 5 + 20,
+is one episode and one prepared call; the default 50 + 1,000 is 17 calls with 16 returns between them.  K may also
+exceed the distinct action tensors that fit ACT_BYTES_MAX of HBM: the region then takes them again from the first.
+With `--full`, after the K steps, `sustained` times 1,000 steps and a ~2 s run of the same walker ranges (the long-run
+clock), and the line carries the single-launch control and per-kernel roofline, the closed loops (`closed_loop`,
+`closed_loop_policy`), a small batch's launch `floor` and `cpu_baseline`.
 Rank 0 prints ONE JSON line.  Workloads: canonical (M=16, K=40, A=8; config 3/4),
 balance (Balance-v0; config 2 at --walkers 4096), ragged (M ~ U{4..32}; config 5), chain (performance_demo's
 chain of --chain-points masses with per-walker Point.gravity; §8(f) 3).
@@ -54,6 +64,9 @@ FP32_PEAK_TFS = 157.3
 #   perfdemo (gym/optimized_engine.py:177-193, gravity_vec): float32 norm (3 products, sqrt) and powf, the quotient
 #     of f, 3 products and 3 quotients of the force, and per end 3 quotients by m and 3 adds: 24 FP32
 #     (+ the norm's 2 float64 adds and the numerator's 2 float64 products)
+DUMP_BYTES_MAX = 64_000_000    # --dump-outputs: the arrays of one run in all
+EPISODE_STEPS = 64             # steps from the initial state before every walker returns to it (main: Episodes)
+ACT_BYTES_MAX = 8 << 30        # distinct per-step actions resident in HBM (4,096 canonical steps); a longer region repeats them
 PAIR_FLOP = {"chain": (34, "fp64-valu", FP64_PEAK_TFS), "perfdemo": (24, "fp32-valu", FP32_PEAK_TFS)}
 
 
@@ -66,6 +79,13 @@ def parse(argv=None):
     ap.add_argument("--workload", default="canonical",
                     choices=["canonical", "balance", "ragged", "chain", "perfdemo", "lattice25"])
     ap.add_argument("--chain-points", type=int, default=100, help="masses per chain walker (--workload chain)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the K timed steps also measure what stands beside the headline: `sustained`, the "
+                         "single-launch control and per-kernel roofline, the closed loops, the launch floor of a small "
+                         "batch and the CPU baseline (a plain run times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left for a caller (obs, reward, done, info's centroid_position, "
+                         "total_energy and steps) as DIR/<name>.npy, float32")
     ap.add_argument("--lanes", type=int, default=None, help="walker ranges on separate streams (default: auto)")
     ap.add_argument("--resident", action="store_true", help="also time the K steps as ONE wg_rollout launch (state in "
                     "registers across steps; open-loop actions) and report it beside the line (not the headline)")
@@ -368,6 +388,27 @@ def host_spin(us: float) -> None:
         pass
 
 
+def dump_outputs(path: str, env, rec, rank: int, world: int) -> None:
+    """--dump-outputs: what the last timed step left for a caller of the timed path (BatchedPhysicsEnv.run): obs, reward,
+    done and info's centroid_position, total_energy and steps, each as DIR/<name>.npy in float32, walkers in the
+    caller's order (inside a torch.distributed world of more than one rank: <name>_rank<r>.npy, each rank its own
+    walkers).  Above DUMP_BYTES_MAX in all, the same seeded sample of walkers (rows, ascending) of every array."""
+    last = (lambda k, t: t) if rec is None else (lambda k, t: rec[k][-1])   # (a record run: the last step's rows)
+    out = {"obs": env.obs, "reward": last("reward", env.reward), "done": last("done", env.done),
+           "centroid_position": last("centroid", env.centroid), "total_energy": last("energy", env.energy),
+           "steps": env.info()["steps"]}
+    n = env.N
+    row_bytes = sum(4 * t.numel() // n for t in out.values())
+    rows = None
+    if n * row_bytes > DUMP_BYTES_MAX:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES_MAX // row_bytes, replace=False))
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, t in out.items():
+        a = t.detach().to("cpu").numpy().astype(np.float32)
+        np.save(os.path.join(path, f"{name}{tag}.npy"), a if rows is None else a[rows])
+
+
 def timed(env, acts, steps, lanes, stream):
     """Per-step kernel time with HIP events on `stream` (the calling stream waits for every walker range)."""
     import torch
@@ -410,6 +451,10 @@ def main():
     ensure_world(args)
     if args.dry_run:
         return dry_run(args)
+    if not args.full:
+        # a plain run: set up, warm up, the K timed steps, the line.  Everything timed or checked beside them is --full's
+        args.no_control = args.no_cpu_baseline = True
+        args.sustained_steps = 0
     import torch
     import torch.distributed as dist
     from walker_gym_amd.batched_env import BatchedPhysicsEnv
@@ -454,7 +499,12 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(7 + rank)
     acts_w = (torch.rand((max(args.warmup, 1), N, A), generator=gen, device=dev) * 2 - 1).contiguous()
-    acts = (torch.rand((args.steps, N, A), generator=gen, device=dev) * 2 - 1).contiguous()
+    # a distinct action tensor for every timed step, up to ACT_BYTES_MAX of them: a longer region (a plain single-process
+    # run only) takes the same actions again from the first, so --steps can be as large as the clock needs
+    chunk = args.steps
+    if not (in_world or args.graph or args.resident):
+        chunk = max(1, min(args.steps, ACT_BYTES_MAX // (N * A * 4)))
+    acts = (torch.rand((chunk, N, A), generator=gen, device=dev) * 2 - 1).contiguous()
     stream = torch.cuda.current_stream(dev)
 
     graph = env.graph(acts, args.steps, lanes=lanes) if args.graph else None
@@ -488,13 +538,54 @@ def main():
         torch.cuda.synchronize()
     warm_ms = args.device_warm_ms if args.device_warm_ms is not None else float(os.environ.get("WG_BENCH_WARM_MS", "100"))
     warm_s = device_warm(stream, dev, warm_ms)
+    # Episodes: under U(-1,1) actions the reference's physics diverges for some walkers: on the C oracle every
+    # one of the 65,536 canonical walkers is finite through step 80 (energies <= 2.4e11), the first energy overflows by
+    # step 90 and the first NaN observation appears by step 100 (two action seeds).  So the bench steps episodes of
+    # EPISODE_STEPS = 64 steps (or max_steps, if less), counted from the env's initial state through the warm-up and
+    # the timed region: when an episode is full every walker returns to the initial state (one copy per state tensor,
+    # on the bench stream, inside the clock) and the next begins.  W + K <= 64, the driver's 5 + 20 included, is one
+    # episode: one prepared C call for the K steps, as before.
+    H = max(1, min(EPISODE_STEPS, int(env.params.max_steps)))
+
+    def snapshot() -> dict:
+        # DeviceBatch.state_dict's tensors (radius where the batch keeps it), but in the stored order: restore() is then
+        # plain copies, with none of load_state_dict's caller-to-stored gathers inside the clock
+        keys = env.batch.STATE + (("radius",) if env.batch.radius is not None else ())
+        return {k: getattr(env.batch, k).clone() for k in keys}
+
+    def restore(sd: dict) -> None:
+        for k, t in sd.items():
+            getattr(env.batch, k).copy_(t)
+        env.batch.version += 1
+
+    def episodes(acts_t, n: int, age: int, record=None) -> tuple:
+        """The prepared runs of n steps over acts_t (taken again from its start where n is longer), in order, None where
+        the walkers return to the initial state first; and the episode's age after them (age: before them)."""
+        T, out, cache, t = acts_t.shape[0], [], {}, 0
+        while t < n:
+            if age == H:
+                out.append(None)
+                age = 0
+            a0 = t % T
+            m = min(n - t, T - a0, H - age)
+            r = None if record is None else {k: v[t:t + m] for k, v in record.items()}
+            if r is not None or (a0, m) not in cache:
+                cache[(a0, m)] = env.prepare_run(acts_t[a0:a0 + m], m, lanes=lanes, record=r)
+            out.append(cache[(a0, m)])
+            t, age = t + m, age + m
+        return out, age
+
+    start, age = snapshot(), 0
     if args.warmup > 0:
-        env.run(acts_w, args.warmup, lanes=lanes)
+        warm, age = episodes(acts_w, args.warmup, age)
+        for p in warm:
+            restore(start) if p is None else p()
     if graph is not None:
         graph.replay()                         # warm the graph path too
-    # the timed call's arguments, walker ranges and C structs built here: inside the timed region the K steps are one
-    # C call (run() spends ~35 us of Python before its first launch, which the GPU would idle through)
-    prep = env.prepare_run(acts, args.steps, lanes=lanes, record=rec) if graph is None else None
+    # the timed calls' arguments, walker ranges and C structs built here: inside the timed region an episode's steps are
+    # one C call (run() spends ~35 us of Python before its first launch, which the GPU would idle through; DESIGN §6)
+    region = episodes(acts, args.steps, age, record=rec)[0] if graph is None else None
+    restores = 0 if region is None else sum(p is None for p in region)
     torch.cuda.synchronize()
 
     def open_region() -> float:
@@ -532,13 +623,16 @@ def main():
     if graph is not None:
         graph.replay()
     else:
-        prep()
+        for p in region:
+            restore(start) if p is None else p()
     ev1.record(stream)
     gathered = None
     if pending is not None:
         gathered = {"obs": pending.wait()}
     wall_max, slowest_rank, wall_bar_max = close_region(t0)
     step_ms = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, env, rec, rank, world)
 
     gather_info = None
     if do_gather:
@@ -583,7 +677,7 @@ def main():
     B = bytes_per_walker_step(env.batch.host, bool(params.get("in3d")))
     if graph is None and args.sustained_steps > 0:
         S = args.sustained_steps
-        acts_s = acts[:S] if args.steps >= S else \
+        acts_s = acts[:S] if chunk >= S else \
             (torch.rand((S, N, A), generator=gen, device=dev) * 2 - 1).contiguous()
         prep_s = env.prepare_run(acts_s, S, lanes=lanes)
         torch.cuda.synchronize()
@@ -635,8 +729,10 @@ def main():
         # still see the clocks ramp, and the per-launch figure is the kernel's, not the bench's K)
         n1 = 200
         single_ms = step_ms if (lanes == 1 and graph is None and args.steps >= n1) else None
-        acts_c = acts[:n1] if args.steps >= n1 else \
-            (torch.rand((n1, N, A), generator=gen, device=dev) * 2 - 1).contiguous()
+        acts_c = None
+        if not args.no_control or args.resident:
+            acts_c = acts[:n1] if chunk >= n1 else \
+                (torch.rand((n1, N, A), generator=gen, device=dev) * 2 - 1).contiguous()
         if single_ms is None and not args.no_control:
             env.run(acts_c, n1, lanes=1)
             single_ms = timed(env, acts_c, n1, 1, stream)
@@ -786,6 +882,12 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(wall_max * 1e3 / args.steps, 5),
+            "episodes": {"steps": (H if graph is None else None), "restores_in_timed_steps": restores,
+                         "prepared_calls_in_timed_steps": (1 if region is None else len(region) - restores),
+                         "note": "the walkers return to the env's initial state after every `steps` steps, counted "
+                                 "from that state through the warm-up and the timed steps (one copy per state tensor, "
+                                 "inside the clock): `restores_in_timed_steps` of them fell into the K timed steps; 0 = "
+                                 "K straight steps in one prepared call (W + K <= `steps`; a --graph replay has none)"},
             "timing": {"clock": ("host CLOCK_MONOTONIC, one clock for the node's ranks: t0 after the opening barrier + "
                                  "synchronize, t1 after each rank's synchronize; job time = max(t1) - min(t0) over "
                                  "ranks (start skew included)" if in_world else
@@ -795,7 +897,7 @@ def main():
                        "device_warm_ms": round(warm_s * 1e3, 2),
                        "kernel_ms_per_step_events": round(step_ms, 5),
                        "region": "burst: a K-step region after a 100 ms device warm-up runs at the GPU's burst clock; "
-                                 "`sustained` times 1,000 steps and a ~2 s run of the same walker ranges beside it",
+                                 "`sustained` (--full) times 1,000 steps and a ~2 s run of the same walker ranges beside it",
                        **({"comm": "RCCL's communicator up before the timed steps (created and checked by a one-element "
                                    "all_reduce, then one untimed gather of the rollout's tensors); barriers and the "
                                    "clock exchange on a gloo group"} if in_world and backend == "nccl" else
@@ -836,9 +938,9 @@ def main():
                                  ("achieved = N * B / the per-launch time of ONE full-batch launch per step (HIP "
                                   "events around back-to-back launches on the launching stream); B = SURVEY §8(d) "
                                   "algorithmic bytes averaged over the walkers") if single_ms is not None else
-                                 (f"achieved = N * B / the time per step of the {lanes} walker ranges (--no-control: "
-                                  "no single-launch timing); B = SURVEY §8(d) algorithmic bytes averaged over the "
-                                  "walkers")},
+                                 (f"achieved = N * B / the time per step of the {lanes} walker ranges (HIP events around "
+                                  "the K timed steps; the single-launch timing is --full's, unless --no-control); B = "
+                                  "SURVEY §8(d) algorithmic bytes averaged over the walkers")},
         }
         if comm is not None:
             line["comm"] = comm
@@ -893,7 +995,7 @@ def main():
                                          "FP64_PEAK_TFS / FP32_PEAK_TFS, measured by scripts/valu_peak.hip)"),
                                 "hbm": {k: hbm[k] for k in ("achieved", "peak", "unit", "frac", "bytes_per_walker_step")}}
             line["pairs_per_s"] = round(pairs / (head_ms * 1e-3), 1)
-        if N <= 16384:
+        if args.full and N <= 16384:
             # a small batch is one wave's latency chain per launch: state the launch floor it is bounded by, timed
             # here, on this box and stream, for the step's own grid (wg_launch_floor: back-to-back launches of an
             # empty kernel and of one coalesced load + store per thread, HIP events)
