@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "walker_hip.h"
@@ -77,6 +78,8 @@ struct KParams {
     int prio;         // WG_LEAN_PRIO: 1 (default) raise the wave priority while a lean tile issues its loads, so a
                       // wave's HBM requests leave before other waves' arithmetic; 0 off
     int xcd;          // WG_XCD bitmask: XCD-aware workgroup order (xcd_block) for 1 the wave kernel, 2 the lean kernel
+    int keep_aux;     // 0: a step of a multi-step call before its last, the lean / wave kernels skip the acc and contact
+                      // stores (the next step overwrites them unread); 1: every store (run())
 };
 
 // The per-step outputs the step kernels write: wg_outputs without the opt-in info pointers (walker_info_kernel writes
@@ -1897,10 +1900,12 @@ __device__ __forceinline__ void spring_edge_regs(const EdgeRec &e, int le, float
 // ------------------------------------------------------------------ lean wave tile: loads, then compute
 // Global inputs of one wave's tile, held in registers: lean_load issues every HBM read of the tile back to
 // back, lean_compute consumes them.
-template <int NE>
+// E8: the compact spring records (wg_edge8, ABI 15): two registers per pass instead of four, the lane roles resolved
+struct EdgeRec8 { uint32_t w; float rest; };
+template <int NE, bool E8 = false>
 struct LeanIn {
     float p3[3], v3[3];          // this lane's mass: pos, vel (the springs gather them with ds_bpermute)
-    EdgeRec er[NE];              // this lane's spring record in each edge pass
+    typename std::conditional<E8, EdgeRec8, EdgeRec>::type er[NE];   // this lane's spring record in each edge pass
     uint32_t gi[NE];             // incidence words (two u16 entries each)
     float mf;                    // mass
     int io0, io1, wsteps, pin;   // incidence range; step counter (q == 0 lanes); DingPoint flag
@@ -1950,8 +1955,8 @@ __device__ __forceinline__ T &at_u32w(T *base, uint32_t byte_off) {
 #define WG_ST(base, e, n) (&at_u32w((base), (uint32_t)(n) * 4u * (uint32_t)(e)))
 // a count (<= 64) halved and negated as the reference's float64 product: exact in float32 (-0.0 for 0, as -(0.0) * 0.5)
 __device__ __forceinline__ float neg_half_count(int n) { return -0.5f * (float)n; }
-template <int NE>
-__device__ __forceinline__ void lean_load_mass(const wg_batch &b, const LeanTile &t, int lane, LeanIn<NE> &L) {
+template <class LI>
+__device__ __forceinline__ void lean_load_mass(const wg_batch &b, const LeanTile &t, int lane, LI &L) {
     L.mf = 0.f; L.io0 = 0; L.io1 = 0; L.wsteps = 0; L.pin = 0;
     // every lane loads (lanes past the tile's masses a duplicate of its last one; their values are never used)
     const int ln = min(lane, t.nP - 1);
@@ -1962,9 +1967,9 @@ __device__ __forceinline__ void lean_load_mass(const wg_batch &b, const LeanTile
     L.io0 = at_u32(b.inc_off, 2u * io); L.io1 = at_u32(b.inc_off, 2u * io + 2u);
     L.wsteps = at_u32(b.steps, 4u * (uint32_t)(t.w0 + wl));   // the walker's counter in each of its lanes
 }
-template <int NE>
+template <class LI>
 __device__ __forceinline__ void lean_load_muscles(const wg_batch &b, const KParams &kp, const float *__restrict__ action,
-                                                  int action_stride, const LeanTile &t, int lane, LeanIn<NE> &L) {
+                                                  int action_stride, const LeanTile &t, int lane, LI &L) {
     L.x = 0.f; L.lo = 0.f; L.hi = 0.f; L.stp = 0.f; L.a = 0.f;
     if (t.nU > 0) {                       // wave-uniform
         const uint32_t ul = t.U0 + min(lane, t.nU - 1);
@@ -1978,9 +1983,9 @@ __device__ __forceinline__ void lean_load_muscles(const wg_batch &b, const KPara
         }
     }
 }
-template <int NE>
+template <int NE, bool E8>
 __device__ __forceinline__ void lean_load(const wg_batch &b, const KParams &kp, const float *__restrict__ action,
-                                          int action_stride, const LeanTile &t, int lane, LeanIn<NE> &L) {
+                                          int action_stride, const LeanTile &t, int lane, LeanIn<NE, E8> &L) {
     // every load unconditional from a clamped (valid) index, issued back to back: no exec-mask branch per load
     // (each with its zero-fill moves), addresses as SGPR base + 32-bit offset.  Lanes past the tile's masses,
     // springs and muscles hold duplicates; every use of them is gated (is_mass, le < nE, is_mus, acts).
@@ -1991,12 +1996,17 @@ __device__ __forceinline__ void lean_load(const wg_batch &b, const KParams &kp, 
 #pragma unroll
     for (int it = 0; it < NE; it++) {
         const uint32_t le = t.E0 + (uint32_t)min(lane + 64 * it, t.nE - 1);
-        const uint4 v = at_u32(reinterpret_cast<const uint4 *>(b.edges), 16u * le);
-        L.er[it] = EdgeRec{v.x, __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
+        if constexpr (E8) {   // one 8-B load (the clamped lanes past nE hold the tile's last record: valid lane roles)
+            const uint2 v = at_u32(reinterpret_cast<const uint2 *>(b.edges8), 8u * le);
+            L.er[it] = EdgeRec8{v.x, __uint_as_float(v.y)};
+        } else {
+            const uint4 v = at_u32(reinterpret_cast<const uint4 *>(b.edges), 16u * le);
+            L.er[it] = EdgeRec{v.x, __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
+        }
         L.gi[it] = at_u32(reinterpret_cast<const uint32_t *>(b.inc), 4u * le);
     }
-    lean_load_mass<NE>(b, t, lane, L);
-    lean_load_muscles<NE>(b, kp, action, action_stride, t, lane, L);
+    lean_load_mass(b, t, lane, L);
+    lean_load_muscles(b, kp, action, action_stride, t, lane, L);
     if (!t.is_mass) {                     // the reference values of the lanes past the tile's masses
         L.p3[0] = 0.f; L.p3[1] = 0.f; L.p3[2] = 0.f; L.v3[0] = 0.f; L.v3[1] = 0.f; L.v3[2] = 0.f;
         L.mf = 0.f; L.pin = 0; L.io0 = 0; L.io1 = 0;
@@ -2200,10 +2210,10 @@ __device__ __forceinline__ LeanTerms lean_terms(char *sl, const LeanGeo &lg) {
 // One wave's tile after its loads: the edge lanes leave the spring term t and the damping force df of every
 // edge in LDS, then each mass lane walks its incidence list, dividing by m as the reference does (mass_step).
 // RES (walker_rollout_lean): the tile's state stays in L across steps; it is written to HBM only when `last`.
-template <bool IN3D, int NE, bool RES = false>
+template <bool IN3D, int NE, bool RES = false, bool E8 = false>
 __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &kp, const KOut &o,
                                              const LeanGeo &lg, char *sl, const LeanTile &t, int lane,
-                                             LeanIn<NE> &L, bool last = true) {
+                                             LeanIn<NE, E8> &L, bool last = true) {
     const bool store = !RES || last;
     const int M = b.M, K = b.K, A = b.A;
     const int w0 = t.w0, nE = t.nE;
@@ -2278,11 +2288,17 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     // 47.8 us per launch, profiles/r02_ab_spring_pipe.json.)
     struct Gath { float v[12]; };
     auto gather = [&](int it, Gath &g) {
-        const int le = lane + 64 * it;
-        const int ewl = fdiv(le, K, lg.invK);
-        const uint32_t ij = L.er[it].ij;
-        // (M | 64 is a power of two: the walker's first lane is a shift; 24-bit products below, one VALU each)
-        const int bi = ((ewl << lg.lgM) + edge_i(ij)) << 2, bj = ((ewl << lg.lgM) + edge_j(ij)) << 2;
+        int bi, bj;
+        if constexpr (E8) {   // the endpoints' lanes as packed (wg_edge8): ds_bpermute reads the low byte's lane bits
+            const uint32_t w = L.er[it].w;
+            bi = (int)w; bj = (int)(w >> 8);
+        } else {
+            const int le = lane + 64 * it;
+            const int ewl = fdiv(le, K, lg.invK);
+            const uint32_t ij = L.er[it].ij;
+            // (M | 64 is a power of two: the walker's first lane is a shift; 24-bit products below, one VALU each)
+            bi = ((ewl << lg.lgM) + edge_i(ij)) << 2; bj = ((ewl << lg.lgM) + edge_j(ij)) << 2;
+        }
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             if (WG_ABLATE & 512) {   // (ablation: no gathers, the lane's own state at both ends, shifted)
@@ -2295,13 +2311,25 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     };
     auto spring = [&](int it, const Gath &g) {
         const int le = lane + 64 * it;
-        const EdgeRec e = L.er[it];
-        const int ewl = fdiv(le, K, lg.invK), ew = le - (int)__umul24(ewl, K);
-        // the muscle's rest length read unconditionally (clamped index), then selected by value: a select
-        // between the LDS slot and e.rest became a pointer select (flat load from a stack copy of e)
-        const bool mus = le < nE && ew < A;
-        const float xs = s_x[mus ? (int)__umul24(ewl, A) + ew : 0];
-        const float xr = mus ? xs : e.rest;
+        EdgeRec e;
+        float xr;
+        if constexpr (E8) {
+            // muscle flag, string flag and the muscle's slot in s_x from the record (0 for the other springs); k and c
+            // are the batch's two classes (wave-uniform), selected on the muscle bit
+            const uint32_t w = L.er[it].w;
+            const bool mus = (w & 0x40000000u) != 0u;
+            const float xs = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_x) + ((w >> 16) & 0xfcu));
+            xr = mus ? xs : L.er[it].rest;
+            e = EdgeRec{w, L.er[it].rest, mus ? b.kc[0] : b.kc[2], mus ? b.kc[1] : b.kc[3]};
+        } else {
+            e = L.er[it];
+            const int ewl = fdiv(le, K, lg.invK), ew = le - (int)__umul24(ewl, K);
+            // the muscle's rest length read unconditionally (clamped index), then selected by value: a select
+            // between the LDS slot and e.rest became a pointer select (flat load from a stack copy of e)
+            const bool mus = le < nE && ew < A;
+            const float xs = s_x[mus ? (int)__umul24(ewl, A) + ew : 0];
+            xr = mus ? xs : e.rest;
+        }
         if (le < nE) {
             if (WG_ABLATE & 1) {   // profiling builds only: no spring arithmetic
                 ts.put(le, xr + g.v[0] + g.v[3] + g.v[6] + g.v[9], g.v[1] + g.v[4] + g.v[7] + g.v[10],
@@ -2387,8 +2415,12 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
             float *gpo = WG_ST(b.pos, pl, 3), *gvo = WG_ST(b.vel, pl, 3), *gao = WG_ST(b.acc, pl, 3);
             gpo[0] = px; gpo[1] = py; gpo[2] = pz;
             gvo[0] = vx; gvo[1] = vy; gvo[2] = vz;
-            gao[0] = ax; gao[1] = ay; gao[2] = az;
-            if (b.contact) at_u32w(b.contact, pl) = (uint8_t)hit;
+            // wave-uniform: not in the steps of a multi-step call before its last (run(); the resident kernel stores
+            // after its last step only)
+            if (RES || kp.keep_aux) {
+                gao[0] = ax; gao[1] = ay; gao[2] = az;
+                if (b.contact) at_u32w(b.contact, pl) = (uint8_t)hit;
+            }
         }
         if (q == 0) {
             const uint32_t wg = (uint32_t)(w0 + wl);
@@ -2469,8 +2501,8 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
 // spills, NE 8 (up to 512 springs per 64 lanes) gets the 4-wave register budget.
 constexpr int lean_waves(int NE) { return NE >= 8 ? 4 : 6; }
 
-// One tile (64 / M walkers) per wave; waves never wait for one another.
-template <bool IN3D, int NE>
+// One tile (64 / M walkers) per wave; waves never wait for one another.  E8: the compact spring records (b.edges8).
+template <bool IN3D, int NE, bool E8>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(NE)))) void walker_step_lean(
     wg_batch b, KParams kp, const float *__restrict__ action, int action_cols, int action_stride, KOut o,
     LeanGeo lg) {
@@ -2486,13 +2518,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
 #endif
     STAMP(0);
     const LeanTile t = lean_tile_of(b, action, action_cols, lg, tile, lane);
-    LeanIn<NE> L;
+    LeanIn<NE, E8> L;
     // load-phase wave priority: this wave's HBM requests leave before other waves' arithmetic
     if (kp.prio) __builtin_amdgcn_s_setprio(2);
-    lean_load<NE>(b, kp, action, action_stride, t, lane, L);
+    lean_load<NE, E8>(b, kp, action, action_stride, t, lane, L);
     if (kp.prio) __builtin_amdgcn_s_setprio(0);
     STAMP(1);
-    lean_compute<IN3D, NE>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
+    lean_compute<IN3D, NE, false, E8>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
 }
 
 // NE = 1, the latency-bound small batches (Balance-4096: 512 waves, one per SIMD, the launch as long as its slowest
@@ -2504,12 +2536,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
 // by-value structs had cost three dependent scalar rounds before the first vector load.  Balance-4096, one launch per
 // step, same box, interleaved: round 5's prologue 5.33 us, the same arguments in one scalar round 5.01
 // (profiles/r06b_ab_balance4096_prologue.json), preloaded 2.5 % below that (profiles/r06e_ab_*).
-template <bool IN3D>
+// E8: `edges` is the batch's compact records (b.edges8) in the same preloaded slot.
+template <bool IN3D, bool E8>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(1)))) void walker_step_lean1(
-    float *pos, float *vel, const wg_edge *edges, const uint16_t *inc, int N, int M, int K, int wpw, int wpb, int nblkx,
+    float *pos, float *vel, const void *edges, const uint16_t *inc, int N, int M, int K, int wpw, int wpb, int nblkx,
     wg_batch b, KParams kp, const float *__restrict__ action, int action_cols, int action_stride, KOut o, LeanGeo lg) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    b.pos = pos; b.vel = vel; b.edges = edges; b.inc = inc; b.N = N; b.M = M; b.K = K;
+    b.pos = pos; b.vel = vel; b.inc = inc; b.N = N; b.M = M; b.K = K;
+    if (E8) b.edges8 = static_cast<const wg_edge8 *>(edges);
+    else b.edges = static_cast<const wg_edge *>(edges);
     lg.nblk = nblkx & 0x3fffffff; lg.wpw = wpw; lg.wpb = wpb;
     kp.prio = (int)((unsigned)nblkx >> 31);
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2522,12 +2557,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
 #endif
     STAMP(0);
     const LeanTile t = lean_tile_of(b, action, action_cols, lg, tile, lane);
-    LeanIn<1> L;
+    LeanIn<1, E8> L;
     if (kp.prio) __builtin_amdgcn_s_setprio(2);
-    lean_load<1>(b, kp, action, action_stride, t, lane, L);
+    lean_load<1, E8>(b, kp, action, action_stride, t, lane, L);
     if (kp.prio) __builtin_amdgcn_s_setprio(0);
     STAMP(1);
-    lean_compute<IN3D, 1>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
+    lean_compute<IN3D, 1, false, E8>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
 }
 
 // n_steps env steps in one launch (wg_rollout): the tile's static inputs (spring records, incidence lists, masses,
@@ -2535,7 +2570,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
 // step; each step reads its actions (the next step's are in flight while this one computes) and writes its
 // outputs; pos / vel / acc / contact / muscle x / steps go to HBM after the last step.  Same arithmetic as
 // walker_step_lean, step for step (bit-identical to n_steps single-step launches).
-template <bool IN3D, int NE>
+template <bool IN3D, int NE, bool E8>
 // (register budget: 5 waves per SIMD since the scalar wave index, 16 B of scratch at NE 3-4: 35.49 against 36.07 us per
 // step at 4, profiles/r04l_ab_resident.json)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4 : 5))) void walker_rollout_lean(
@@ -2549,9 +2584,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
     const int stamp_wave = tile;
 #endif
     const LeanTile t = lean_tile_of(b, action, action_cols, lg, tile, lane);
-    LeanIn<NE> L;
+    LeanIn<NE, E8> L;
     if (kp.prio) __builtin_amdgcn_s_setprio(2);
-    lean_load<NE>(b, kp, action, action_stride, t, lane, L);
+    lean_load<NE, E8>(b, kp, action, action_stride, t, lane, L);
     if (kp.prio) __builtin_amdgcn_s_setprio(0);
     {   // the incidence lists are static: into LDS once
         uint32_t *s_inc = reinterpret_cast<uint32_t *>(smem + wv * lg.slice + lg.off_inc);
@@ -2580,9 +2615,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
         // the same for the static inputs (the mass's 1/m, the springs' endpoint indices are re-derived per step)
         asm volatile("" : "+v"(L.mf), "+v"(L.io0), "+v"(L.io1), "+v"(L.lo), "+v"(L.hi), "+v"(L.stp));
 #pragma unroll
-        for (int it = 0; it < NE; it++) asm volatile("" : "+v"(L.er[it].ij), "+v"(L.er[it].rest), "+v"(L.er[it].k),
-                                                     "+v"(L.er[it].c));
-        lean_compute<IN3D, NE, true>(b, kp, os, lg, smem + wv * lg.slice, ts, ln, L, s == n_steps - 1);
+        for (int it = 0; it < NE; it++) {
+            if constexpr (E8) asm volatile("" : "+v"(L.er[it].w), "+v"(L.er[it].rest));
+            else asm volatile("" : "+v"(L.er[it].ij), "+v"(L.er[it].rest), "+v"(L.er[it].k), "+v"(L.er[it].c));
+        }
+        lean_compute<IN3D, NE, true, E8>(b, kp, os, lg, smem + wv * lg.slice, ts, ln, L, s == n_steps - 1);
         L.a = a_next;
         wave_sync();   // this step's LDS reads stay ahead of the next step's writes
     }
@@ -2812,8 +2849,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
         float *gpo = WG_ST(b.pos, pl, 3), *gvo = WG_ST(b.vel, pl, 3), *gao = WG_ST(b.acc, pl, 3);
         gpo[0] = px; gpo[1] = py; gpo[2] = pz;
         gvo[0] = vx; gvo[1] = vy; gvo[2] = vz;
-        gao[0] = ax; gao[1] = ay; gao[2] = az;
-        if (b.contact) at_u32w(b.contact, pl) = (uint8_t)hit;
+        if (kp.keep_aux) {   // (as the lean kernel)
+            gao[0] = ax; gao[1] = ay; gao[2] = az;
+            if (b.contact) at_u32w(b.contact, pl) = (uint8_t)hit;
+        }
         if (b.radius) b.radius[pl] = hit ? 3.0 : 1.0;   // gym/optimized_env.py:156,175
     }
     STAMP(4);
@@ -3026,6 +3065,7 @@ KParams make_kparams(const wg_params &p) {
     k.friction_mode = p.friction_mode;
     k.prio = env_int("WG_LEAN_PRIO", 1);
     k.xcd = env_int("WG_XCD", 3);   // both kernels (profiles/r03e_ab_canon.json, r03d_ab_ragged_window_xcd.json)
+    k.keep_aux = 1;
 
     k.dt2 = (float)(p.dt * p.dt);
     return k;
@@ -3144,6 +3184,13 @@ int env_int(const char *name, int dflt) {
 
 bool lean_enabled() { return env_int("WG_LEAN", 1) != 0; }
 
+// The compact spring records (wg_batch.edges8, ABI 15) are addressed by tile-relative lane roles: a lean launch reads
+// them only with the standard tile of 64 / M walkers per wave (small batches whose tiles lean_geo halves, and WG_LEAN_WPW,
+// keep the 16-B records).  WG_EDGE8=0 (read on every launch, like WG_LEAN) forces the 16-B records.
+bool use_edge8(const wg_batch *b, const LeanGeo &g) {
+    return b->edges8 != nullptr && g.wpw * b->M == 64 && env_int("WG_EDGE8", 1) != 0;
+}
+
 // The barrier-free kernels address their loads as SGPR base + 32-bit byte offset (at_u32): every array of the batch
 // must then span less than 4 GiB (positions 12 B and spring records 16 B per element dominate; M, K are maxima).
 bool u32_bytes(const wg_batch *b) {
@@ -3203,30 +3250,33 @@ int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const float *a,
     const int ne = (g.wpw * b->K + 63) / 64;
     // WG_LDS_PAD (diagnostic): extra LDS bytes per workgroup, to measure the kernel at lower occupancy
     const int lds = g.wpb * g.slice + std::max(0, env_int("WG_LDS_PAD", 0));
-#define WG_LAUNCH_LEAN(D3, NE_)                                                                                  \
-    WG_KLAUNCH((walker_step_lean<D3, NE_>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st, *b, kp, a, cols,  \
-               astride, kout(o), g)
-#define WG_LEAN_NE(D3)                                                         \
+    const bool e8 = use_edge8(b, g);
+#define WG_LAUNCH_LEAN(D3, NE_, E8_)                                                                             \
+    WG_KLAUNCH((walker_step_lean<D3, NE_, E8_>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st, *b, kp, a,   \
+               cols, astride, kout(o), g)
+#define WG_LEAN_NE(D3, E8_)                                                    \
     do {                                                                       \
-        if (ne == 2) WG_LAUNCH_LEAN(D3, 2);                                    \
-        else if (ne == 3) WG_LAUNCH_LEAN(D3, 3);                               \
-        else if (ne == 4) WG_LAUNCH_LEAN(D3, 4);                               \
-        else WG_LAUNCH_LEAN(D3, 8);                                            \
+        if (ne == 2) WG_LAUNCH_LEAN(D3, 2, E8_);                               \
+        else if (ne == 3) WG_LAUNCH_LEAN(D3, 3, E8_);                          \
+        else if (ne == 4) WG_LAUNCH_LEAN(D3, 4, E8_);                          \
+        else WG_LAUNCH_LEAN(D3, 8, E8_);                                       \
     } while (0)
-    if (ne <= 1) {   // (the NE = 1 entry with preloaded arguments)
-        if (in3d)
-            WG_KLAUNCH((walker_step_lean1<true>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st, b->pos, b->vel,
-                               b->edges, b->inc, b->N, b->M, b->K, g.wpw, g.wpb, (int)((unsigned)g.nblk | ((unsigned)(kp.xcd & 2) << 29) | ((unsigned)(kp.prio != 0) << 31)), *b,
-                               kp, a, cols, astride, kout(o), g);
-        else
-            WG_KLAUNCH((walker_step_lean1<false>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st, b->pos, b->vel,
-                               b->edges, b->inc, b->N, b->M, b->K, g.wpw, g.wpb, (int)((unsigned)g.nblk | ((unsigned)(kp.xcd & 2) << 29) | ((unsigned)(kp.prio != 0) << 31)), *b,
-                               kp, a, cols, astride, kout(o), g);
+    // (the NE = 1 entry with preloaded arguments; the compact records take the spring records' slot)
+#define WG_LAUNCH_LEAN1(D3, E8_)                                                                                 \
+    WG_KLAUNCH((walker_step_lean1<D3, E8_>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st, b->pos, b->vel,  \
+               (E8_) ? static_cast<const void *>(b->edges8) : static_cast<const void *>(b->edges), b->inc, b->N, \
+               b->M, b->K, g.wpw, g.wpb,                                                                         \
+               (int)((unsigned)g.nblk | ((unsigned)(kp.xcd & 2) << 29) | ((unsigned)(kp.prio != 0) << 31)), *b,  \
+               kp, a, cols, astride, kout(o), g)
+    if (ne <= 1) {
+        if (in3d) { if (e8) WG_LAUNCH_LEAN1(true, true); else WG_LAUNCH_LEAN1(true, false); }
+        else { if (e8) WG_LAUNCH_LEAN1(false, true); else WG_LAUNCH_LEAN1(false, false); }
     } else if (in3d) {
-        WG_LEAN_NE(true);
+        if (e8) WG_LEAN_NE(true, true); else WG_LEAN_NE(true, false);
     } else {
-        WG_LEAN_NE(false);
+        if (e8) WG_LEAN_NE(false, true); else WG_LEAN_NE(false, false);
     }
+#undef WG_LAUNCH_LEAN1
 #undef WG_LEAN_NE
 #undef WG_LAUNCH_LEAN
     const hipError_t e = hipGetLastError();
@@ -3239,18 +3289,20 @@ int launch_lean_rollout(const wg_batch *b, const KParams &kp, bool in3d, const f
     const int blocks = lean_blocks(b, g);
     const int ne = (g.wpw * b->K + 63) / 64;
     const int lds = g.wpb * g.slice;
-#define WG_LAUNCH_RO(D3, NE_)                                                                                    \
-    hipLaunchKernelGGL((walker_rollout_lean<D3, NE_>), dim3(blocks), dim3(64 * g.wpb), lds, st, *b, kp, a, cols, \
-                       astride, astep, kout(o), n_steps, g)
-#define WG_RO_NE(D3)                                                                                             \
+    const bool e8 = use_edge8(b, g);
+#define WG_LAUNCH_RO(D3, NE_, E8_)                                                                               \
+    hipLaunchKernelGGL((walker_rollout_lean<D3, NE_, E8_>), dim3(blocks), dim3(64 * g.wpb), lds, st, *b, kp, a,  \
+                       cols, astride, astep, kout(o), n_steps, g)
+#define WG_RO_NE(D3, E8_)                                                                                        \
     do {                                                                                                         \
-        if (ne <= 1) WG_LAUNCH_RO(D3, 1);                                                                        \
-        else if (ne == 2) WG_LAUNCH_RO(D3, 2);                                                                   \
-        else if (ne == 3) WG_LAUNCH_RO(D3, 3);                                                                   \
-        else if (ne == 4) WG_LAUNCH_RO(D3, 4);                                                                   \
-        else WG_LAUNCH_RO(D3, 8);                                                                                \
+        if (ne <= 1) WG_LAUNCH_RO(D3, 1, E8_);                                                                   \
+        else if (ne == 2) WG_LAUNCH_RO(D3, 2, E8_);                                                              \
+        else if (ne == 3) WG_LAUNCH_RO(D3, 3, E8_);                                                              \
+        else if (ne == 4) WG_LAUNCH_RO(D3, 4, E8_);                                                              \
+        else WG_LAUNCH_RO(D3, 8, E8_);                                                                           \
     } while (0)
-    if (in3d) WG_RO_NE(true); else WG_RO_NE(false);
+    if (in3d) { if (e8) WG_RO_NE(true, true); else WG_RO_NE(true, false); }
+    else { if (e8) WG_RO_NE(false, true); else WG_RO_NE(false, false); }
 #undef WG_RO_NE
 #undef WG_LAUNCH_RO
     const hipError_t e = hipGetLastError();
@@ -3332,7 +3384,10 @@ int dispatch(const wg_batch *b, const KParams &kp, bool in3d, const float *a, in
 
 int run(const wg_batch *b, const wg_params *p, const float *action, int32_t cols, int32_t astride,
         int64_t astep, const wg_outputs *o, int32_t n_steps, const int32_t *plan, int32_t plan_blocks,
-        hipStream_t stream, bool step, bool resident = false, bool check_only = false, int s_first = 0) {
+        hipStream_t stream, bool step, bool resident = false, bool check_only = false, int s_first = 0,
+        int s_total = 0) {
+    // s_total: the steps of the caller's whole call when this is one slice of it (wg_run_ranges issues one step per
+    // call), 0 = s_first + n_steps, < 0 = every step keeps its acc / contact stores (wg_time_step)
     int rc = validate(b);
     if (rc) return rc;
     if (!p) return fail(WG_EINVAL, "null params");
@@ -3344,7 +3399,7 @@ int run(const wg_batch *b, const wg_params *p, const float *action, int32_t cols
     if (b->ragged && (!plan || plan_blocks <= 0)) return fail(WG_EINVAL, "ragged batch needs a plan");
     wg_outputs out = o ? *o : wg_outputs{};
     if (out.obs && out.obs_stride <= 0) return fail(WG_EINVAL, "obs_stride must be > 0");
-    const KParams kp = make_kparams(*p);
+    KParams kp = make_kparams(*p);
     const Geo g = b->ragged ? ragged_geo(b) : uniform_geo(b, out.obs ? out.obs_stride : 0, step && p->pair_mode != 0);
     if (g.W > g.threads) return fail(WG_ERANGE, "more than %d walkers per workgroup", g.threads);
     const int blocks = b->ragged ? plan_blocks : (b->N + g.W - 1) / g.W;
@@ -3377,7 +3432,11 @@ int run(const wg_batch *b, const wg_params *p, const float *action, int32_t cols
     if (resident && use_lean && p->pair_mode == 0 && !extras)   // one launch for every step, state in registers
         return launch_lean_rollout(b, kp, p->in3d != 0, action, cols, astride, action ? astep : 0, out, n_steps, lg,
                                    stream);
+    // acc and contact are read by nothing on the step path and overwritten by the next step: only the call's last step
+    // stores them (the info kernel reads acc: with its outputs requested every step does)
+    const int s_last = (s_total > 0 ? s_total : s_first + n_steps) - 1;
     for (int s = s_first; s < s_first + n_steps; s++) {   // (s_first: wg_run_ranges issues one step per call)
+        kp.keep_aux = (s_total < 0 || s >= s_last || extras) ? 1 : 0;
         wg_outputs os = out;
         if (os.obs) os.obs += s * os.obs_step;
         if (os.reward) os.reward += s * os.out_step;
@@ -3457,7 +3516,7 @@ int wg_run_ranges(const wg_range *ranges, int32_t n, const wg_params *p, const f
     auto issue = [&](int i, int s) -> int {
         const wg_range &r = ranges[i];
         return run(r.batch, p, action ? action + r.action_offset : nullptr, action_cols, action_stride, action_step,
-                   r.outputs, 1, r.plan, r.plan_blocks, r.stream, true, false, false, s);
+                   r.outputs, 1, r.plan, r.plan_blocks, r.stream, true, false, false, s, n_steps);
     };
     // A launch-time failure (hipGetLastError after a launch) can still stop the issue part-way, after other ranges or
     // steps went out: the call then returns that error with a partially stepped batch, but the side streams are joined
@@ -3521,7 +3580,7 @@ int wg_time_step(const wg_batch *b, const wg_params *p, const float *action, int
     for (int s = 0; s < n_steps && !rc; s++) {
         g_kev_start = ev[2 * s]; g_kev_stop = ev[2 * s + 1];
         rc = run(b, p, action, action_cols, action_stride, action_step, o, 1, plan, plan_blocks, stream, true, false,
-                 false, s);
+                 false, s, -1);
     }
     g_kev_start = g_kev_stop = nullptr;
     double total = 0.0;

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .layout import HostLayout, default_radius
+from .layout import HostLayout, default_radius, refresh_edges8, set_springs
 
 
 def _to_dev(a: np.ndarray, device) -> torch.Tensor:
@@ -50,6 +50,9 @@ class DeviceBatch:
         self.acc = _to_dev(host.acc, dv)
         self.mass = _to_dev(host.mass, dv)
         self.edges = _to_dev(host.edges, dv)
+        if host.edges8 is None:   # (a layout built without pack())
+            refresh_edges8(host)
+        self._upload_edges8()
         self.inc = _to_dev(host.inc, dv) if host.E else None
         self.inc_off = _to_dev(host.inc_off, dv)
         self.muscle_x = _to_dev(host.muscle_x, dv)
@@ -77,6 +80,30 @@ class DeviceBatch:
         self.ragged_kind = 0
         self.version = 0   # bumped by every host-side write of the state (load_state_dict, setters, reset)
         self.replan(wave_ok)
+
+    def _upload_edges8(self) -> None:
+        """The host layout's compact spring records (HostLayout.edges8 / kc) on the device, or none."""
+        host = self.host
+        if host.edges8 is None:
+            self.edges8, self.kc = None, (0.0, 0.0, 0.0, 0.0)
+        else:
+            self.edges8, self.kc = _to_dev(host.edges8, self.device), tuple(float(x) for x in host.kc)
+
+    def set_springs(self, ei=None, ej=None, rest=None, k=None, c=None, flags=None) -> None:
+        """layout.set_springs on the host layout (the spring records in the STORED order), then the device copies: the
+        16-byte records, the incidence lists after a change of endpoints, and the compact records (rebuilt, or dropped
+        when the batch is no longer eligible).  Bumps `version` and replaces `struct`, so cached walker-range views
+        and prepared runs are rebuilt."""
+        topo = set_springs(self.host, ei=ei, ej=ej, rest=rest, k=k, c=c, flags=flags)
+        if self.E:
+            self.edges.copy_(_to_dev(self.host.edges, self.device))
+        if topo:
+            if self.inc is not None:
+                self.inc.copy_(_to_dev(self.host.inc, self.device))
+            self.inc_off.copy_(_to_dev(self.host.inc_off, self.device))
+        self._upload_edges8()
+        self.version += 1
+        self.struct = self._make_struct()
 
     def replan(self, wave_ok: bool) -> None:
         """Choose the launch plan for parameters that can (wave_ok) or cannot use the barrier-free wave kernel.
@@ -161,7 +188,8 @@ class DeviceBatch:
             muscle_x=self._p(self.muscle_x), muscle_bounds=self._p(self.muscle_bounds),
             muscle_stride=self._p(self.muscle_stride), steps=self._p(self.steps), contact=self._p(self.contact),
             pinned=self._p(self.pinned), charge=self._p(self.charge), radius=self._p(self.radius),
-            bounce_set=self._p(self.bounce_set))
+            bounce_set=self._p(self.bounce_set),
+            edges8=self._p(self.edges8) if not r else None, kc=(C.c_float * 4)(*self.kc))
 
     def sub_struct(self, w0: int, w1: int) -> _lib.WgBatch:
         """A WgBatch view of walkers [w0, w1) of a uniform batch: the same device memory, pointers offset
@@ -186,7 +214,10 @@ class DeviceBatch:
             muscle_stride=self._p(self.muscle_stride) if A == 0 else off(self.muscle_stride, A * w0),
             steps=off(self.steps, w0), contact=off(self.contact, M * w0), pinned=off(self.pinned, M * w0),
             charge=off(self.charge, M * w0), radius=off(self.radius, M * w0), row=None,
-            bounce_set=off(self.bounce_set, M * w0))
+            bounce_set=off(self.bounce_set, M * w0),
+            # the compact records hold tile-relative lane roles: only a range that starts on a tile (64 / M walkers)
+            edges8=off(self.edges8, 2 * K * w0) if self.edges8 is not None and w0 % (64 // M) == 0 else None,
+            kc=(C.c_float * 4)(*self.kc))
 
     def launch_geometry(self) -> dict:
         info = _lib.WgLaunchInfo()

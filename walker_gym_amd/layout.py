@@ -6,6 +6,8 @@ ordered by walker so that any contiguous walker range is a contiguous byte range
 
   per mass   pos, vel, acc (old_a)  f32[P,3];  mass f32[P];  contact u8[P]
   per edge   edges: 16-B records {ij = i | j<<16 | string<<31 (walker-local), rest, k, c} [E]
+             edges8: 8-B records {w = lane roles in the wave tile | muscle<<30 | string<<31, rest} [E] beside them
+             for uniform M | 64 batches with one (k, c) per spring class (pack_edges8; the lean kernels' read)
   per walker-edge-end   inc u16[2E] = (edge<<1 | end) sorted by (mass, edge, end);
              inc_off u16[P+N] (M_w+1 offsets per walker) — the deterministic accumulation order
   per muscle muscle_x f32[U]; bounds (lo, hi) = (f32(originx*minl), f32(originx*maxl)) f32[U,2];
@@ -61,6 +63,11 @@ class HostLayout:
     row: Optional[np.ndarray] = None
     mass_perm: Optional[np.ndarray] = None
     muscle_perm: Optional[np.ndarray] = None
+    # the compact 8-byte spring records of an eligible batch (pack_edges8: uniform, M | 64, one (k, c) per spring class)
+    # and the classes' (k_muscle, c_muscle, k_other, c_other); None / zeros otherwise.  Derived from `edges`: whatever
+    # rewrites the spring records goes through set_springs, which rebuilds or drops them
+    edges8: Optional[np.ndarray] = None   # uint32 [E, 2]: lane roles w, rest (float bits)
+    kc: Optional[np.ndarray] = None       # float32 [4]
     extra: Dict[str, np.ndarray] = field(default_factory=dict)
 
     @property
@@ -149,6 +156,7 @@ def pack(spec: Dict[str, np.ndarray], mx: Optional[np.ndarray] = None, steps: Op
             row, mass_perm, muscle_perm = order.astype(np.int32), spec["_mass_perm"], spec["_muscle_perm"]
     lay = _pack(spec, spec.get("mx"), spec.get("steps"))
     lay.row, lay.mass_perm, lay.muscle_perm = row, mass_perm, muscle_perm
+    refresh_edges8(lay)
     return lay
 
 
@@ -208,6 +216,111 @@ def _pack(spec: Dict[str, np.ndarray], mx: Optional[np.ndarray], steps: Optional
         radius=_per_mass_f64(spec, "radius", int(mass_off[-1])),
         bounce_set=_bounce_set(spec, int(mass_off[-1])),
     )
+
+
+EDGE8_MUSCLE = np.uint32(1 << 30)
+EDGE8_STRING = np.uint32(1 << 31)
+
+
+def edge8_classes(edges: np.ndarray, K: int, A: int):
+    """The (k, c) classes of a uniform batch's spring records (uint32 [E, 4]) as float32 bit patterns:
+    (k_muscle, c_muscle, k_other, c_other), or None when the muscles (each walker's first A springs) do not all share
+    one (k, c) or the other springs do not (bit patterns compared: -0.0 is not +0.0).  An empty class takes the other
+    class's pair (zeros when there is no spring at all)."""
+    edges = np.asarray(edges, np.uint32).reshape(-1, 4)
+    mus = (np.arange(len(edges)) % max(K, 1)) < A
+    out = []
+    for sel in (mus, ~mus):
+        kc = edges[sel][:, 2:4]
+        if len(kc) == 0:
+            out.append(None)
+            continue
+        if np.any(kc != kc[0]):
+            return None
+        out.append((int(kc[0, 0]), int(kc[0, 1])))
+    if out[0] is None and out[1] is None:
+        out = [(0, 0), (0, 0)]
+    m, o = (out[0] or out[1]), (out[1] or out[0])
+    return np.array([m[0], m[1], o[0], o[1]], np.uint32)
+
+
+def pack_edges8(lay: "HostLayout"):
+    """The compact 8-byte spring records of a uniform batch with M | 64 (include/walker_hip.h wg_edge8) and its (k, c)
+    classes: (edges8 uint32 [E, 2], kc float32 [4]), or None when the batch is not eligible (ragged, M not a divisor
+    of 64 in 4..64, no spring, more than 64 muscles per tile, or more than one (k, c) per class).  Record e of stored
+    walker w holds the lane roles inside w's tile, the 64 / M walkers starting at a multiple of 64 / M:
+    w = bi | bj << 8 | xoff << 16 | muscle << 30 | string << 31 with bi, bj = ((w % wpw) * M + i, j) * 4 and, for a
+    muscle u, xoff = ((w % wpw) * A + u) * 4; rest as in the 16-byte record."""
+    M, K, A = lay.M, lay.K, lay.A
+    if lay.ragged or M < 4 or M > 64 or 64 % M or K < 1 or lay.E == 0:
+        return None
+    wpw = 64 // M
+    if wpw * A > 64:
+        return None
+    kc = edge8_classes(lay.edges, K, A)
+    if kc is None:
+        return None
+    e = np.arange(lay.E, dtype=np.int64)
+    wt, k = (e // K) % wpw, e % K
+    ij = lay.edges[:, 0].astype(np.int64)
+    i, j = ij & 0x7fff, (ij >> 16) & 0x7fff
+    mus = k < A
+    w = ((wt * M + i) * 4) | (((wt * M + j) * 4) << 8) | (np.where(mus, (wt * A + k) * 4, 0) << 16)
+    w = w.astype(np.uint32) | np.where(mus, EDGE8_MUSCLE, np.uint32(0)) | (lay.edges[:, 0] & EDGE8_STRING)
+    return np.ascontiguousarray(np.stack([w, lay.edges[:, 1]], axis=1), np.uint32), kc.view(f32).copy()
+
+
+def refresh_edges8(lay: "HostLayout") -> None:
+    """lay.edges8 / lay.kc from lay.edges as they are now: the compact records, or None when not eligible."""
+    packed = pack_edges8(lay)
+    lay.edges8, lay.kc = (None, None) if packed is None else packed
+
+
+def set_springs(lay: "HostLayout", ei=None, ej=None, rest=None, k=None, c=None, flags=None) -> bool:
+    """Rewrite the spring records of a packed batch in its STORED spring order (arrays of E entries or scalars; None =
+    unchanged): endpoints ei / ej (walker-local mass indices), Skeleton rest lengths, stiffness k, damping c, string
+    flags.  Rebuilds the 16-byte records, after a change of endpoints the incidence lists, and the compact records
+    (dropped when the batch is no longer eligible, e.g. a third (k, c) class).  Muscle state is left as it is.
+    Returns True when the endpoints changed (inc / inc_off were rebuilt)."""
+    E = lay.E
+    ed = np.asarray(lay.edges, np.uint32).reshape(-1, 4).copy()
+
+    def full(v, dtype):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype), (E,)))
+
+    topo = ei is not None or ej is not None
+    if topo or flags is not None:
+        i = (ed[:, 0] & np.uint32(0x7fff)) if ei is None else full(ei, np.int64).astype(np.uint32)
+        j = ((ed[:, 0] >> np.uint32(16)) & np.uint32(0x7fff)) if ej is None else full(ej, np.int64).astype(np.uint32)
+        st = (ed[:, 0] >> np.uint32(31)) if flags is None else (full(flags, np.uint8) & 1).astype(np.uint32)
+        if topo:
+            lay.inc, lay.inc_off = incidence(i.astype(np.int64), j.astype(np.int64), lay.mass_off, lay.edge_off)
+        ed[:, 0] = i | (j << np.uint32(16)) | (st << np.uint32(31))
+    for col, v in ((1, rest), (2, k), (3, c)):
+        if v is not None:
+            ed[:, col] = full(v, f32).view(np.uint32)
+    lay.edges = np.ascontiguousarray(ed, np.uint32)
+    refresh_edges8(lay)
+    return topo
+
+
+def unpack_edges8(edges8: np.ndarray, M: int, K: int, A: int) -> Dict[str, np.ndarray]:
+    """Inverse of pack_edges8's records (tests, diagnostics): per spring the tile-relative byte addresses bi, bj, xoff,
+    the walker-local endpoints ei, ej, the tile-local walker wt, rest (float32) and the muscle / string flags."""
+    w = np.asarray(edges8, np.uint32).reshape(-1, 2)[:, 0].astype(np.int64)
+    bi, bj, xoff = w & 0xff, (w >> 8) & 0xff, (w >> 16) & 0xff
+    return dict(bi=bi, bj=bj, xoff=xoff, wt=(bi >> 2) // M, ei=(bi >> 2) % M, ej=(bj >> 2) % M,
+                rest=np.asarray(edges8, np.uint32).reshape(-1, 2)[:, 1].copy().view(f32),
+                muscle=((w >> 30) & 1).astype(bool), string=((w >> 31) & 1).astype(bool))
+
+
+def compact_bytes_per_walker_step(M, K, A, obs_floats, info: bool = True, contact: bool = True, last: bool = False):
+    """layout_bytes_per_walker_step for a step that reads the compact spring records (8 B instead of 16 B per spring)
+    and, unless it is the `last` step of its call, stores neither acc (12 B per mass) nor contact (1 B per mass)."""
+    b = layout_bytes_per_walker_step(M, K, A, obs_floats, info=info, contact=contact) - 8 * K
+    if not last:
+        b = b - 12 * M - (M if contact else 0)
+    return b
 
 
 def _per_mass_f64(spec, key: str, P: int):
