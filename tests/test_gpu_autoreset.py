@@ -1,0 +1,387 @@
+"""Auto-reset fused into the lean step kernels (ABI 16, BatchedPhysicsEnv.enable_auto_reset): a walker whose step ends
+its episode is back at the episode-start snapshot, with its reset noise and its fresh observation row, when the launch
+that stepped it returns.
+
+The reference is the C oracle (the reference restated), composed in this file exactly as the semantics are defined:
+Oracle.step; select the walkers (done, or a non-finite state); for those, pos / vel / acc / mx = the snapshot, v += the
+noise row episodes % rows (x, y, and z if in3d; one float32 add), steps = 0, episodes += 1; their obs rows =
+Oracle.observe() of that state.  reward / done / centroid / energy stay the terminal step's, contact too.  Everything is
+compared bit for bit (test_gpu_parity._close: rtol = atol = 0, NaN == NaN).
+
+Shapes: the smallest that reach each lean path — canonical x 2051 (M = 16, four walkers per wave, NE = 3, a partial last
+tile, the compact 8-byte spring records; also with WG_EDGE8=0), canonical x 37 (tiles halved to one walker per wave: the
+NE = 1 kernel with preloaded arguments, 16-byte records), Balance-v0 x 8195 (M = 4, 16 walkers per wave), Balance-v0 x
+2052 (M = 4 on the NE = 1 kernel with four walkers per wave) and Box-v0 in 3-D x 4099 (noise on z).  max_steps = 5 with
+the walkers' step counters staggered by w % 5, 12 steps, two noise rows, and ~1 % of the walkers with a snapshot below
+ground - 50, which therefore reset at every step."""
+import functools
+
+import numpy as np
+import pytest
+
+from conftest import gpu_available
+from test_gpu_parity import _close
+from test_gpu_diverged import _diverge
+
+pytestmark = pytest.mark.gpu
+
+T = 12
+MAX_STEPS = 5
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    if not gpu_available():
+        pytest.skip("no ROCm GPU")
+
+
+# name -> (spec builder, in3d, walkers per wave the lean launch uses)
+def _specs():
+    from walker_gym_amd.synthetic import canonical_walkers
+    from walker_gym_amd.walker import balance_spec, box_spec
+    return {
+        "canonical2051": (lambda: canonical_walkers(2051, seed=3), 1, 4),
+        "canonical37": (lambda: canonical_walkers(37, seed=4), 1, 1),
+        "balance8195": (lambda: balance_spec(8195), 0, 16),
+        "balance2052": (lambda: balance_spec(2052), 0, 4),
+        "box3d4099": (lambda: box_spec(4099), 1, 8),
+    }
+
+
+SHAPES = ["canonical2051", "canonical37", "balance8195", "balance2052", "box3d4099"]
+
+
+@functools.lru_cache(maxsize=None)
+def _config(name):
+    """The inputs of one shape: spec (staggered step counters, ~1 % of the walkers sunk below ground - 50), params,
+    actions, the two-row noise pool."""
+    build, in3d, wpw = _specs()[name]
+    spec = dict(build())
+    mo = np.asarray(spec["mass_off"])
+    N = len(mo) - 1
+    rng = np.random.default_rng(11)
+    pos = np.array(spec["pos"], np.float32).reshape(-1, 3).copy()
+    sunk = rng.permutation(N)[:max(2, N // 100)]
+    for w in sunk:
+        a, b = mo[w], mo[w + 1]
+        pos[a:b, 1] += np.float32(-80.0) - pos[a:b, 1].mean()
+    spec["pos"] = pos
+    spec["steps"] = (np.arange(N) % MAX_STEPS).astype(np.int32)
+    A = max(1, int(np.max(spec["n_muscles"])))
+    acts = rng.uniform(-1, 1, (T, N, A)).astype(np.float32)
+    pool = (rng.standard_normal((2, len(pos), 3)) * 0.5).astype(np.float32)
+    params = dict(in3d=in3d, max_steps=MAX_STEPS)
+    return dict(spec=spec, params=params, acts=acts, pool=pool, N=N, A=A, wpw=wpw, sunk=sunk)
+
+
+class _Composed:
+    """Oracle.step + the host-composed reset of the selected walkers (the semantics, spelled out)."""
+
+    def __init__(self, spec, params, bits, pool, snapshot=None):
+        from oracle.oracle import Oracle
+        self.orc = o = Oracle(spec, params, n_threads=8)
+        self.bits, self.pool, self.in3d = bits, pool, int(params["in3d"])
+        src = o if snapshot is None else snapshot
+        self.init = {k: np.array(getattr(src, k), copy=True) for k in ("pos", "vel", "acc", "mx")}
+        self.episodes = np.zeros(o.N, np.int32)
+        self.Ms = np.diff(o.mass_off)
+        self.As = np.asarray(o.n_muscles)
+        self.final_obs = np.zeros((o.N, o.obs_stride), np.float32)
+
+    def step(self, act):
+        from oracle.oracle import nonfinite
+        o = self.orc
+        out = o.step(act)
+        sel = np.zeros(o.N, bool)
+        if self.bits & 1:
+            sel |= out["done"].astype(bool)
+        if self.bits & 2:
+            sel |= nonfinite(o.pos, o.vel, o.acc, o.mass_off).astype(bool)
+        out["steps_out"] = o.steps.copy()                       # the terminal step's counter
+        self.final_obs[sel] = out["obs"][sel]
+        if sel.any():
+            ms, us = np.repeat(sel, self.Ms), np.repeat(sel, self.As)
+            o.pos[ms] = self.init["pos"][ms]
+            o.acc[ms] = self.init["acc"][ms]
+            o.mx[us] = self.init["mx"][us]
+            vel = self.init["vel"][ms].copy()
+            if self.pool is not None:
+                row = np.repeat(self.episodes % self.pool.shape[0], self.Ms)[ms]
+                nz = self.pool[row, np.flatnonzero(ms)]
+                d = 3 if self.in3d else 2
+                vel[:, :d] = vel[:, :d] + nz[:, :d]             # float32 + float32, as walker_reset_kernel
+            o.vel[ms] = vel
+            o.steps[sel] = 0
+            self.episodes[sel] += 1
+            out["obs"][sel] = o.observe()["obs"][sel]
+        out["reset"] = sel.astype(np.uint8)
+        return out
+
+    def state(self):
+        o = self.orc
+        return dict(pos=o.pos.copy(), vel=o.vel.copy(), acc=o.acc.copy(), mx=o.mx.copy(), steps=o.steps.copy(),
+                    contact=o.contact.copy(), episodes=self.episodes.copy(), final_obs=self.final_obs.copy())
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name):
+    """Every step's outputs and state of the composed oracle for one shape (computed once, shared, never modified),
+    after checking that the run exercises what the tests are about."""
+    cfg = _config(name)
+    ref = _Composed(cfg["spec"], cfg["params"], 1, cfg["pool"])
+    steps = []
+    rows_used = set()
+    for t in range(T):
+        ep_before = ref.episodes.copy()
+        out = ref.step(cfg["acts"][t])
+        rows_used |= set((ep_before[out["reset"] == 1] % 2).tolist())
+        steps.append(dict(out=out, state=ref.state()))
+    resets = np.stack([s["out"]["reset"] for s in steps])
+    assert (resets.sum(0) >= 2).all(), "every walker resets at least twice"
+    assert resets[:, cfg["sunk"]].all(), "the sunk walkers reset at every step"
+    assert rows_used == {0, 1}, "both noise rows are used"
+    if cfg["wpw"] > 1:   # a wave tile with a reset and a non-reset walker in the same step
+        w = cfg["wpw"]
+        n_full = (cfg["N"] // w) * w
+        tiles = resets[:, :n_full].reshape(T, -1, w).sum(2)
+        assert ((tiles > 0) & (tiles < w)).any()
+    return steps
+
+
+def _env(name, on=("done",), final_obs=True, **kw):
+    from walker_gym_amd.batched_env import BatchedPhysicsEnv
+    cfg = _config(name)
+    env = BatchedPhysicsEnv(cfg["spec"], **cfg["params"], **kw)
+    env.enable_auto_reset(on=on, noise=cfg["pool"], final_obs=final_obs)
+    geo = env.launch_geometry()
+    assert geo["walkers_per_block"] // (geo["threads"] // 64) == cfg["wpw"]
+    return env, cfg
+
+
+def _check_state(env, st):
+    _close(env.pos.cpu().numpy(), st["pos"])
+    _close(env.vel.cpu().numpy(), st["vel"])
+    _close(env.acc.cpu().numpy(), st["acc"])
+    _close(env.muscle_x.cpu().numpy(), st["mx"])
+    assert np.array_equal(env.steps.cpu().numpy(), st["steps"])
+    assert np.array_equal(env.contact.cpu().numpy(), st["contact"])
+    assert np.array_equal(env.batch.episodes.cpu().numpy(), st["episodes"])
+
+
+def _check_outputs(env, out, st=None):
+    info = env.info()
+    _close(env.obs.cpu().numpy(), out["obs"])
+    _close(env.reward.cpu().numpy(), out["reward"])
+    _close(info["centroid_position"].cpu().numpy(), out["centroid"])
+    _close(info["total_energy"].cpu().numpy(), out["energy"])
+    assert np.array_equal(env.done.cpu().numpy().astype(np.uint8), out["done"])
+    assert np.array_equal(info["reset"].cpu().numpy().astype(np.uint8), out["reset"])
+    if st is not None:
+        assert np.array_equal(info["episodes"].cpu().numpy(), st["episodes"])
+        _close(info["final_obs"].cpu().numpy(), st["final_obs"])
+
+
+def _step_loop(name, monkeypatch=None, edge8=True):
+    import torch
+    if not edge8:
+        monkeypatch.setenv("WG_EDGE8", "0")
+    ref = _reference(name)
+    env, cfg = _env(name)
+    for t in range(T):
+        env.step(cfg["acts"][t])
+        torch.cuda.synchronize()
+        _check_state(env, ref[t]["state"])
+        _check_outputs(env, ref[t]["out"], ref[t]["state"])
+
+
+@pytest.mark.parametrize("name", SHAPES)
+def test_step_loop_against_composed_oracle(name):
+    """Case 1: T single step() calls: state, obs, reward, done, centroid, energy, steps, reset, episodes, final_obs."""
+    _step_loop(name)
+
+
+def test_step_loop_16_byte_records(monkeypatch):
+    """Case 1 on the canonical shape with the 16-byte spring records (WG_EDGE8=0)."""
+    _step_loop("canonical2051", monkeypatch, edge8=False)
+
+
+@pytest.mark.parametrize("lanes", [1, 2])
+@pytest.mark.parametrize("name", SHAPES)
+def test_run_against_composed_oracle(name, lanes):
+    """Case 2: run(actions, T) in one call, one walker range and two: the multi-step path (no acc / contact stores
+    before the last step) and the walker-range views (sub_struct: the snapshot, the counters and each noise row at
+    the range's first walker).  Every step's reward / done / reset through record buffers, then the final state; a plain
+    run for the last step's outputs and the terminal rows."""
+    import torch
+    ref = _reference(name)
+    env, cfg = _env(name)
+    acts = torch.from_numpy(cfg["acts"]).to(env.device)
+    N = cfg["N"]
+    rec = dict(reward=torch.zeros((T, N), device=env.device), done=torch.zeros((T, N), dtype=torch.uint8, device=env.device),
+               reset=torch.full((T, N), 7, dtype=torch.uint8, device=env.device))
+    env.run(acts, T, lanes=lanes, record=rec)
+    torch.cuda.synchronize()
+    _check_state(env, ref[-1]["state"])
+    _close(env.obs.cpu().numpy(), ref[-1]["out"]["obs"])
+    _close(rec["reward"].cpu().numpy(), np.stack([s["out"]["reward"] for s in ref]))
+    assert np.array_equal(rec["done"].cpu().numpy(), np.stack([s["out"]["done"] for s in ref]))
+    assert np.array_equal(rec["reset"].cpu().numpy(), np.stack([s["out"]["reset"] for s in ref]))
+    assert "reset" not in env.info()
+    env2, _ = _env(name)
+    env2.run(acts, T, lanes=lanes)
+    torch.cuda.synchronize()
+    _check_state(env2, ref[-1]["state"])
+    _check_outputs(env2, ref[-1]["out"], ref[-1]["state"])
+
+
+def test_captured_graph_against_composed_oracle():
+    """graph(actions, T) over two walker ranges: one replay advances the batch T steps, resets included."""
+    import torch
+    ref = _reference("canonical2051")
+    env, cfg = _env("canonical2051")
+    g = env.graph(torch.from_numpy(cfg["acts"]).to(env.device), T, lanes=2)
+    torch.cuda.synchronize()
+    assert int(env.batch.episodes.max()) == 0               # capture runs nothing
+    g.replay()
+    torch.cuda.synchronize()
+    _check_state(env, ref[-1]["state"])
+    _check_outputs(env, ref[-1]["out"], ref[-1]["state"])
+    env.disable_auto_reset()
+    with pytest.raises(RuntimeError, match="stale"):
+        g.replay()
+
+
+@pytest.mark.parametrize("name", ["canonical2051", "balance2052"])
+def test_resident_rollout_falls_back_to_steps(name):
+    """Case 3: rollout(resident=True) with auto-reset runs as per-step launches and equals the step loop's reference."""
+    import torch
+    ref = _reference(name)
+    env, cfg = _env(name)
+    assert env.resident_ok()
+    reset = torch.full((T, cfg["N"]), 7, dtype=torch.uint8, device=env.device)
+    obs, rew, done = env.rollout(torch.from_numpy(cfg["acts"]).to(env.device), resident=True, reset_out=reset)
+    torch.cuda.synchronize()
+    _close(obs.cpu().numpy(), np.stack([s["out"]["obs"] for s in ref]))
+    _close(rew.cpu().numpy(), np.stack([s["out"]["reward"] for s in ref]))
+    assert np.array_equal(done.cpu().numpy(), np.stack([s["out"]["done"] for s in ref]))
+    assert np.array_equal(reset.cpu().numpy(), np.stack([s["out"]["reset"] for s in ref]))
+    _check_state(env, ref[-1]["state"])
+
+
+@pytest.mark.parametrize("name", ["canonical2051", "balance8195"])
+def test_policy_loop_graph_equals_eager_steps(name):
+    """Case 4: a closed loop with a row-wise linear policy, captured as HIP graphs over two walker ranges, equals the
+    eager step() loop with the same policy."""
+    import torch
+    A = _config(name)["A"]
+
+    def policy(obs, t):
+        return (obs[:, :A] * 0.01 - obs[:, A:2 * A] * 0.02).contiguous()
+
+    a, cfg = _env(name)
+    b, _ = _env(name)
+    a.observe()
+    b.observe()
+    a.policy_loop(policy, T, lanes=2, graph=True)
+    for t in range(T):
+        b.step(policy(b.obs, t))
+    torch.cuda.synchronize()
+    assert int(b.batch.episodes.min()) >= 2
+    for k in ("pos", "vel", "acc", "muscle_x"):
+        _close(getattr(a, k).cpu().numpy(), getattr(b, k).cpu().numpy())
+    _close(a.obs.cpu().numpy(), b.obs.cpu().numpy())
+    _close(a.reward.cpu().numpy(), b.reward.cpu().numpy())
+    _close(a.final_obs.cpu().numpy(), b.final_obs.cpu().numpy())
+    for k in ("steps",):
+        assert np.array_equal(getattr(a, k).cpu().numpy(), getattr(b, k).cpu().numpy())
+    assert np.array_equal(a.batch.episodes.cpu().numpy(), b.batch.episodes.cpu().numpy())
+    assert np.array_equal(a.reset_out.cpu().numpy(), b.reset_out.cpu().numpy())
+    assert np.array_equal(a.done.cpu().numpy(), b.done.cpu().numpy())
+
+
+@pytest.mark.parametrize("name", ["canonical2051", "balance2052"])
+def test_nonfinite_walkers_are_reset(name):
+    """Case 5: auto_reset = done | nonfinite.  Walkers that diverge (all-NaN: the kernels' stand-in path, partly NaN,
+    inf) after a finite snapshot was taken are reset at their first step, and the whole state is finite from then on."""
+    import torch
+    from oracle.oracle import Oracle
+    cfg = _config(name)
+    bad = _diverge(cfg["spec"], np.random.default_rng(5), n_dead=40, n_partial=20, n_inf=10, pin=False)
+    changed = ~np.isfinite(np.asarray(bad["pos"])).all(1) | ~np.isfinite(np.asarray(bad["vel"])).all(1)
+    mo = np.asarray(cfg["spec"]["mass_off"])
+    wbad = np.array([changed[a:b].any() for a, b in zip(mo[:-1], mo[1:])])
+    assert wbad.sum() >= 70
+    env, _ = _env(name, on=("done", "nonfinite"))           # the snapshot: the finite state
+    env.pos = bad["pos"]
+    env.vel = bad["vel"]
+    ref = _Composed(bad, cfg["params"], 3, cfg["pool"], snapshot=Oracle(cfg["spec"], cfg["params"]))
+    for t in range(4):
+        env.step(cfg["acts"][t])
+        out = ref.step(cfg["acts"][t])
+        torch.cuda.synchronize()
+        st = ref.state()
+        if t == 0:
+            assert out["reset"][wbad].all()
+        for k in ("pos", "vel", "acc"):
+            assert np.isfinite(st[k]).all()
+        _check_state(env, st)
+        _check_outputs(env, out, st)
+
+
+def test_disable_equals_never_enabled():
+    """Case 6: enable_auto_reset then disable_auto_reset: a short run equals an env that never had it."""
+    import torch
+    from walker_gym_amd.batched_env import BatchedPhysicsEnv
+    cfg = _config("canonical2051")
+    a, _ = _env("canonical2051")
+    a.disable_auto_reset()
+    b = BatchedPhysicsEnv(cfg["spec"], **cfg["params"])
+    acts = torch.from_numpy(cfg["acts"][:6]).to(a.device)
+    for e in (a, b):
+        e.run(acts, 6)
+        e.step(acts[0])
+    torch.cuda.synchronize()
+    assert "reset" not in a.info() and "episodes" not in a.info()
+    for k in ("pos", "vel", "acc", "muscle_x", "obs", "reward"):
+        _close(getattr(a, k).cpu().numpy(), getattr(b, k).cpu().numpy())
+    assert np.array_equal(a.steps.cpu().numpy(), b.steps.cpu().numpy())
+    assert int(a.steps.min()) >= 7                          # nobody was reset
+    assert np.array_equal(a.done.cpu().numpy(), b.done.cpu().numpy())
+
+
+def test_batches_without_a_lean_kernel_are_refused():
+    """Case 7: a ragged batch and an env with pair forces raise ValueError from enable_auto_reset (no launch)."""
+    from walker_gym_amd.batched_env import BatchedPhysicsEnv
+    from walker_gym_amd.synthetic import canonical_walkers, ragged_walkers
+    with pytest.raises(ValueError, match="lean"):
+        BatchedPhysicsEnv(ragged_walkers(64, seed=1), in3d=1).enable_auto_reset()
+    with pytest.raises(ValueError, match="lean"):
+        BatchedPhysicsEnv(canonical_walkers(64, seed=1), in3d=1, pair_mode=1).enable_auto_reset()
+    with pytest.raises(ValueError, match="nonfinite"):
+        BatchedPhysicsEnv(canonical_walkers(64, seed=1), in3d=1).enable_auto_reset(on=("fallen",))
+
+
+def test_episode_start_and_noise_pool_are_updated_in_place():
+    """set_episode_start() re-snapshots into the same tensors, refresh_reset_noise() redraws the pool in place (so
+    captured graphs keep their pointers); a prepared run from before enable_auto_reset refuses to run."""
+    import torch
+    from walker_gym_amd.batched_env import BatchedPhysicsEnv
+    cfg = _config("canonical37")
+    env = BatchedPhysicsEnv(cfg["spec"], rand_sigma=0.25, seed=3, **cfg["params"])
+    acts = torch.from_numpy(cfg["acts"]).to(env.device)
+    stale = env.prepare_run(acts, T)
+    env.enable_auto_reset(noise_rows=3)
+    with pytest.raises(RuntimeError, match="stale"):
+        stale()
+    pool = env.batch.reset_noise
+    assert tuple(pool.shape) == (3, env.batch.P, 3) and float(pool.abs().max()) > 0
+    before, ptr = pool.clone(), pool.data_ptr()
+    env.refresh_reset_noise()
+    assert pool.data_ptr() == ptr and not torch.equal(before, pool)
+    env.step(acts[0])
+    ip = env.batch.init_pos.data_ptr()
+    env.set_episode_start()
+    torch.cuda.synchronize()
+    assert env.batch.init_pos.data_ptr() == ip
+    assert torch.equal(env.batch.init_pos, env.batch.pos) and torch.equal(env.batch.init_muscle_x, env.batch.muscle_x)
+    assert not np.array_equal(env.batch.init_pos.cpu().numpy().reshape(-1, 3), cfg["spec"]["pos"])

@@ -13,7 +13,7 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libwalker_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 WG_EINVAL, WG_ERANGE, WG_EHIP = -1, -2, -3
 
@@ -28,7 +28,8 @@ class WgParams(C.Structure):
                [(n, C.c_double) for n in ("pair_g", "pair_k", "pair_e", "bounce_k")] + \
                [("g3_gravity", C.c_double * 3)] + \
                [(n, C.c_double) for n in ("g3_damping", "g3_air", "g3_ground_level", "g3_restitution",
-                                          "g3_friction")] + [("g3_ground", C.c_int32), ("friction_mode", C.c_int32)]
+                                          "g3_friction")] + [("g3_ground", C.c_int32), ("friction_mode", C.c_int32),
+                                                             ("auto_reset", C.c_int32)]   # ABI 16: 1 done, 2 non-finite
 
 
 class WgBatch(C.Structure):
@@ -41,13 +42,18 @@ class WgBatch(C.Structure):
                 ("muscle_x", _vp), ("muscle_bounds", _vp), ("muscle_stride", _vp),
                 ("steps", _vp), ("contact", _vp), ("pinned", _vp),
                 ("charge", _vp), ("radius", _vp), ("row", _vp), ("bounce_set", _vp),
-                ("edges8", _vp), ("kc", C.c_float * 4)]   # ABI 15: the compact spring records and their (k, c) classes
+                ("edges8", _vp), ("kc", C.c_float * 4),   # ABI 15: the compact spring records and their (k, c) classes
+                # ABI 16, auto-reset: the episode-start snapshot, the reset-noise pool and the episode counters
+                ("init_pos", _vp), ("init_vel", _vp), ("init_acc", _vp), ("init_muscle_x", _vp),
+                ("reset_noise", _vp), ("reset_noise_rows", C.c_int32), ("reset_noise_stride", C.c_int64),
+                ("episodes", _vp)]
 
 
 class WgOutputs(C.Structure):
     _fields_ = [("obs", _vp), ("obs_stride", C.c_int32), ("reward", _vp), ("done", _vp),
                 ("centroid", _vp), ("energy", _vp), ("obs_step", C.c_int64), ("out_step", C.c_int64),
-                ("obs_pad_clean", C.c_int32), ("steps", _vp), ("nonfinite", _vp), ("momentum", _vp)]
+                ("obs_pad_clean", C.c_int32), ("steps", _vp), ("nonfinite", _vp), ("momentum", _vp),
+                ("reset", _vp), ("final_obs", _vp)]   # ABI 16, auto-reset
 
 
 class WgRange(C.Structure):

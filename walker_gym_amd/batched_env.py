@@ -185,7 +185,9 @@ class BatchedPhysicsEnv:
         self.N = host.N
         self.obs_len = host.obs_len(self.params.in3d, self.params.conmid)
         self.obs_dim = int(self.obs_len.max())
-        self._pstruct = self.params.to_struct()
+        # auto-reset (enable_auto_reset): wg_params.auto_reset, info['reset'] and the optional terminal rows
+        self._ar_mode, self.reset_out, self.final_obs = 0, None, None
+        self._pstruct = self._make_pstruct()
         self._gen = torch.Generator(device=device)
         if seed is not None:
             self._gen.manual_seed(int(seed))
@@ -245,6 +247,83 @@ class BatchedPhysicsEnv:
         self._steps_at = -1
         self.momentum = torch.zeros((N, 3), dtype=torch.float32, device=dv) if self._extras else None
         self.nonfinite = torch.zeros(N, dtype=torch.bool, device=dv) if self._extras else None
+        if getattr(self, "final_obs", None) is not None:   # (auto-reset's terminal rows follow the row length)
+            self.final_obs = torch.zeros((N, D), dtype=torch.float32, device=dv)
+
+    def _make_pstruct(self) -> _lib.WgParams:
+        ps = self.params.to_struct()
+        ps.auto_reset = self._ar_mode
+        return ps
+
+    # ------------------------------------------------------------------ auto-reset (ABI 16)
+    _AR_BITS = {"done": 1, "nonfinite": 2}
+
+    def enable_auto_reset(self, on=("done",), noise_rows: int = 1, final_obs: bool = False, noise=None) -> None:
+        """Episodes roll over on the device: from now on a walker whose step ends its episode — its `done` is set
+        ('done'), or its state after the step holds an inf / NaN ('nonfinite') — is put back to the episode start inside
+        the launch that stepped it: pos / vel / acc / muscle_x from a snapshot of the CURRENT state, then reset()'s
+        velocity noise and steps = 0, and its obs row is the fresh state's (what reset() returns), while reward, done
+        and info keep the terminal step's values.  info() gains 'reset' (the walkers reset by the last step),
+        'episodes' (resets taken so far) and, with final_obs, 'final_obs' (the terminal rows of the walkers just reset;
+        other rows are left as they were).
+
+        The noise comes from a pool of `noise_rows` draws of randn * sigma over [P, 3] from the env's generator (none
+        when sigma == 0); a walker's episode e uses row e % noise_rows, and refresh_reset_noise() redraws the pool.
+        noise [rows, P, 3]: a pool of the caller's instead.  Works with step, run, rollout (per-step launches),
+        policy_loop and graph; prepared runs and graphs made before the call refuse to run.  Only batches the
+        barrier-free lean kernel takes (uniform, M dividing 64, spring_mode 0, pair_mode 0): ValueError otherwise."""
+        names = (on,) if isinstance(on, str) else tuple(on)
+        if not names or any(n not in self._AR_BITS for n in names):
+            raise ValueError(f"enable_auto_reset: on must name 'done' and / or 'nonfinite', got {on!r}")
+        if not self.resident_ok():
+            raise ValueError("enable_auto_reset: only batches of the lean step kernel (uniform, M dividing 64 with "
+                             "M >= 4, spring_mode 0, pair_mode 0, WG_LEAN not 0); ragged batches and the workgroup "
+                             "kernel have no auto-reset")
+        if noise is not None:
+            pool = torch.as_tensor(noise, dtype=torch.float32).to(self.device).reshape(-1, self.batch.P, 3).contiguous()
+        elif self.sigma > 0:
+            if int(noise_rows) < 1:
+                raise ValueError("enable_auto_reset: noise_rows must be >= 1")
+            pool = torch.randn((int(noise_rows), self.batch.P, 3), generator=self._gen, device=self.device) * self.sigma
+        else:
+            pool = None
+        self.batch.set_auto_reset(pool)
+        self._ar_mode = sum(self._AR_BITS[n] for n in set(names))
+        self.reset_out = torch.zeros(self.N, dtype=torch.bool, device=self.device)
+        self.final_obs = torch.zeros((self.N, self.obs_dim), dtype=torch.float32, device=self.device) if final_obs \
+            else None
+        self._pstruct = self._make_pstruct()
+        self._generation += 1   # prepared runs and graphs rebuild
+
+    def disable_auto_reset(self) -> None:
+        """Turn auto-reset off: the step is the plain step again (the snapshot and the noise pool are dropped)."""
+        if self._ar_mode:
+            self._ar_mode, self.reset_out, self.final_obs = 0, None, None
+            self.batch.clear_auto_reset()
+            self._pstruct = self._make_pstruct()
+            self._generation += 1
+
+    def set_episode_start(self) -> None:
+        """Take the current state as the episode start of the walkers reset from now on (stream-ordered copies into
+        the existing snapshot: graphs and prepared runs stay valid)."""
+        if not self._ar_mode:
+            raise RuntimeError("set_episode_start: auto-reset is off (enable_auto_reset first)")
+        self.batch.snapshot_episode_start()
+
+    def refresh_reset_noise(self) -> None:
+        """Redraw the reset-noise pool in place (randn * sigma from the env's generator); nothing to do without one."""
+        if not self._ar_mode:
+            raise RuntimeError("refresh_reset_noise: auto-reset is off (enable_auto_reset first)")
+        pool = self.batch.reset_noise
+        if pool is not None:
+            pool.copy_(torch.randn(pool.shape, generator=self._gen, device=self.device) * self.sigma)
+
+    def _ar_out(self, w0: int = 0, w1: Optional[int] = None) -> dict:
+        """Auto-reset's outputs of walkers [w0, w1) (or none)."""
+        if not self._ar_mode:
+            return {}
+        w1 = self.N if w1 is None else w1
+        return {"reset": self.reset_out[w0:w1], "final_obs": None if self.final_obs is None else self.final_obs[w0:w1]}
 
     def enable_info_extras(self) -> None:
         """Start producing info['momentum'] and info['nonfinite'] every step (one small per-walker pass after the
@@ -258,12 +337,12 @@ class BatchedPhysicsEnv:
             self._generation += 1
 
     def _outputs(self, obs=None, reward=None, done=None, centroid=None, energy=None, obs_step=0, out_step=0,
-                 pad_clean=False, steps=None, nonfinite=None, momentum=None):
+                 pad_clean=False, steps=None, nonfinite=None, momentum=None, reset=None, final_obs=None):
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         return _lib.WgOutputs(obs=p(obs), obs_stride=self.obs_dim, reward=p(reward), done=p(done),
                               centroid=p(centroid), energy=p(energy), obs_step=obs_step, out_step=out_step,
                               obs_pad_clean=int(pad_clean), steps=p(steps), nonfinite=p(nonfinite),
-                              momentum=p(momentum))
+                              momentum=p(momentum), reset=p(reset), final_obs=p(final_obs))
 
     @staticmethod
     def _range_outputs(o, w0: int):
@@ -276,7 +355,8 @@ class BatchedPhysicsEnv:
                               reward=adv(o.reward, 4 * w0), done=adv(o.done, w0), centroid=adv(o.centroid, 12 * w0),
                               energy=adv(o.energy, 4 * w0), obs_step=o.obs_step, out_step=o.out_step,
                               obs_pad_clean=o.obs_pad_clean, steps=adv(o.steps, 4 * w0),
-                              nonfinite=adv(o.nonfinite, w0), momentum=adv(o.momentum, 12 * w0))
+                              nonfinite=adv(o.nonfinite, w0), momentum=adv(o.momentum, 12 * w0),
+                              reset=adv(o.reset, w0), final_obs=adv(o.final_obs, 4 * w0 * o.obs_stride))
 
     def _extra_out(self, w0: int = 0, w1: Optional[int] = None) -> dict:
         """The opt-in info outputs of walkers [w0, w1) (or none)."""
@@ -302,7 +382,7 @@ class BatchedPhysicsEnv:
             self.batch.enable_radius()
         if self._needs_plan() and self.batch.wave_ok != self._wave_ok():
             self.batch.replan(self._wave_ok())   # the plan kind follows the parameters (DeviceBatch.replan)
-        self._pstruct = self.params.to_struct()
+        self._pstruct = self._make_pstruct()
         self._generation += 1   # graphs captured before this replay stale parameters: WalkerGraph refuses them
 
     def _wave_ok(self) -> bool:
@@ -376,7 +456,7 @@ class BatchedPhysicsEnv:
             o = self._outputs(self.obs[w0:w1], self.reward[w0:w1], self.done[w0:w1], self.centroid[w0:w1],
                               self.energy[w0:w1], pad_clean=True,
                               steps=None if self.steps_out is None else self.steps_out[w0:w1],
-                              **self._extra_out(w0, w1))
+                              **self._extra_out(w0, w1), **self._ar_out(w0, w1))
             keep.append(o)
             return C.pointer(o)
         if lanes == 1 or b.ragged:
@@ -408,10 +488,11 @@ class BatchedPhysicsEnv:
         return self._plan_cache
 
     def rollout(self, actions, obs_out=None, reward_out=None, done_out=None, lanes: Optional[int] = None,
-                resident: bool = True):
+                resident: bool = True, reset_out=None):
         """T steps in one C call, no host sync; outputs for every step.  resident (default): wg_rollout, one launch
         for all T steps where the batch allows it (uniform M | 64, no pair forces), each walker's state kept in
-        registers between steps; False: wg_step, one launch per step.  Bit-identical either way."""
+        registers between steps; False: wg_step, one launch per step.  Bit-identical either way.  With auto-reset the
+        steps run as per-step launches either way; reset_out [T, N] uint8 (optional) receives every step's resets."""
         if not isinstance(actions, torch.Tensor):
             actions = torch.as_tensor(np.asarray(actions, dtype=np.float32))
         actions = actions.to(self.device, torch.float32).contiguous()
@@ -421,7 +502,7 @@ class BatchedPhysicsEnv:
         dv = self.device
         self._steps_at = -1   # the step counters move without the steps output: info() gathers them afterwards
         # (the per-step outputs went to the rollout's buffers: the env's own centroid / energy / extras are not current)
-        self._stale = frozenset({"centroid_position", "total_energy", "momentum", "nonfinite"})
+        self._stale = frozenset({"centroid_position", "total_energy", "momentum", "nonfinite", "reset", "final_obs"})
         # zero-filled: a ragged batch's short rows then need only their own values written each step
         clean = obs_out is None
         obs_out = torch.zeros((T, self.N, self.obs_dim), dtype=torch.float32, device=dv) if obs_out is None else obs_out
@@ -430,13 +511,17 @@ class BatchedPhysicsEnv:
         require_tensor(obs_out, "obs_out", dv, torch.float32, (T, self.N, self.obs_dim))
         require_tensor(reward_out, "reward_out", dv, torch.float32, (T, self.N))
         require_tensor(done_out, "done_out", dv, torch.uint8, (T, self.N))
+        if reset_out is not None:
+            if not self._ar_mode:
+                raise ValueError("rollout(reset_out=...) needs auto-reset (enable_auto_reset)")
+            require_tensor(reset_out, "reset_out", dv, torch.uint8, (T, self.N))
         # one resident launch holds its walkers for all T steps: no per-step launch tail for a second range to fill
         # (profiles/r02_ab_resident_occupancy.json: 38.2 us/step with one range, 39.6 with two)
         # (only where the resident kernel actually runs: otherwise the default walker ranges keep their overlap)
         lanes = self._lanes(1 if (resident and lanes is None and self.resident_ok()) else lanes) if T > 0 else 1
         entry = "wg_rollout" if resident else "wg_step"
         o = self._outputs(obs_out, reward_out, done_out, None, None, obs_step=self.N * self.obs_dim,
-                          out_step=self.N, pad_clean=clean)
+                          out_step=self.N, pad_clean=clean, reset=reset_out)
         if lanes > 1:
             self._run_lanes(actions, T, o, lanes, entry=entry)
             return obs_out, reward_out, done_out
@@ -504,11 +589,23 @@ class BatchedPhysicsEnv:
             cen = en = None
             stale |= {"centroid_position", "total_energy", "momentum", "nonfinite"}
         # the opt-in info extras follow the last step only when the outputs are overwritten each step (no record)
+        # (auto-reset's outputs likewise: a record run strides its outputs per step, so it takes record['reset'] [n_steps,
+        # N] uint8 / bool, if given, and no final_obs)
+        ar_out = self._ar_out()
+        if record is not None and self._ar_mode:
+            rs = record.get("reset")
+            if rs is not None:
+                if not isinstance(rs, torch.Tensor) or rs.dtype not in (torch.bool, torch.uint8):
+                    raise ValueError("record['reset'] must be a bool or uint8 tensor")
+                require_tensor(rs, "record['reset']", self.device, rs.dtype, (int(n_steps), self.N))
+            ar_out = {"reset": None if rs is None else rs[0]}
+            stale |= {"reset", "final_obs"}
         o = self._outputs(self.obs, rew, done, cen, en, pad_clean=True, steps=so, out_step=out_step,
-                          **(self._extra_out() if (info and record is None) else {}))
+                          **(self._extra_out() if (info and record is None) else {}), **ar_out)
         # every tensor whose raw pointer sits in `o`, held by the PreparedRun (a caller that drops its record
         # buffers and calls the PreparedRun again must not have the kernel write into freed memory)
-        pins = [self.obs, so, actions, *(() if record is None else record.values()), *self._extra_out().values()]
+        pins = [self.obs, so, actions, *(() if record is None else record.values()), *self._extra_out().values(),
+                *self._ar_out().values()]
         steps_valid = so is not None
         n_steps = int(n_steps)
         if lanes > 1:
@@ -731,7 +828,8 @@ class BatchedPhysicsEnv:
                 w0, w1 = bounds[i], bounds[i + 1]
                 sub = b.sub_struct(w0, w1)
                 o = self._outputs(self.obs[w0:w1], self.reward[w0:w1], self.done[w0:w1], self.centroid[w0:w1],
-                                  self.energy[w0:w1], pad_clean=True, **self._extra_out(w0, w1))
+                                  self.energy[w0:w1], pad_clean=True, **self._extra_out(w0, w1),
+                                  **self._ar_out(w0, w1))
                 keep += [sub, o]
                 args.append((self.obs[w0:w1], None, w1 - w0, C.byref(sub), C.byref(o), None, 0))
                 aoff.append(0)   # (a sub-batch indexes its actions from its own first walker)
@@ -915,6 +1013,11 @@ class BatchedPhysicsEnv:
         if self._extras:
             info["momentum"] = self.momentum      # Point.momentum (gym/engine.py:160-166) of each walker
             info["nonfinite"] = self.nonfinite    # True: the walker's pos / vel / acc hold an inf or NaN
+        if self._ar_mode:                         # auto-reset: the last step's resets, the resets taken so far
+            info["reset"] = self.reset_out
+            info["episodes"] = self.batch.episodes
+            if self.final_obs is not None:
+                info["final_obs"] = self.final_obs
         for k in self._stale:                     # not written by the last run() (record buffers, info=False)
             info.pop(k, None)
         return info

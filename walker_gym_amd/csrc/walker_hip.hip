@@ -97,6 +97,59 @@ inline KOut kout(const wg_outputs &o) {
     return KOut{o.obs, o.reward, o.done, o.centroid, o.energy, o.steps, o.obs_step, o.out_step, o.obs_stride,
                 o.obs_pad_clean};
 }
+// Auto-reset (ABI 16): what the AR instances of the lean step kernels take beside wg_batch's snapshot pointers, as a
+// trailing kernel argument of their own (the other instances take the empty KNoReset, so their arguments, and the
+// registers that hold them, are what they were).
+struct KReset {
+    uint8_t *reset;     // wg_outputs.reset of this step, or NULL
+    float *final_obs;   // wg_outputs.final_obs of this step, or NULL
+    int mode;           // wg_params.auto_reset: 1 done, 2 non-finite
+};
+struct KNoReset {};
+// wg_batch as it was before ABI 16 (its leading 208 bytes, field for field): what the lean step kernel's instances
+// without auto-reset take as their first argument, so that their argument layout, and with it their register
+// allocation (73 VGPRs at NE 2-4; 78 with the longer struct in front of the other arguments), stays what it was.
+struct KBatch15 {
+    int32_t N, M, K, A;
+    int32_t ragged;
+    const int32_t *mass_off, *edge_off, *muscle_off;
+    float *pos, *vel, *acc;
+    const float *mass;
+    const wg_edge *edges;
+    const uint16_t *inc;
+    const uint16_t *inc_off;
+    float *muscle_x;
+    const float *muscle_bounds;
+    const float *muscle_stride;
+    int32_t *steps;
+    uint8_t *contact;
+    const uint8_t *pinned;
+    const double *charge;
+    double *radius;
+    const int32_t *row;
+    const uint8_t *bounce_set;
+    const wg_edge8 *edges8;
+    float kc[4];
+};
+static_assert(sizeof(KBatch15) == offsetof(wg_batch, init_pos) && offsetof(KBatch15, pos) == offsetof(wg_batch, pos) &&
+                  offsetof(KBatch15, steps) == offsetof(wg_batch, steps) &&
+                  offsetof(KBatch15, edges8) == offsetof(wg_batch, edges8) && offsetof(KBatch15, kc) == offsetof(wg_batch, kc),
+              "KBatch15 is wg_batch's ABI-15 prefix");
+inline const KBatch15 &kbatch15(const wg_batch *b) { return *reinterpret_cast<const KBatch15 *>(b); }
+// (in a kernel) the wg_batch of that prefix, the ABI-16 fields zero
+__device__ __forceinline__ wg_batch batch_of(const KBatch15 &k) {
+    wg_batch b{};
+    b.N = k.N; b.M = k.M; b.K = k.K; b.A = k.A; b.ragged = k.ragged;
+    b.mass_off = k.mass_off; b.edge_off = k.edge_off; b.muscle_off = k.muscle_off;
+    b.pos = k.pos; b.vel = k.vel; b.acc = k.acc; b.mass = k.mass; b.edges = k.edges; b.inc = k.inc; b.inc_off = k.inc_off;
+    b.muscle_x = k.muscle_x; b.muscle_bounds = k.muscle_bounds; b.muscle_stride = k.muscle_stride; b.steps = k.steps;
+    b.contact = k.contact; b.pinned = k.pinned; b.charge = k.charge; b.radius = k.radius; b.row = k.row;
+    b.bounce_set = k.bounce_set; b.edges8 = k.edges8;
+    for (int i = 0; i < 4; i++) b.kc[i] = k.kc[i];
+    return b;
+}
+__device__ __forceinline__ const wg_batch &batch_of(const wg_batch &b) { return b; }
+inline KReset kreset(const wg_outputs &o, int mode) { return KReset{o.reset, o.final_obs, mode}; }
 
 // Step-kernel launches.  wg_time_step (ABI 14, a measurement aid) sets the two events on this thread around each step it
 // issues: the launch then goes through hipExtLaunchKernel, which stamps the kernel's own start and end on them (the
@@ -2207,13 +2260,57 @@ __device__ __forceinline__ LeanTerms lean_terms(char *sl, const LeanGeo &lg) {
     return TermsAoS{reinterpret_cast<double *>(sl), reinterpret_cast<float *>(sl + lg.off_df)};
 }
 
+// The observation rows of one wave's walkers, Creature.getstat (gym/optimized_walker.py:129-162), straight from
+// registers: lane q's 3d values are one contiguous piece of its walker's row, stored as d-float vectors; the wave's
+// pieces tile the rows, and the L2 merges them into whole lines.  One function for the step's rows and, with auto-reset,
+// the terminal rows' copy (wg_outputs.final_obs) and the fresh rows of the walkers just reset: mass_on / mus_on select
+// the lanes that store (the mass lanes / muscle lanes of the tile, or of the reset walkers only); s = the walker's
+// position sums, mid = s / M.
+template <bool IN3D>
+__device__ __forceinline__ void lean_obs_rows(float *obs, int stride, const KParams &kp, int M, int A, int w0, int wl,
+                                              int q, int mu_wl, int mu_ua, bool mass_on, bool mus_on, float px, float py,
+                                              float pz, float vx, float vy, float vz, float ax, float ay, float az,
+                                              float sx, float sy, float sz, float midx, float midy, float midz, float x) {
+    constexpr int d = IN3D ? 3 : 2, per = 3 * d;
+    const int nmid = kp.conmid ? 3 : 0;
+    typedef float fvd __attribute__((ext_vector_type(d), aligned(4)));
+    if (mass_on) {
+        const uint32_t row0 = (uint32_t)(w0 + wl) * (uint32_t)stride;   // the row's first element
+        // G1 getstat (midform 2, gym/walker.py:88-96) subtracts the SUM of positions
+        const float mm[3] = {kp.midform == 2 ? sx : midx, kp.midform == 2 ? sy : midy, kp.midform == 2 ? sz : midz};
+        const float pm[3] = {px, py, pz}, vm[3] = {vx, vy, vz}, am[3] = {ax, ay, az};
+        fvd vp, vv, va;
+#pragma unroll
+        for (int c = 0; c < d; c++) {
+            vp[c] = kp.midform ? (pm[c] - mm[c]) * kp.pk : pm[c] * kp.pk;
+            vv[c] = vm[c] * kp.vk;
+            va[c] = am[c] * kp.ak;
+        }
+        float *dst = WG_ST(obs, row0 + per * q, 1);   // (a 3-vector's type is 16 B: no array indexing over fvd)
+        *reinterpret_cast<fvd *>(dst) = vp;
+        *reinterpret_cast<fvd *>(dst + d) = vv;
+        *reinterpret_cast<fvd *>(dst + 2 * d) = va;
+        if (q == 0) {
+            if (nmid) {
+                float *mrow = WG_ST(obs, row0 + per * M, 1);
+                mrow[0] = kp.midform ? mm[0] : 0.f; mrow[1] = kp.midform ? mm[1] : 0.f;
+                mrow[2] = kp.midform ? mm[2] : 0.f;
+            }
+            for (int r = per * M + nmid + A; r < stride; r++) *WG_ST(obs, row0 + r, 1) = 0.f;
+        }
+    }
+    if (mus_on) *WG_ST(obs, (uint32_t)(w0 + mu_wl) * (uint32_t)stride + per * M + nmid + mu_ua, 1) = x * kp.mk;
+}
+
 // One wave's tile after its loads: the edge lanes leave the spring term t and the damping force df of every
 // edge in LDS, then each mass lane walks its incidence list, dividing by m as the reference does (mass_step).
 // RES (walker_rollout_lean): the tile's state stays in L across steps; it is written to HBM only when `last`.
-template <bool IN3D, int NE, bool RES = false, bool E8 = false>
+// AR (auto-reset, ABI 16; never with RES): after the outputs, the walkers whose episode this step ended are put back to
+// the snapshot (b.init_*) with their reset noise and their fresh observation rows, in a rare wave-uniform branch.
+template <bool IN3D, int NE, bool RES = false, bool E8 = false, bool AR = false>
 __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &kp, const KOut &o,
                                              const LeanGeo &lg, char *sl, const LeanTile &t, int lane,
-                                             LeanIn<NE, E8> &L, bool last = true) {
+                                             LeanIn<NE, E8> &L, bool last = true, const KReset &ar = KReset{}) {
     const bool store = !RES || last;
     const int M = b.M, K = b.K, A = b.A;
     const int w0 = t.w0, nE = t.nE;
@@ -2410,6 +2507,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     const unsigned long long sb = __ballot(is_mass && nv < 0.1f);
     // M | 64 is a power of two: x / M == x * (1/M) exactly (the same real number, rounded once)
     const float midx = sx * lg.invM, midy = sy * lg.invM, midz = sz * lg.invM;
+    int ep_done = 0;   // (AR) the step's done, in lane q == 0 of each walker
     if (is_mass) {
         if (store) {
             float *gpo = WG_ST(b.pos, pl, 3), *gvo = WG_ST(b.vel, pl, 3), *gao = WG_ST(b.acc, pl, 3);
@@ -2433,11 +2531,12 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
                 const float vpen = (-(vsum * lg.invM)) * 0.1f;
                 *WG_ST(o.reward, wg, 1) = (cy + vpen) + neg_half_count((int)__popcll(hb & gmask));
             }
-            if (o.done) {
+            if (o.done || (AR && (ar.mode & 1))) {
                 int done = steps >= kp.max_steps;
                 if (!done && cy < kp.done_y) done = 1;
                 if (!done && steps > 100) done = (sb & gmask) == gmask;
-                at_u32w(o.done, wg) = (uint8_t)done;
+                if (o.done) at_u32w(o.done, wg) = (uint8_t)done;
+                ep_done = done;
             }
             if (o.centroid) {
                 float *c = WG_ST(o.centroid, wg, 3);
@@ -2449,38 +2548,67 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
 
     STAMP(5);
     // ================= observation rows: Creature.getstat (gym/optimized_walker.py:129-162) =========
-    if (o.obs && !(WG_ABLATE & 16)) {
-        // straight from registers: lane q's 3d values are one contiguous piece of its walker's row, stored as d-float
-        // vectors; the wave's pieces tile the rows, and the L2 merges them into whole lines
-        constexpr int d = IN3D ? 3 : 2, per = 3 * d;
-        const int stride = o.obs_stride, nmid = kp.conmid ? 3 : 0;
-        typedef float fvd __attribute__((ext_vector_type(d), aligned(4)));
-        if (is_mass) {
-            const uint32_t row0 = (uint32_t)(w0 + wl) * (uint32_t)stride;   // the row's first element
-            // G1 getstat (midform 2, gym/walker.py:88-96) subtracts the SUM of positions
-            const float mm[3] = {kp.midform == 2 ? sx : midx, kp.midform == 2 ? sy : midy, kp.midform == 2 ? sz : midz};
-            const float pm[3] = {px, py, pz}, vm[3] = {vx, vy, vz}, am[3] = {ax, ay, az};
-            fvd vp, vv, va;
-#pragma unroll
-            for (int c = 0; c < d; c++) {
-                vp[c] = kp.midform ? (pm[c] - mm[c]) * kp.pk : pm[c] * kp.pk;
-                vv[c] = vm[c] * kp.vk;
-                va[c] = am[c] * kp.ak;
-            }
-            float *dst = WG_ST(o.obs, row0 + per * q, 1);   // (a 3-vector's type is 16 B: no array indexing over fvd)
-            *reinterpret_cast<fvd *>(dst) = vp;
-            *reinterpret_cast<fvd *>(dst + d) = vv;
-            *reinterpret_cast<fvd *>(dst + 2 * d) = va;
-            if (q == 0) {
-                if (nmid) {
-                    float *mrow = WG_ST(o.obs, row0 + per * M, 1);
-                    mrow[0] = kp.midform ? mm[0] : 0.f; mrow[1] = kp.midform ? mm[1] : 0.f;
-                    mrow[2] = kp.midform ? mm[2] : 0.f;
+    if (o.obs && !(WG_ABLATE & 16))
+        lean_obs_rows<IN3D>(o.obs, o.obs_stride, kp, M, A, w0, wl, q, mu_wl, mu_ua, is_mass, is_mus, px, py, pz, vx, vy,
+                            vz, ax, ay, az, sx, sy, sz, midx, midy, midz, x);
+    // ================= auto-reset (ABI 16): the walkers whose episode this step ended start their next one here
+    if constexpr (AR && !RES) {
+        // walker-level events as lane bits: the step's done (lane q == 0 holds it), a non-finite component of the state
+        // the step leaves (wg_outputs.nonfinite's test, on the registers; the diverged walkers' NaN included)
+        const bool nonf = is_mass && !(__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz) &&
+                                       __builtin_isfinite(vx) && __builtin_isfinite(vy) && __builtin_isfinite(vz) &&
+                                       __builtin_isfinite(ax) && __builtin_isfinite(ay) && __builtin_isfinite(az));
+        const unsigned long long eb = __ballot(is_mass && q == 0 && ep_done != 0), nb = __ballot(nonf);
+        const unsigned long long hot = ((ar.mode & 1) ? eb : 0ull) | ((ar.mode & 2) ? nb : 0ull);
+        const bool selw = is_mass && (hot & gmask) != 0ull;             // this mass lane's walker is reset
+        if (ar.reset && is_mass && q == 0) at_u32w(ar.reset, (uint32_t)(w0 + wl)) = (uint8_t)selw;
+        if (__builtin_expect(hot != 0ull, 0)) {   // wave-uniform, rare: every lane enters (walker_sums, the gathers)
+            const unsigned long long mmask = (M == 64) ? ~0ull : (((1ull << M) - 1ull) << ((mu_wl << lg.lgM) & 63));
+            const bool selm = is_mus && (hot & mmask) != 0ull;          // this muscle lane's walker is reset
+            if (ar.final_obs)   // the terminal rows of the reset walkers
+                lean_obs_rows<IN3D>(ar.final_obs, o.obs_stride, kp, M, A, w0, wl, q, mu_wl, mu_ua, selw, selm, px, py, pz,
+                                    vx, vy, vz, ax, ay, az, sx, sy, sz, midx, midy, midz, x);
+            // the walker's episode count from its lane q == 0, which also writes it back (no lane reads what another
+            // lane of the wave stores)
+            int ep = 0;
+            if (selw && q == 0) ep = at_u32(b.episodes, 4u * (uint32_t)(w0 + wl));
+            ep = __builtin_amdgcn_ds_bpermute(gbase << 2, ep);
+            float fx = px, fy = py, fz = pz, fvx = vx, fvy = vy, fvz = vz, fax = ax, fay = ay, faz = az, fxm = x;
+            if (selw) {
+                const float *ip = &at_u32(b.init_pos, 12u * pl), *iv = &at_u32(b.init_vel, 12u * pl),
+                            *ia = &at_u32(b.init_acc, 12u * pl);
+                fx = ip[0]; fy = ip[1]; fz = ip[2];
+                fvx = iv[0]; fvy = iv[1]; fvz = iv[2];
+                fax = ia[0]; fay = ia[1]; faz = ia[2];
+                if (b.reset_noise) {   // wg_reset: v += noise, one float32 add per component (z if in3d)
+                    // (64-bit addressing: rows x stride of the pool may pass 4 GiB, and the branch is rare)
+                    const float *nz = b.reset_noise +
+                                      (size_t)((uint32_t)ep % (uint32_t)b.reset_noise_rows) * (size_t)b.reset_noise_stride +
+                                      3 * (size_t)pl;
+                    fvx = fvx + nz[0]; fvy = fvy + nz[1];
+                    if (IN3D) fvz = fvz + nz[2];
                 }
-                for (int r = per * M + nmid + A; r < stride; r++) *WG_ST(o.obs, row0 + r, 1) = 0.f;
+                float *gpo = WG_ST(b.pos, pl, 3), *gvo = WG_ST(b.vel, pl, 3), *gao = WG_ST(b.acc, pl, 3);
+                gpo[0] = fx; gpo[1] = fy; gpo[2] = fz;
+                gvo[0] = fvx; gvo[1] = fvy; gvo[2] = fvz;
+                gao[0] = fax; gao[1] = fay; gao[2] = faz;
+                if (q == 0) {
+                    const uint32_t wg = (uint32_t)(w0 + wl);
+                    *WG_ST(b.steps, wg, 1) = 0;
+                    *WG_ST(b.episodes, wg, 1) = ep + 1;
+                }
+            }
+            if (selm) {
+                fxm = at_u32(b.init_muscle_x, 4u * ul);
+                *WG_ST(b.muscle_x, ul, 1) = fxm;
+            }
+            if (o.obs && !(WG_ABLATE & 16)) {   // wg_observe's rows of the fresh state
+                const WalkerSums fs = walker_sums(fx, fy, fz, 0.f, 0.f, 0.f, gbase, M, lane);
+                lean_obs_rows<IN3D>(o.obs, o.obs_stride, kp, M, A, w0, wl, q, mu_wl, mu_ua, selw, selm, fx, fy, fz, fvx,
+                                    fvy, fvz, fax, fay, faz, fs.sx, fs.sy, fs.sz, fs.sx * lg.invM, fs.sy * lg.invM,
+                                    fs.sz * lg.invM, fxm);
             }
         }
-        if (is_mus) *WG_ST(o.obs, (uint32_t)(w0 + mu_wl) * (uint32_t)stride + per * M + nmid + mu_ua, 1) = x * kp.mk;
     }
     if (RES) {   // the next step starts from this one's state (Point.pos/v, Muscle.x), in registers
         L.p3[0] = px; L.p3[1] = py; L.p3[2] = pz;
@@ -2502,11 +2630,13 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
 constexpr int lean_waves(int NE) { return NE >= 8 ? 4 : 6; }
 
 // One tile (64 / M walkers) per wave; waves never wait for one another.  E8: the compact spring records (b.edges8).
-template <bool IN3D, int NE, bool E8>
+// AR: the auto-reset tail (ABI 16), its arguments in the trailing `ar` (empty otherwise).
+template <bool IN3D, int NE, bool E8, bool AR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(NE)))) void walker_step_lean(
-    wg_batch b, KParams kp, const float *__restrict__ action, int action_cols, int action_stride, KOut o,
-    LeanGeo lg) {
+    typename std::conditional<AR, wg_batch, KBatch15>::type bk, KParams kp, const float *__restrict__ action,
+    int action_cols, int action_stride, KOut o, LeanGeo lg, typename std::conditional<AR, KReset, KNoReset>::type ar) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const wg_batch b = batch_of(bk);
     // the wave index as a wave-uniform (scalar) value: the tile's walker range and element bases are then SALU
     // products, not per-lane v_mul_lo_u32
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2524,7 +2654,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
     lean_load<NE, E8>(b, kp, action, action_stride, t, lane, L);
     if (kp.prio) __builtin_amdgcn_s_setprio(0);
     STAMP(1);
-    lean_compute<IN3D, NE, false, E8>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
+    if constexpr (AR) lean_compute<IN3D, NE, false, E8, true>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L, true, ar);
+    else lean_compute<IN3D, NE, false, E8>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
 }
 
 // NE = 1, the latency-bound small batches (Balance-4096: 512 waves, one per SIMD, the launch as long as its slowest
@@ -2537,10 +2668,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
 // step, same box, interleaved: round 5's prologue 5.33 us, the same arguments in one scalar round 5.01
 // (profiles/r06b_ab_balance4096_prologue.json), preloaded 2.5 % below that (profiles/r06e_ab_*).
 // E8: `edges` is the batch's compact records (b.edges8) in the same preloaded slot.
-template <bool IN3D, bool E8>
+template <bool IN3D, bool E8, bool AR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(1)))) void walker_step_lean1(
     float *pos, float *vel, const void *edges, const uint16_t *inc, int N, int M, int K, int wpw, int wpb, int nblkx,
-    wg_batch b, KParams kp, const float *__restrict__ action, int action_cols, int action_stride, KOut o, LeanGeo lg) {
+    wg_batch b, KParams kp, const float *__restrict__ action, int action_cols, int action_stride, KOut o, LeanGeo lg,
+    typename std::conditional<AR, KReset, KNoReset>::type ar) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     b.pos = pos; b.vel = vel; b.inc = inc; b.N = N; b.M = M; b.K = K;
     if (E8) b.edges8 = static_cast<const wg_edge8 *>(edges);
@@ -2562,7 +2694,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
     lean_load<1, E8>(b, kp, action, action_stride, t, lane, L);
     if (kp.prio) __builtin_amdgcn_s_setprio(0);
     STAMP(1);
-    lean_compute<IN3D, 1, false, E8>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
+    if constexpr (AR) lean_compute<IN3D, 1, false, E8, true>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L, true, ar);
+    else lean_compute<IN3D, 1, false, E8>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
 }
 
 // n_steps env steps in one launch (wg_rollout): the tile's static inputs (spring records, incidence lists, masses,
@@ -3244,16 +3377,23 @@ bool lean_geo(const wg_batch *b, int obs_stride, LeanGeo *out, int spring_mode =
 // grid of a lean launch: one tile (64 / M walkers) per wave
 int lean_blocks(const wg_batch *b, const LeanGeo &g) { return (b->N + g.wpb * g.wpw - 1) / (g.wpb * g.wpw); }
 
+// ar_mode (wg_params.auto_reset) != 0: the AR instances (the auto-reset tail, ABI 16)
 int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const float *a, int cols, int astride,
-                const wg_outputs &o, const LeanGeo &g, hipStream_t st) {
+                const wg_outputs &o, const LeanGeo &g, hipStream_t st, int ar_mode = 0) {
     const int blocks = lean_blocks(b, g);
     const int ne = (g.wpw * b->K + 63) / 64;
     // WG_LDS_PAD (diagnostic): extra LDS bytes per workgroup, to measure the kernel at lower occupancy
     const int lds = g.wpb * g.slice + std::max(0, env_int("WG_LDS_PAD", 0));
     const bool e8 = use_edge8(b, g);
 #define WG_LAUNCH_LEAN(D3, NE_, E8_)                                                                             \
-    WG_KLAUNCH((walker_step_lean<D3, NE_, E8_>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st, *b, kp, a,   \
-               cols, astride, kout(o), g)
+    do {                                                                                                         \
+        if (ar_mode)                                                                                             \
+            WG_KLAUNCH((walker_step_lean<D3, NE_, E8_, true>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds,    \
+                       st, *b, kp, a, cols, astride, kout(o), g, kreset(o, ar_mode));                            \
+        else                                                                                                     \
+            WG_KLAUNCH((walker_step_lean<D3, NE_, E8_>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st,      \
+                       kbatch15(b), kp, a, cols, astride, kout(o), g, KNoReset{});                               \
+    } while (0)
 #define WG_LEAN_NE(D3, E8_)                                                    \
     do {                                                                       \
         if (ne == 2) WG_LAUNCH_LEAN(D3, 2, E8_);                               \
@@ -3262,12 +3402,20 @@ int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const float *a,
         else WG_LAUNCH_LEAN(D3, 8, E8_);                                       \
     } while (0)
     // (the NE = 1 entry with preloaded arguments; the compact records take the spring records' slot)
+#define WG_LEAN1_ARGS(E8_)                                                                                       \
+    b->pos, b->vel, (E8_) ? static_cast<const void *>(b->edges8) : static_cast<const void *>(b->edges), b->inc,  \
+        b->N, b->M, b->K, g.wpw, g.wpb,                                                                          \
+        (int)((unsigned)g.nblk | ((unsigned)(kp.xcd & 2) << 29) | ((unsigned)(kp.prio != 0) << 31)), *b, kp, a,  \
+        cols, astride, kout(o), g
 #define WG_LAUNCH_LEAN1(D3, E8_)                                                                                 \
-    WG_KLAUNCH((walker_step_lean1<D3, E8_>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st, b->pos, b->vel,  \
-               (E8_) ? static_cast<const void *>(b->edges8) : static_cast<const void *>(b->edges), b->inc, b->N, \
-               b->M, b->K, g.wpw, g.wpb,                                                                         \
-               (int)((unsigned)g.nblk | ((unsigned)(kp.xcd & 2) << 29) | ((unsigned)(kp.prio != 0) << 31)), *b,  \
-               kp, a, cols, astride, kout(o), g)
+    do {                                                                                                         \
+        if (ar_mode)                                                                                             \
+            WG_KLAUNCH((walker_step_lean1<D3, E8_, true>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st,    \
+                       WG_LEAN1_ARGS(E8_), kreset(o, ar_mode));                                                  \
+        else                                                                                                     \
+            WG_KLAUNCH((walker_step_lean1<D3, E8_>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st,          \
+                       WG_LEAN1_ARGS(E8_), KNoReset{});                                                          \
+    } while (0)
     if (ne <= 1) {
         if (in3d) { if (e8) WG_LAUNCH_LEAN1(true, true); else WG_LAUNCH_LEAN1(true, false); }
         else { if (e8) WG_LAUNCH_LEAN1(false, true); else WG_LAUNCH_LEAN1(false, false); }
@@ -3277,6 +3425,7 @@ int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const float *a,
         if (e8) WG_LEAN_NE(false, true); else WG_LEAN_NE(false, false);
     }
 #undef WG_LAUNCH_LEAN1
+#undef WG_LEAN1_ARGS
 #undef WG_LEAN_NE
 #undef WG_LAUNCH_LEAN
     const hipError_t e = hipGetLastError();
@@ -3418,6 +3567,24 @@ int run(const wg_batch *b, const wg_params *p, const float *action, int32_t cols
         return fail(WG_EINVAL, "pair_mode %d needs spring_mode 0", p->pair_mode);
     if (step && (p->pair_mode & 4) && !b->radius)
         return fail(WG_EINVAL, "pair_mode 4 (bounce) needs the radius array");
+    // auto-reset (ABI 16): fused into the lean step kernels only; everything it reads checked here
+    const int ar_mode = step ? p->auto_reset : 0;
+    if (ar_mode) {
+        if (ar_mode & ~3) return fail(WG_EINVAL, "auto_reset %d: bits 1 (done) and 2 (non-finite) only", ar_mode);
+        if (!b->init_pos || !b->init_vel || !b->init_acc || !b->init_muscle_x)
+            return fail(WG_EINVAL, "auto_reset needs the snapshot (init_pos, init_vel, init_acc, init_muscle_x)");
+        if (!b->episodes) return fail(WG_EINVAL, "auto_reset needs the episodes array");
+        if (b->reset_noise && b->reset_noise_rows < 1)
+            return fail(WG_EINVAL, "auto_reset: reset_noise with reset_noise_rows %d < 1", b->reset_noise_rows);
+        if (b->reset_noise && b->reset_noise_stride < 3ll * b->N * b->M)
+            return fail(WG_EINVAL, "auto_reset: reset_noise_stride %lld < 3 * P = %lld",
+                        (long long)b->reset_noise_stride, 3ll * b->N * b->M);
+        if (p->pair_mode != 0) return fail(WG_EINVAL, "auto_reset needs pair_mode 0 (pair_mode %d)", p->pair_mode);
+        if (!use_lean)
+            return fail(WG_EINVAL, "auto_reset needs a batch the lean kernel takes (uniform, M dividing 64, "
+                                   "spring_mode 0, pair_mode 0, WG_LEAN not 0): the ragged wave kernel and the "
+                                   "workgroup kernel have no auto-reset");
+    }
     if (check_only) return 0;   // wg_step_ranges: every range's arguments checked before any range launches
     const bool extras = out.nonfinite || out.momentum;   // opt-in per-walker info after each step (ABI 10)
     auto info_pass = [&](const wg_outputs &os) -> int {
@@ -3429,7 +3596,8 @@ int run(const wg_batch *b, const wg_params *p, const float *action, int32_t cols
     };
     // (the resident rollout keeps the state in registers between steps: with the per-step info extras requested the
     // steps run as per-step launches instead, bit-identical)
-    if (resident && use_lean && p->pair_mode == 0 && !extras)   // one launch for every step, state in registers
+    // (and with auto-reset: the resident kernel has no reset tail)
+    if (resident && use_lean && p->pair_mode == 0 && !extras && !ar_mode)   // one launch for every step, state in registers
         return launch_lean_rollout(b, kp, p->in3d != 0, action, cols, astride, action ? astep : 0, out, n_steps, lg,
                                    stream);
     // acc and contact are read by nothing on the step path and overwritten by the next step: only the call's last step
@@ -3446,8 +3614,10 @@ int run(const wg_batch *b, const wg_params *p, const float *action, int32_t cols
         if (os.steps) os.steps += s * os.out_step;
         if (os.nonfinite) os.nonfinite += s * os.out_step;
         if (os.momentum) os.momentum += 3 * s * os.out_step;
+        if (os.reset) os.reset += s * os.out_step;
+        if (os.final_obs) os.final_obs += s * os.obs_step;
         const float *a = action ? action + s * astep : nullptr;
-        if (step && use_lean) rc = launch_lean(b, kp, p->in3d != 0, a, cols, astride, os, lg, stream);
+        if (step && use_lean) rc = launch_lean(b, kp, p->in3d != 0, a, cols, astride, os, lg, stream, ar_mode);
         else if (use_waves) rc = launch_waves(b, kp, p->in3d != 0, a, cols, astride, os, plan, plan_blocks, rgeo, stream);
         else rc = step ? dispatch<true>(b, kp, p->in3d != 0, a, cols, astride, os, plan, blocks, g, stream)
                        : dispatch<false>(b, kp, p->in3d != 0, nullptr, 0, 0, os, plan, blocks, g, stream);

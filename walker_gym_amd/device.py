@@ -64,6 +64,10 @@ class DeviceBatch:
         self.charge = _to_dev(host.charge, dv) if host.charge is not None else None
         self.bounce_set = _to_dev(host.bounce_set, dv) if host.bounce_set is not None else None
         self.radius = None   # allocated by enable_radius(): the step writes it, so only when bounce needs it
+        # auto-reset (ABI 16): the episode-start snapshot, the resets each walker has taken and the reset-noise pool
+        # [rows, P, 3] (or none), set by set_auto_reset(); not part of state_dict / STATE
+        self.init_pos = self.init_vel = self.init_acc = self.init_muscle_x = None
+        self.episodes = self.reset_noise = None
         # placeholders so that zero-size arrays still have a valid device pointer
         self._dummy = torch.zeros(16, dtype=torch.float32, device=dv)
         # ragged batches are stored in wave-tile / size order (layout.pack): row = caller index of each stored walker
@@ -169,6 +173,54 @@ class DeviceBatch:
             self.radius = _to_dev(r, self.device)
             self.struct = self._make_struct()
 
+    def set_auto_reset(self, noise: Optional[torch.Tensor] = None) -> None:
+        """Take the current state as the episode-start snapshot of the fused auto-reset (wg_batch.init_*), zero the
+        episode counters and install the reset-noise pool ([rows, P, 3] float32 in the stored mass order, or None)."""
+        if self.ragged:
+            raise ValueError("auto-reset: uniform batches of the lean kernel only")
+        if noise is not None and (noise.dim() != 3 or tuple(noise.shape[1:]) != (self.P, 3) or noise.shape[0] < 1 or
+                                  noise.dtype != torch.float32 or not noise.is_contiguous() or
+                                  noise.device != self.device):
+            raise ValueError(f"reset noise must be a contiguous float32 [rows, {self.P}, 3] tensor on {self.device}")
+        self.snapshot_episode_start()
+        self.episodes = torch.zeros(self.N, dtype=torch.int32, device=self.device)
+        self.reset_noise = noise
+        self.struct = self._make_struct()
+
+    def snapshot_episode_start(self) -> None:
+        """The current pos / vel / acc / muscle_x as the episode start (in place once the snapshot exists, so structs
+        and captured graphs that hold its pointers stay valid)."""
+        for name in ("pos", "vel", "acc", "muscle_x"):
+            cur, snap = getattr(self, name), getattr(self, "init_" + name)
+            if snap is None:
+                setattr(self, "init_" + name, cur.clone())
+            else:
+                snap.copy_(cur)
+
+    def clear_auto_reset(self) -> None:
+        self.init_pos = self.init_vel = self.init_acc = self.init_muscle_x = None
+        self.episodes = self.reset_noise = None
+        self.struct = self._make_struct()
+
+    def _auto_reset_fields(self, w0: int = 0) -> dict:
+        """wg_batch's ABI 16 fields for the walkers from w0 on: the snapshot and the counters offset like the state, the
+        noise pool at the range's first mass inside every row (the row stride stays the pool's)."""
+        if self.init_pos is None:
+            return {}
+        M, A = self.M, self.A
+
+        def off(t, elems):
+            return C.c_void_p(t.data_ptr() + elems * t.element_size())
+
+        nz = self.reset_noise
+        return dict(init_pos=off(self.init_pos, 3 * M * w0), init_vel=off(self.init_vel, 3 * M * w0),
+                    init_acc=off(self.init_acc, 3 * M * w0),
+                    init_muscle_x=self._p(self.init_muscle_x) if A == 0 else off(self.init_muscle_x, A * w0),
+                    episodes=off(self.episodes, w0),
+                    reset_noise=None if nz is None else off(nz, 3 * M * w0),
+                    reset_noise_rows=0 if nz is None else int(nz.shape[0]),
+                    reset_noise_stride=0 if nz is None else 3 * self.P)
+
     def _p(self, t):
         if t is None:
             return None
@@ -189,7 +241,8 @@ class DeviceBatch:
             muscle_stride=self._p(self.muscle_stride), steps=self._p(self.steps), contact=self._p(self.contact),
             pinned=self._p(self.pinned), charge=self._p(self.charge), radius=self._p(self.radius),
             bounce_set=self._p(self.bounce_set),
-            edges8=self._p(self.edges8) if not r else None, kc=(C.c_float * 4)(*self.kc))
+            edges8=self._p(self.edges8) if not r else None, kc=(C.c_float * 4)(*self.kc),
+            **self._auto_reset_fields())
 
     def sub_struct(self, w0: int, w1: int) -> _lib.WgBatch:
         """A WgBatch view of walkers [w0, w1) of a uniform batch: the same device memory, pointers offset
@@ -217,7 +270,7 @@ class DeviceBatch:
             bounce_set=off(self.bounce_set, M * w0),
             # the compact records hold tile-relative lane roles: only a range that starts on a tile (64 / M walkers)
             edges8=off(self.edges8, 2 * K * w0) if self.edges8 is not None and w0 % (64 // M) == 0 else None,
-            kc=(C.c_float * 4)(*self.kc))
+            kc=(C.c_float * 4)(*self.kc), **self._auto_reset_fields(w0))
 
     def launch_geometry(self) -> dict:
         info = _lib.WgLaunchInfo()
