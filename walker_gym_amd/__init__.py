@@ -21,6 +21,9 @@ def __getattr__(name):
     if name in ("BatchedPhysicsEnv", "EnvParams"):
         from . import batched_env
         return getattr(batched_env, name)
+    if name == "MLPPolicy":
+        from . import policy
+        return policy.MLPPolicy
     if name in ("PhysicsEnv", "make_env"):
         from . import optimized_env
         return getattr(optimized_env, name)

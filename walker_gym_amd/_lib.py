@@ -66,9 +66,17 @@ class WgLaunchInfo(C.Structure):
                 ("lds_bytes", C.c_int32)]
 
 
+class WgPolicy(C.Structure):
+    """wg_policy: the in-kernel policy of wg_rollout_policy and its optional per-step / per-walker outputs."""
+    _fields_ = [("n_sets", C.c_int32), ("obs_dim", C.c_int32), ("hidden", C.c_int32), ("act_dim", C.c_int32),
+                ("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("act_limit", C.c_float),
+                ("action_out", _vp), ("action_out_step", C.c_int64), ("return_out", _vp), ("length_out", _vp)]
+
+
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
            "wg_step_simple", "wg_observe_simple", "wg_reset", "wg_reset_noise", "wg_plan_ragged", "wg_plan_waves",
-           "wg_wave_edge_passes", "wg_plan_errors", "wg_launch_geometry", "wg_launch_floor", "wg_time_step")
+           "wg_wave_edge_passes", "wg_plan_errors", "wg_launch_geometry", "wg_launch_floor", "wg_time_step",
+           "wg_rollout_policy")
 
 _lib = None
 _lock = threading.Lock()
@@ -95,6 +103,8 @@ def load(path: str | None = None):
         L.wg_step.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), _vp, C.c_int32, C.c_int32, C.c_int64,
                               C.POINTER(WgOutputs), C.c_int32, _vp, C.c_int32, _vp]
         L.wg_rollout.argtypes = L.wg_step.argtypes
+        L.wg_rollout_policy.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), C.POINTER(WgPolicy),
+                                        C.POINTER(WgOutputs), C.c_int32, _vp]
         L.wg_step_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,
                                      C.POINTER(_vp)]
         L.wg_run_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,

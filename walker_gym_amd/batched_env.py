@@ -532,6 +532,71 @@ class BatchedPhysicsEnv:
             self.batch.plan_blocks, self._stream()), entry)
         return obs_out, reward_out, done_out
 
+    def rollout_policy(self, policy, n_steps: int, obs_out=None, reward_out=None, done_out=None,
+                       action_out=None) -> dict:
+        """A whole closed-loop episode in ONE launch (wg_rollout_policy): the resident kernel of rollout() with each
+        step's actions computed inside the wave from the walker's own observation row by `policy`, an MLPPolicy
+        (walker_gym_amd.policy) on this device.  Step 0 acts on the observation of the state at entry (what observe()
+        returns), step s + 1 on step s's.  No per-step host work and no action traffic; the per-step buffers are
+        optional and written only when given: obs_out [T, N, D] f32, reward_out [T, N] f32, done_out [T, N] u8,
+        action_out [T, N, C] f32 (the actions applied at each step).  Returns {'returns': [N] f32, the rewards added
+        in step order up to and including the walker's first done step (or all T); 'lengths': [N] i32, the steps
+        counted}.  Walkers keep stepping after done, as in rollout(); there is no auto-reset on this path.
+        Bit-identical to `for t: env.step(policy(env.obs, t))`.
+
+        ValueError (nothing launched, no silent fallback) for a batch the resident kernel does not take (ragged, M not
+        dividing 64, spring_mode or pair_mode set, WG_LEAN=0), with auto-reset enabled, or for a policy that does not
+        fit (D, C, G): close the loop with policy_loop(policy, n_steps) instead, which takes any batch (it binds an
+        MLPPolicy's parameter sets to each walker range's caller rows).  Also ValueError (WG_ERANGE) when the rows,
+        hidden vectors and actions of a workgroup's walkers beside the kernel's own LDS pass 80 KiB (very wide walkers
+        with a large hidden layer)."""
+        from .policy import MLPPolicy
+        alt = "use policy_loop(policy, n_steps), which closes the loop with one step launch per step on any batch"
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError(f"rollout_policy needs an MLPPolicy; for another callable {alt}")
+        T = int(n_steps)
+        if T < 1:
+            raise ValueError(f"rollout_policy: n_steps {n_steps} < 1")
+        if not self.resident_ok():
+            raise ValueError("rollout_policy: only batches of the resident lean kernel (uniform, M dividing 64 with "
+                             f"M >= 4, spring_mode 0, pair_mode 0, WG_LEAN not 0); {alt}")
+        if self._ar_mode:
+            raise ValueError(f"rollout_policy: auto-reset is enabled and the resident loop has no reset tail; {alt}")
+        if policy.D != self.obs_dim:
+            raise ValueError(f"rollout_policy: the policy takes {policy.D} inputs, the observation rows have "
+                             f"{self.obs_dim}")
+        if policy.C > self.batch.A:
+            raise ValueError(f"rollout_policy: the policy has {policy.C} outputs, the walkers {self.batch.A} muscles")
+        if self.N % policy.G != 0:
+            raise ValueError(f"rollout_policy: {policy.G} parameter sets do not divide N = {self.N}; {alt}")
+        dv, N = self.device, self.N
+        for name in ("w1", "b1", "w2", "b2"):
+            t = getattr(policy, name)
+            if t is not None:
+                require_tensor(t, f"policy.{name}", dv, torch.float32)
+        if obs_out is not None:
+            require_tensor(obs_out, "obs_out", dv, torch.float32, (T, N, self.obs_dim))
+        if reward_out is not None:
+            require_tensor(reward_out, "reward_out", dv, torch.float32, (T, N))
+        if done_out is not None:
+            require_tensor(done_out, "done_out", dv, torch.uint8, (T, N))
+        if action_out is not None:
+            require_tensor(action_out, "action_out", dv, torch.float32, (T, N, policy.C))
+        returns = torch.empty(N, dtype=torch.float32, device=dv)
+        lengths = torch.empty(N, dtype=torch.int32, device=dv)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        pol = _lib.WgPolicy(n_sets=policy.G, obs_dim=policy.D, hidden=policy.H, act_dim=policy.C, w1=p(policy.w1),
+                            b1=p(policy.b1), w2=p(policy.w2), b2=p(policy.b2), act_limit=policy.act_limit,
+                            action_out=p(action_out), action_out_step=N * policy.C, return_out=p(returns),
+                            length_out=p(lengths))
+        o = self._outputs(obs_out, reward_out, done_out, None, None, obs_step=N * self.obs_dim, out_step=N,
+                          pad_clean=True)
+        _lib.check(_lib.load().wg_rollout_policy(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
+                                                 C.byref(o), T, self._stream()), "wg_rollout_policy")
+        self._steps_at = -1   # (as rollout(): the env's one-step outputs are not this call's; a refused call ran nothing)
+        self._stale = frozenset({"centroid_position", "total_energy", "momentum", "nonfinite", "reset", "final_obs"})
+        return {"returns": returns, "lengths": lengths}
+
     def run(self, actions, n_steps: int, info: bool = True, lanes: Optional[int] = None, resident: bool = False,
             record: Optional[dict] = None, _only: Optional[int] = None):
         """Throughput path: n_steps env steps in one C call; step s acts with actions[s % T]
@@ -772,7 +837,7 @@ class BatchedPhysicsEnv:
             ev = self._run_events = (objs, (C.c_void_p * lanes)(*[e.cuda_event for e in objs]))
         return ev[1]
 
-    def policy_loop(self, policy, n_steps: int, lanes: Optional[int] = None, graph: bool = False) -> None:
+    def policy_loop(self, policy, n_steps: int, lanes: Optional[int] = None, graph: bool = False):
         """A closed loop with a per-walker policy, the walker ranges pipelined: at every step, each range computes its
         actions from ITS OWN current observation rows, action = policy(obs[w0:w1], t), and launches its step right
         after, on its own stream; the ranges never wait for one another.  So one range's step t + 1 fills the other's
@@ -781,10 +846,13 @@ class BatchedPhysicsEnv:
         each launch drains on its own (the drain is what separates one launch from two overlapped ranges).
 
         policy(obs_rows [n_r, D] view, t) -> actions [n_r, A_cols] float32, contiguous, on the current (range)
-        stream.  It must be row-wise — walker w's action a function of walker w's observation only — which is what
+        stream.  A policy that offers for_rows(first_row, N) and for_row_index(rows, N) (MLPPolicy: several parameter
+        sets, caller row r using set r // (N // G)) is bound to each range's caller rows, so it never has to guess which
+        walkers a slice of rows belongs to.  It must be row-wise — walker w's action a function of walker w's observation only — which is what
         makes the ranges independent; then the results are bit-identical to `for t: env.step(policy(env.obs, t))`.
         graph=True captures the n_steps x ranges loop (policy kernels included) as one HIP graph and replays it once
-        (no per-step host cost; the policy must be capturable).  After the call obs / reward / done / info hold the last
+        (no per-step host cost; the policy must be capturable).  It then returns the captured loop: its replay() runs the
+        same n_steps again from the current state (eager calls return None).  After the call obs / reward / done / info hold the last
         step's outputs.
 
         Ragged batches (stored in wave-tile order, wg_batch.row) run ranges of plan blocks.  The wave tiles are packed
@@ -834,6 +902,16 @@ class BatchedPhysicsEnv:
                 args.append((self.obs[w0:w1], None, w1 - w0, C.byref(sub), C.byref(o), None, 0))
                 aoff.append(0)   # (a sub-batch indexes its actions from its own first walker)
 
+        # a policy whose output depends on the walker index (MLPPolicy with G > 1): one bound policy per range, made
+        # here (outside any capture), for the range's caller rows: a slice [row0, row0 + n_r), or a scattered ragged
+        # range's row index
+        pols = [policy] * lanes
+        if hasattr(policy, "for_rows") and hasattr(policy, "for_row_index"):
+            row0 = [int(b.plan_host[bb[i]]) for i in range(lanes)] if b.ragged else bounds[:lanes]
+            pols = [policy.for_rows(row0[i], self.N, args[i][2]) if args[i][1] is None
+                    else policy.for_row_index(args[i][1], self.N)
+                    for i in range(lanes)]
+
         def check(a, n_r):
             require_tensor(a, "policy actions", dev, f32)
             if a.dim() != 2 or a.shape[0] != n_r:
@@ -865,7 +943,7 @@ class BatchedPhysicsEnv:
                     for (r, (obs_r, idx, n_r, b_ref, o_ref, plan, nblk)), (st, st_ptr) in zip(rng, sts):
                         if multi:
                             torch.cuda.set_stream(st)
-                        a = policy(obs_r if idx is None else self.obs.index_select(0, idx), t)
+                        a = pols[r](obs_r if idx is None else self.obs.index_select(0, idx), t)
                         # the full check at a range's first step, then the same shape, dtype, device and layout
                         if shapes[r] is None:
                             check(a, n_r)
@@ -925,6 +1003,7 @@ class BatchedPhysicsEnv:
             parts.append((g, st))
         self._policy_graph = _RangeGraphs(parts, cur)   # (kept until the next call: the replay may still be running)
         self._policy_graph.replay()
+        return self._policy_graph   # replay() runs the same n_steps again from the current state
 
     def _caller_bounds(self, lanes: int):
         """Plan-block bounds of `lanes` ragged walker ranges, each split moved to the nearest block whose stored prefix

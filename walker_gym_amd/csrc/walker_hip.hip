@@ -2307,10 +2307,15 @@ __device__ __forceinline__ void lean_obs_rows(float *obs, int stride, const KPar
 // RES (walker_rollout_lean): the tile's state stays in L across steps; it is written to HBM only when `last`.
 // AR (auto-reset, ABI 16; never with RES): after the outputs, the walkers whose episode this step ended are put back to
 // the snapshot (b.init_*) with their reset noise and their fresh observation rows, in a rare wave-uniform branch.
-template <bool IN3D, int NE, bool RES = false, bool E8 = false, bool AR = false>
+// POL (walker_rollout_policy; with RES): what the policy's next observation row and the episode return need beside the
+// state carried in L leaves in `po` (acc, the position sums; reward and done in the walker's lane q == 0), and reward /
+// done are computed whether or not they are stored.  Dead code in every other instance.
+struct LeanPolOut { float ax, ay, az, sx, sy, sz, reward; int done; };
+template <bool IN3D, int NE, bool RES = false, bool E8 = false, bool AR = false, bool POL = false>
 __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &kp, const KOut &o,
                                              const LeanGeo &lg, char *sl, const LeanTile &t, int lane,
-                                             LeanIn<NE, E8> &L, bool last = true, const KReset &ar = KReset{}) {
+                                             LeanIn<NE, E8> &L, bool last = true, const KReset &ar = KReset{},
+                                             LeanPolOut *po = nullptr) {
     const bool store = !RES || last;
     const int M = b.M, K = b.K, A = b.A;
     const int w0 = t.w0, nE = t.nE;
@@ -2527,11 +2532,15 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
             if (RES) L.wsteps = steps;
             if (o.steps) *WG_ST(o.steps, wg, 1) = steps;
             const float cy = ysum * lg.invM;
-            if (o.reward) {
+            if constexpr (POL) {   // the same expression, kept for the return
+                const float vpen = (-(vsum * lg.invM)) * 0.1f;
+                po->reward = (cy + vpen) + neg_half_count((int)__popcll(hb & gmask));
+                if (o.reward) *WG_ST(o.reward, wg, 1) = po->reward;
+            } else if (o.reward) {
                 const float vpen = (-(vsum * lg.invM)) * 0.1f;
                 *WG_ST(o.reward, wg, 1) = (cy + vpen) + neg_half_count((int)__popcll(hb & gmask));
             }
-            if (o.done || (AR && (ar.mode & 1))) {
+            if (o.done || (AR && (ar.mode & 1)) || POL) {
                 int done = steps >= kp.max_steps;
                 if (!done && cy < kp.done_y) done = 1;
                 if (!done && steps > 100) done = (sb & gmask) == gmask;
@@ -2614,6 +2623,11 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
         L.p3[0] = px; L.p3[1] = py; L.p3[2] = pz;
         L.v3[0] = vx; L.v3[1] = vy; L.v3[2] = vz;
         L.x = x;
+    }
+    if constexpr (POL) {
+        po->ax = ax; po->ay = ay; po->az = az;
+        po->sx = sx; po->sy = sy; po->sz = sz;
+        po->done = ep_done;
     }
     STAMP(6);
 #ifdef WG_STAMPS
@@ -2755,6 +2769,238 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
         lean_compute<IN3D, NE, true, E8>(b, kp, os, lg, smem + wv * lg.slice, ts, ln, L, s == n_steps - 1);
         L.a = a_next;
         wave_sync();   // this step's LDS reads stay ahead of the next step's writes
+    }
+}
+
+// ------------------------------------------------------------------ closed-loop resident rollout (wg_rollout_policy)
+// The policy of include/walker_hip.h (wg_policy): piecewise-linear, stateless, at most one hidden layer, n_sets
+// parameter sets.  Kernel arguments of walker_rollout_policy.
+struct KPolicy {
+    const float *w1, *b1, *w2, *b2;
+    float *action_out, *return_out;
+    int32_t *length_out;
+    int64_t action_out_step;
+    float act_limit;
+    int D, H, C;
+    int wps;                       // walkers per parameter set (N / n_sets)
+    int off_row, off_h, off_a;     // byte offsets in the wave's LDS slice: observation rows | hidden units | actions
+    int off_w;                     // ... | per walker: return, steps counted, still counting, parameter set
+    int off_wts;                   // >= 0: a shared policy's weights staged in the workgroup's LDS (w1 | w2) at this byte
+                                   // offset, behind the waves' slices; < 0: every lane reads its set's weights through L2
+};
+
+// One unit of a layer, the contract's chain: acc = bias; acc = RN32(acc + RN32(x[i] * w[i][j])) for i ascending, the
+// multiply and the add separate roundings (no FMA).  x: the walker's input vector in LDS (the same address in every lane
+// of the walker: a broadcast); w: column j of the set's [n][stride] matrix.
+__device__ __forceinline__ float policy_unit(const float *x, const float *__restrict__ w, int n, int stride, float bias) {
+    float acc = bias;
+    int i = 0;
+    // eight weights in flight before the chain consumes the first (the compiler, left alone, waited for every load
+    // before its multiply: one memory latency per input); the compiler barrier keeps the loads ahead of the arithmetic
+    for (; i + 8 <= n; i += 8) {
+        float wv[8], xv[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) wv[k] = w[(size_t)(i + k) * (size_t)stride];
+#pragma unroll
+        for (int k = 0; k < 8; k++) xv[k] = x[i + k];
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int k = 0; k < 8; k++) acc = __fadd_rn(acc, __fmul_rn(xv[k], wv[k]));
+    }
+    for (; i < n; i++) acc = __fadd_rn(acc, __fmul_rn(x[i], w[(size_t)i * (size_t)stride]));
+    return acc;
+}
+// Two units of a lane (columns j and j + d) side by side: each unit's chain is the one above, op for op; the pair
+// shares the x[i] read, and its two multiplies and two adds can issue as packed float32 operations (unfused).
+__device__ __forceinline__ void policy_unit2(const float *x, const float *__restrict__ w, int n, int stride, int d,
+                                             float bias0, float bias1, float &r0, float &r1) {
+    float a0 = bias0, a1 = bias1;
+    int i = 0;
+    for (; i + 4 <= n; i += 4) {   // (eight weights in flight, as policy_unit)
+        float w0[4], w1[4], xv[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const float *wi = w + (size_t)(i + k) * (size_t)stride;
+            w0[k] = wi[0]; w1[k] = wi[d];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) xv[k] = x[i + k];
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            a0 = __fadd_rn(a0, __fmul_rn(xv[k], w0[k]));
+            a1 = __fadd_rn(a1, __fmul_rn(xv[k], w1[k]));
+        }
+    }
+    for (; i < n; i++) {
+        const float xv = x[i];
+        const float *wi = w + (size_t)i * (size_t)stride;
+        a0 = __fadd_rn(a0, __fmul_rn(xv, wi[0]));
+        a1 = __fadd_rn(a1, __fmul_rn(xv, wi[d]));
+    }
+    r0 = a0; r1 = a1;
+}
+
+// The actions of the wave's walkers from their state: every mass and muscle lane writes its piece of its walker's
+// observation row into the wave's LDS slice (lean_obs_rows itself, with the slice as the destination: the rows the
+// policy reads are the rows the step stores, by construction), then the walker's M lanes share the units of each layer,
+// lane q taking units q, q + M, ...; the hidden vector and the actions go through LDS.  Returns the muscle lane's action
+// (0 where the lane does not act).  act_dst: this step's action_out rows, or NULL.
+template <bool IN3D>
+__device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &kp, const KPolicy &pol, const LeanGeo &lg,
+                                             char *smem, char *sl, const LeanTile &t, const float *p3, const float *v3,
+                                             const LeanPolOut &ps, float x, float *act_dst) {
+    const int M = b.M, D = pol.D, H = pol.H, C = pol.C;
+    float *row = reinterpret_cast<float *>(sl + pol.off_row);
+    float *hid = reinterpret_cast<float *>(sl + pol.off_h);
+    float *act = reinterpret_cast<float *>(sl + pol.off_a);
+    lean_obs_rows<IN3D>(row, D, kp, M, b.A, 0, t.wl, t.q, t.mu_wl, t.mu_ua, t.is_mass, t.is_mus, p3[0], p3[1], p3[2],
+                        v3[0], v3[1], v3[2], ps.ax, ps.ay, ps.az, ps.sx, ps.sy, ps.sz, ps.sx * lg.invM, ps.sy * lg.invM,
+                        ps.sz * lg.invM, x);
+    wave_sync();
+    // the walker's parameter set, from its LDS record (a register carried across the step would spill)
+    const uint32_t gset = t.is_mass ? reinterpret_cast<const uint32_t *>(sl + pol.off_w)[4 * t.wl + 3] : 0u;
+    const float *xin = row + t.wl * D;   // (read by the tile's mass lanes only: t.wl < t.nw)
+    int n = D;
+    if (H > 0) {   // wave-uniform
+        if (t.is_mass) {
+            // the lane's units two at a time (j and j + M; a lane with an odd count repeats its last unit and drops
+            // the copy)
+            for (int j = t.q; j < H; j += 2 * M) {
+                const bool two = j + M < H;
+                const int d = two ? M : 0;
+                const float *bp = pol.b1 ? pol.b1 + (size_t)gset * (size_t)H + j : nullptr;
+                const float bias0 = bp ? bp[0] : 0.f, bias1 = bp ? bp[d] : 0.f;
+                float z0, z1;
+                // (two calls: the staged weights are read with LDS instructions, the others with global loads)
+                if (pol.off_wts >= 0)
+                    policy_unit2(xin, reinterpret_cast<const float *>(smem + pol.off_wts) + j, D, H, d, bias0, bias1, z0, z1);
+                else
+                    policy_unit2(xin, pol.w1 + (size_t)gset * (size_t)D * (size_t)H + j, D, H, d, bias0, bias1, z0, z1);
+                hid[t.wl * H + j] = (z0 > 0.f) ? z0 : 0.f;   // (a NaN becomes +0)
+                if (two) hid[t.wl * H + j + M] = (z1 > 0.f) ? z1 : 0.f;
+            }
+        }
+        wave_sync();
+        xin = hid + t.wl * H;
+        n = H;
+    }
+    if (t.is_mass) {
+        const float lim = pol.act_limit;
+        for (int j = t.q; j < C; j += M) {
+            const float bias = pol.b2 ? pol.b2[(size_t)gset * (size_t)C + j] : 0.f;
+            const float y = pol.off_wts >= 0
+                                ? policy_unit(xin, reinterpret_cast<const float *>(smem + pol.off_wts) + D * H + j, n, C,
+                                              bias)
+                                : policy_unit(xin, pol.w2 + (size_t)gset * (size_t)n * (size_t)C + j, n, C, bias);
+            const float a = (y < -lim) ? -lim : ((y > lim) ? lim : y);   // (a NaN passes through)
+            act[t.wl * C + j] = a;
+            if (act_dst) act_dst[(size_t)(uint32_t)(t.w0 + t.wl) * (size_t)C + j] = a;
+        }
+    }
+    wave_sync();
+    return t.acts ? act[t.mu_wl * C + t.mu_ua] : 0.f;
+}
+
+// n_steps closed-loop env steps in one launch: walker_rollout_lean with each step's actions computed in the wave from
+// the observation row of the state the step starts from (step 0: the state at entry, wg_observe's row of it), instead
+// of read from an action array.  The per-step outputs are optional; each walker's return (rewards added in step order
+// up to and including its first done step) and the steps counted are carried in its lane q == 0 and stored after the
+// last step.  The step itself is walker_rollout_lean's, op for op.
+template <bool IN3D, int NE, bool E8>
+// (register budget: one wave per SIMD fewer than walker_rollout_lean.  The LDS slice with the rows already holds the
+// canonical walker to 4 waves per SIMD, the NE 8 shapes to 2, and the latency-bound NE 1 batches run one)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3 : 4))) void walker_rollout_policy(
+    wg_batch b, KParams kp, KPolicy pol, KOut o, int n_steps, LeanGeo lg) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tile = blockIdx.x * lg.wpb + wv;
+    if (pol.off_wts >= 0) {   // a shared policy: its weights into the workgroup's LDS once, by every wave of it
+        float *sw = reinterpret_cast<float *>(smem + pol.off_wts);
+        const int n1 = pol.D * pol.H, n2 = (pol.H > 0 ? pol.H : pol.D) * pol.C;
+        for (int i = threadIdx.x; i < n1; i += 64 * lg.wpb) sw[i] = pol.w1[i];
+        for (int i = threadIdx.x; i < n2; i += 64 * lg.wpb) sw[n1 + i] = pol.w2[i];
+        __syncthreads();      // (the only workgroup barrier: the waves run on their own from here)
+    }
+    if (tile * lg.wpw >= b.N) return;
+    char *sl = smem + wv * lg.slice;
+    LeanTile t = lean_tile_of(b, nullptr, pol.C, lg, tile, lane);
+    t.acts = t.is_mus && t.mu_ua < pol.C;
+    LeanIn<NE, E8> L;
+    if (kp.prio) __builtin_amdgcn_s_setprio(2);
+    lean_load<NE, E8>(b, kp, nullptr, 0, t, lane, L);
+    // what lean_load reads only beside an action array: the muscles' regulation bounds and strides; and the entry
+    // state's acc (the resident kernel carries none: its steps overwrite it unread)
+    LeanPolOut ps{};
+    if (t.nU > 0) {   // wave-uniform
+        const uint32_t ul = t.U0 + min(lane, t.nU - 1);
+        const float2 bd = at_u32(reinterpret_cast<const float2 *>(b.muscle_bounds), 8u * ul);
+        L.lo = bd.x; L.hi = bd.y;
+        if (kp.action_mode == 1) L.stp = at_u32(b.muscle_stride, 4u * ul);
+    }
+    {
+        const float *ga = &at_u32(b.acc, 12u * (t.P0 + min(lane, t.nP - 1)));
+        ps.ax = ga[0]; ps.ay = ga[1]; ps.az = ga[2];
+    }
+    if (kp.prio) __builtin_amdgcn_s_setprio(0);
+    if (!t.is_mus) { L.lo = 0.f; L.hi = 0.f; L.stp = 0.f; }
+    if (!t.is_mass) { ps.ax = 0.f; ps.ay = 0.f; ps.az = 0.f; }
+    {   // the incidence lists are static: into LDS once
+        uint32_t *s_inc = reinterpret_cast<uint32_t *>(sl + lg.off_inc);
+#pragma unroll
+        for (int it = 0; it < NE; it++)
+            if (lane + 64 * it < t.nE) s_inc[lane + 64 * it] = L.gi[it];
+    }
+    {   // the entry state's position sums, as the step leaves them for every later row
+        const WalkerSums fs = walker_sums(L.p3[0], L.p3[1], L.p3[2], 0.f, 0.f, 0.f, lane & ~(b.M - 1), b.M, lane);
+        ps.sx = fs.sx; ps.sy = fs.sy; ps.sz = fs.sz;
+    }
+    // per walker, in LDS (the carried registers are the state's): the return so far, the steps counted, whether the
+    // walker still counts (no done yet), and its parameter set (stored walker w uses set w / (N / n_sets); a set
+    // boundary may fall inside the tile).  Written and updated by the walker's lane q == 0.
+    if (t.is_mass && t.q == 0) {
+        uint32_t *wk = reinterpret_cast<uint32_t *>(sl + pol.off_w) + 4 * t.wl;
+        wk[0] = __float_as_uint(0.f); wk[1] = 0u; wk[2] = 1u;
+        wk[3] = (uint32_t)(t.w0 + t.wl) / (uint32_t)pol.wps;
+    }
+#pragma clang loop unroll(disable)
+    for (int s = 0; s < n_steps; s++) {
+        // (the lane index opaque each step, the static inputs pinned: as walker_rollout_lean)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        LeanTile ts = lean_tile_of(b, nullptr, pol.C, lg, tile, ln);
+        ts.acts = ts.is_mus && ts.mu_ua < pol.C;
+        L.a = lean_policy<IN3D>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x,
+                                pol.action_out ? pol.action_out + (size_t)s * (size_t)pol.action_out_step : nullptr);
+        KOut os = o;
+        if (os.obs) os.obs += (size_t)s * os.obs_step;
+        if (os.reward) os.reward += (size_t)s * os.out_step;
+        if (os.done) os.done += (size_t)s * os.out_step;
+        if (os.energy) os.energy += (size_t)s * os.out_step;
+        if (os.centroid) os.centroid += 3 * (size_t)s * os.out_step;
+        if (os.steps) os.steps += (size_t)s * os.out_step;
+        asm volatile("" : "+v"(L.mf), "+v"(L.io0), "+v"(L.io1), "+v"(L.lo), "+v"(L.hi), "+v"(L.stp));
+#pragma unroll
+        for (int it = 0; it < NE; it++) {
+            if constexpr (E8) asm volatile("" : "+v"(L.er[it].w), "+v"(L.er[it].rest));
+            else asm volatile("" : "+v"(L.er[it].ij), "+v"(L.er[it].rest), "+v"(L.er[it].k), "+v"(L.er[it].c));
+        }
+        lean_compute<IN3D, NE, true, E8, false, true>(b, kp, os, lg, sl, ts, ln, L, s == n_steps - 1, KReset{}, &ps);
+        if (ts.is_mass && ts.q == 0) {   // (the lane that holds the walker's reward and done)
+            uint32_t *wk = reinterpret_cast<uint32_t *>(sl + pol.off_w) + 4 * ts.wl;
+            if (wk[2]) {
+                wk[0] = __float_as_uint(__uint_as_float(wk[0]) + ps.reward);
+                wk[1] = wk[1] + 1u;
+                wk[2] = ps.done == 0;
+            }
+        }
+        wave_sync();   // this step's LDS reads stay ahead of the next step's writes
+    }
+    if (t.is_mass && t.q == 0) {
+        const uint32_t *wk = reinterpret_cast<const uint32_t *>(sl + pol.off_w) + 4 * t.wl;
+        const uint32_t wg = (uint32_t)(t.w0 + t.wl);
+        if (pol.return_out) pol.return_out[wg] = __uint_as_float(wk[0]);
+        if (pol.length_out) pol.length_out[wg] = (int32_t)wk[1];
     }
 }
 
@@ -3459,6 +3705,101 @@ int launch_lean_rollout(const wg_batch *b, const KParams &kp, bool in3d, const f
     return 0;
 }
 
+// a batch's observation row length under p: Creature.getstat's list (gym/optimized_walker.py:129-162)
+int obs_row_len(const wg_batch *b, const wg_params *p) {
+    return 3 * (p->in3d ? 3 : 2) * b->M + (p->conmid ? 3 : 0) + b->A;
+}
+
+// wg_rollout_policy: every argument checked, then one walker_rollout_policy launch.  The wave's LDS slice is the lean
+// kernel's plus the walkers' observation rows, hidden vectors and actions.
+int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o, int32_t n_steps,
+                   hipStream_t stream) {
+    int rc = validate(b);
+    if (rc) return rc;
+    if (!p) return fail(WG_EINVAL, "null params");
+    if (!pol) return fail(WG_EINVAL, "wg_rollout_policy: null policy");
+    if (!pol->w2) return fail(WG_EINVAL, "wg_rollout_policy: null w2");
+    if (n_steps < 1) return fail(WG_EINVAL, "wg_rollout_policy: n_steps %d < 1", n_steps);
+    if (pol->hidden < 0 || pol->hidden > 256)
+        return fail(WG_EINVAL, "wg_rollout_policy: hidden %d outside 0..256", pol->hidden);
+    if (pol->hidden > 0 && !pol->w1) return fail(WG_EINVAL, "wg_rollout_policy: hidden %d with a null w1", pol->hidden);
+    if (pol->act_dim < 1 || pol->act_dim > b->A)
+        return fail(WG_EINVAL, "wg_rollout_policy: act_dim %d outside 1..A = %d", pol->act_dim, b->A);
+    if (pol->obs_dim != obs_row_len(b, p))
+        return fail(WG_EINVAL, "wg_rollout_policy: obs_dim %d, the batch's rows have %d values", pol->obs_dim,
+                    obs_row_len(b, p));
+    if (pol->n_sets < 1 || b->N % pol->n_sets != 0)
+        return fail(WG_EINVAL, "wg_rollout_policy: n_sets %d does not divide N = %d", pol->n_sets, b->N);
+    if (!(pol->act_limit > 0.f)) return fail(WG_EINVAL, "wg_rollout_policy: act_limit must be > 0 (+inf allowed)");
+    if (p->auto_reset != 0)
+        return fail(WG_EINVAL, "wg_rollout_policy: auto_reset %d (the resident loop has no reset tail)", p->auto_reset);
+    if (p->integrator < 0 || p->integrator > 2) return fail(WG_EINVAL, "integrator must be 0/1 (run1) or 2 (run2)");
+    if (!b->muscle_bounds) return fail(WG_EINVAL, "actions need muscle_bounds");
+    if (p->action_mode == 1 && !b->muscle_stride) return fail(WG_EINVAL, "discrete actions need muscle_stride");
+    wg_outputs out = o ? *o : wg_outputs{};
+    if (out.obs && out.obs_stride < pol->obs_dim)
+        return fail(WG_EINVAL, "wg_rollout_policy: obs_stride %d < obs_dim %d", out.obs_stride, pol->obs_dim);
+    if (out.nonfinite || out.momentum || out.reset || out.final_obs)
+        return fail(WG_EINVAL, "wg_rollout_policy: nonfinite / momentum / reset / final_obs are not produced here");
+    LeanGeo lg{};
+    if (b->ragged || p->spring_mode != 0 || p->pair_mode != 0 ||
+        !lean_geo(b, out.obs ? out.obs_stride : 0, &lg, p->spring_mode))
+        return fail(WG_EINVAL, "wg_rollout_policy needs a batch the resident lean kernel takes (uniform, M dividing 64, "
+                               "spring_mode 0, pair_mode 0, WG_LEAN not 0)");
+    if (b->N == 0) return 0;
+    const KParams kp = make_kparams(*p);
+    KPolicy kpol{};
+    kpol.w1 = pol->hidden > 0 ? pol->w1 : nullptr; kpol.b1 = pol->hidden > 0 ? pol->b1 : nullptr;
+    kpol.w2 = pol->w2; kpol.b2 = pol->b2;
+    kpol.action_out = pol->action_out; kpol.return_out = pol->return_out; kpol.length_out = pol->length_out;
+    kpol.action_out_step = pol->action_out_step;
+    kpol.act_limit = pol->act_limit;
+    kpol.D = pol->obs_dim; kpol.H = pol->hidden; kpol.C = pol->act_dim;
+    kpol.wps = b->N / pol->n_sets;
+    kpol.off_row = lg.slice;
+    kpol.off_h = kpol.off_row + align16(lg.wpw * kpol.D * 4);
+    kpol.off_a = kpol.off_h + align16(std::max(1, lg.wpw * kpol.H) * 4);
+    kpol.off_w = kpol.off_a + align16(lg.wpw * kpol.C * 4);
+    lg.slice = kpol.off_w + lg.wpw * 16;
+    int lds = lg.wpb * lg.slice;
+    if (lds > 80 * 1024) return fail(WG_ERANGE, "wg_rollout_policy: workgroup needs %d B of LDS (> 80 KiB)", lds);
+    // a shared policy's weights staged in LDS where that costs no resident wave: as many workgroups per CU (160 KiB of
+    // LDS, the kernel's register budget of 4 waves per SIMD, 3 at NE 8) with the weights as without.  (Staged at the
+    // price of occupancy the canonical batch ran 90.6 us per step with H = 32 against 73.8 through L2; the one-wave
+    // workgroups of a small batch keep their occupancy and run 7.96 against 9.03: profiles/r08_policy_rollout_ab.json.)
+    // WG_POLICY_STAGE (read on every call, like WG_LEAN): 0 never, 2 whenever the workgroup stays within 80 KiB
+    const int wbytes = 4 * (kpol.D * kpol.H + (kpol.H > 0 ? kpol.H : kpol.D) * kpol.C);
+    const int ne = (lg.wpw * b->K + 63) / 64;
+    const int cap = std::max(1, (ne > 4 ? 12 : 16) / lg.wpb);
+    const int stage = env_int("WG_POLICY_STAGE", 1);
+    const bool free_stage = std::min(cap, LDS_LIMIT / lds) == std::min(cap, LDS_LIMIT / (lds + wbytes));
+    kpol.off_wts = -1;
+    if (pol->n_sets == 1 && lds + wbytes <= 80 * 1024 && (stage == 2 || (stage == 1 && free_stage))) {
+        kpol.off_wts = lds;
+        lds += wbytes;
+    }
+    const int blocks = lean_blocks(b, lg);
+    const bool e8 = use_edge8(b, lg);
+#define WG_LAUNCH_RP(D3, NE_, E8_)                                                                               \
+    hipLaunchKernelGGL((walker_rollout_policy<D3, NE_, E8_>), dim3(blocks), dim3(64 * lg.wpb), lds, stream, *b,  \
+                       kp, kpol, kout(out), n_steps, lg)
+#define WG_RP_NE(D3, E8_)                                                                                        \
+    do {                                                                                                         \
+        if (ne <= 1) WG_LAUNCH_RP(D3, 1, E8_);                                                                   \
+        else if (ne == 2) WG_LAUNCH_RP(D3, 2, E8_);                                                              \
+        else if (ne == 3) WG_LAUNCH_RP(D3, 3, E8_);                                                              \
+        else if (ne == 4) WG_LAUNCH_RP(D3, 4, E8_);                                                              \
+        else WG_LAUNCH_RP(D3, 8, E8_);                                                                           \
+    } while (0)
+    if (p->in3d) { if (e8) WG_RP_NE(true, true); else WG_RP_NE(true, false); }
+    else { if (e8) WG_RP_NE(false, true); else WG_RP_NE(false, false); }
+#undef WG_RP_NE
+#undef WG_LAUNCH_RP
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(WG_EHIP, "launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
 // ---- ragged wave kernel (wg_batch.ragged = 2): spring passes, planner, geometry, launch
 // Spring passes of a wave tile from the batch maxima: enough for the longest walker, and for 64 masses of the
 // densest one (K / M springs per mass), rounded up to an instantiated NE (1, 2, 3, 4, 8); 0 = not eligible.
@@ -3662,6 +4003,11 @@ int wg_rollout(const wg_batch *b, const wg_params *p, const float *action, int32
                const int32_t *plan, int32_t plan_blocks, hipStream_t stream) {
     return run(b, p, action, action_cols, action_stride, action_step, o, n_steps, plan, plan_blocks, stream, true,
                true);
+}
+
+int wg_rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o,
+                      int32_t n_steps, hipStream_t stream) {
+    return rollout_policy(b, p, pol, o, n_steps, stream);
 }
 
 int wg_run_ranges(const wg_range *ranges, int32_t n, const wg_params *p, const float *action, int32_t action_cols,
