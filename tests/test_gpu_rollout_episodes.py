@@ -1,0 +1,391 @@
+"""BatchedPhysicsEnv.rollout_episodes (wg_rollout_episodes: closed-loop steps with episode roll-over in one resident
+launch) against the composed CPU reference (tests/episode_cases.py) and against the device loop step(policy(obs)) with
+auto-reset on; and rollout(resident=True) with auto-reset, which now runs the resident kernel's AR twin.  Comparisons
+are bitwise (the non-finite cases: test_gpu_parity._close, bit-identical with NaN == NaN)."""
+import functools
+
+import numpy as np
+import pytest
+
+import episode_cases as ec
+import policy_cases as pc
+from conftest import gpu_available
+
+pytestmark = pytest.mark.gpu
+
+T, SLOTS = ec.T, ec.SLOTS
+CASES = pytest.mark.parametrize("name", ec.NAMES)
+ORACLE = pytest.mark.parametrize("name", [n for n in ec.NAMES if ec.case_of(n).oracle])
+STEP = ("action", "obs", "reward", "done", "reset", "final_obs")
+STATE = ("pos", "vel", "acc", "muscle_x", "steps", "contact", "episodes")
+STATS = ("return_sum", "length_sum", "episodes", "tail_return", "tail_length", "ep_returns", "ep_lengths")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    if not gpu_available():
+        pytest.skip("no ROCm GPU")
+
+
+def _bits(t):
+    a = t.detach().cpu().contiguous().numpy() if hasattr(t, "detach") else np.ascontiguousarray(t)
+    return a.view(np.uint8)
+
+
+def _same(a, b):
+    a, b = _bits(a), _bits(b)
+    return a.shape == b.shape and np.array_equal(a, b)
+
+
+def _env(name, on=("done",), spec=None):
+    from walker_gym_amd.batched_env import BatchedPhysicsEnv
+    cfg = ec.config(name)
+    env = BatchedPhysicsEnv(cfg["spec"] if spec is None else spec, device="cuda:0", **cfg["params"])
+    env.enable_auto_reset(on=on, noise=cfg["pool"], final_obs=True)
+    return env
+
+
+def _state(env):
+    st = {k: getattr(env, k).detach().cpu().numpy().copy() for k in STATE if k != "episodes"}
+    st["episodes"] = env.batch.episodes.detach().cpu().numpy().copy()
+    return st
+
+
+def _buffers(env, Tn, C):
+    import torch
+    dv, N, D = env.device, env.N, env.obs_dim
+    # (NaN / 0xff fills: a value the kernel failed to write cannot pass for one it wrote)
+    return dict(obs_out=torch.full((Tn, N, D), float("nan"), device=dv),
+                reward_out=torch.full((Tn, N), float("nan"), device=dv),
+                done_out=torch.full((Tn, N), 255, dtype=torch.uint8, device=dv),
+                action_out=torch.full((Tn, N, C), float("nan"), device=dv),
+                reset_out=torch.full((Tn, N), 255, dtype=torch.uint8, device=dv),
+                final_obs_out=torch.full((Tn, N, D), float("nan"), device=dv))
+
+
+def _host(buf):
+    return {k[:-4]: v.cpu().numpy() for k, v in buf.items()}
+
+
+def _stats(res):
+    return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+def _device_loop(env, pol, Tn):
+    """step(policy(obs)) with auto-reset on: every step's outputs, final_obs as one step writes it (the rows of the
+    walkers it resets; NaN elsewhere, the buffers' fill)."""
+    env.observe()
+    loop = {k: [] for k in STEP}
+    for t in range(Tn):
+        a = pol.for_rows(0, env.N)(env.obs, t)
+        obs, rew, done, info = env.step(a)
+        sel = info["reset"].cpu().numpy().astype(bool)
+        fo = np.full((env.N, env.obs_dim), np.nan, np.float32)
+        fo[sel] = info["final_obs"].cpu().numpy()[sel]
+        loop["action"].append(a.cpu().numpy().copy()); loop["obs"].append(obs.cpu().numpy().copy())
+        loop["reward"].append(rew.cpu().numpy().copy()); loop["done"].append(done.cpu().numpy().astype(np.uint8))
+        loop["reset"].append(sel.astype(np.uint8)); loop["final_obs"].append(fo)
+    return {k: np.stack(v) for k, v in loop.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def _runs(name):
+    """One fused rollout with every per-step buffer, one with none, and the device step loop, of one case: host copies,
+    computed once and shared by the tests below (never modified)."""
+    import torch
+    case = ec.case_of(name)
+    pol = pc.policy_of(case, "cuda:0")
+    env = _env(name)
+    geo = env.launch_geometry()   # the wave tile the case is there for
+    assert geo["walkers_per_block"] * 64 // geo["threads"] == case.wpw, geo
+    buf = _buffers(env, T, case.C)
+    res = env.rollout_episodes(pol, T, episode_slots=SLOTS, **buf)
+    torch.cuda.synchronize()
+    fused = dict(_host(buf), **_state(env))
+    fused["stats"] = _stats(res)
+    fused["info_episodes"] = env.info()["episodes"].cpu().numpy().copy()
+    env2 = _env(name)
+    res2 = env2.rollout_episodes(pol, T)
+    torch.cuda.synchronize()
+    bare = dict(_state(env2), stats=_stats(res2))
+    ref = _env(name)
+    loop = dict(_device_loop(ref, pol, T), **_state(ref))
+    return fused, bare, loop
+
+
+def _check_against_reference(fused, ref):
+    for k in STEP:
+        a, b = fused[k], np.ascontiguousarray(ref[k]).reshape(fused[k].shape)
+        assert a.dtype == b.dtype and _same(a, b), k
+    st = ref["state"]
+    for k, r in (("pos", "pos"), ("vel", "vel"), ("acc", "acc"), ("muscle_x", "mx"), ("steps", "steps"),
+                 ("episodes", "episodes")):
+        assert _same(fused[k], np.asarray(st[r]).reshape(fused[k].shape).astype(fused[k].dtype)), k
+    assert np.array_equal(fused["contact"].astype(np.uint8).ravel(), np.asarray(st["contact"]).astype(np.uint8).ravel())
+    for k in STATS:
+        assert fused["stats"][k].dtype == ref["stats"][k].dtype and _same(fused["stats"][k], ref["stats"][k]), k
+
+
+@ORACLE
+def test_fused_equals_composed_oracle(name):
+    """Every byte of every step's action / obs / reward / done / reset / final_obs, the final state, every stats array
+    (four slots, fewer than the sunk walkers' sixteen episodes; unfilled slots keep their fill)."""
+    fused, _, _ = _runs(name)
+    ref = ec.reference(name)
+    _check_against_reference(fused, ref)
+    assert np.array_equal(fused["info_episodes"], ref["state"]["episodes"])
+    n = fused["stats"]["episodes"]
+    assert np.isnan(fused["stats"]["ep_returns"][n < SLOTS, -1]).all() and (n < SLOTS).any() and (n > SLOTS).any()
+    assert (fused["stats"]["ep_lengths"][n < SLOTS, -1] == -1).all()
+
+
+def test_fused_equals_composed_oracle_16_byte_records(monkeypatch):
+    import torch
+    monkeypatch.setenv("WG_EDGE8", "0")
+    name = "canonical4-mlp-5sets"
+    case = ec.case_of(name)
+    env = _env(name)
+    buf = _buffers(env, T, case.C)
+    res = env.rollout_episodes(pc.policy_of(case, "cuda:0"), T, episode_slots=SLOTS, **buf)
+    torch.cuda.synchronize()
+    _check_against_reference(dict(_host(buf), stats=_stats(res), **_state(env)), ec.reference(name))
+
+
+@CASES
+def test_fused_equals_device_step_loop(name):
+    fused, _, loop = _runs(name)
+    for k in STEP + STATE:
+        assert fused[k].shape == loop[k].shape and _same(fused[k], loop[k]), k
+    assert fused["reset"].sum(0).min() >= 2 and fused["reset"][-1].any()
+
+
+@CASES
+def test_no_per_step_buffers(name):
+    fused, bare, _ = _runs(name)
+    for k in STATE:
+        assert _same(fused[k], bare[k]), k
+    for k in STATS[:5]:
+        assert _same(fused["stats"][k], bare["stats"][k]), k
+    assert set(bare["stats"]) == set(STATS[:5])
+
+
+@CASES
+def test_stats_equal_the_restatement(name):
+    fused, _, _ = _runs(name)
+    want = ec.accounting(fused["reward"], fused["reset"], SLOTS)
+    for k in STATS:
+        assert fused["stats"][k].dtype == want[k].dtype and _same(fused["stats"][k], want[k]), k
+
+
+@CASES
+def test_split_rollouts(name):
+    """n_steps = 1 equals one step(policy(observe())); two calls of 8 steps equal one of 16 in per-step outputs, final
+    state and episodes; the stats restart at every call."""
+    import torch
+    fused, _, _ = _runs(name)
+    case = ec.case_of(name)
+    pol = pc.policy_of(case, "cuda:0")
+    one = _env(name)
+    b1 = _buffers(one, 1, case.C)
+    r1 = one.rollout_episodes(pol, 1, episode_slots=SLOTS, **b1)
+    ref = _env(name)
+    l1 = _device_loop(ref, pol, 1)
+    torch.cuda.synchronize()
+    h1 = _host(b1)
+    for k in STEP:
+        assert _same(h1[k], l1[k]), k
+    s1, sr = _state(one), _state(ref)
+    for k in STATE:
+        assert _same(s1[k], sr[k]), k
+    want = ec.accounting(h1["reward"], h1["reset"], SLOTS)
+    for k in STATS:
+        assert _same(r1[k], want[k]), k
+    h = T // 2
+    two = _env(name)
+    ba, bb = _buffers(two, h, case.C), _buffers(two, T - h, case.C)
+    ra = _stats(two.rollout_episodes(pol, h, episode_slots=SLOTS, **ba))
+    rb = _stats(two.rollout_episodes(pol, T - h, episode_slots=SLOTS, **bb))
+    torch.cuda.synchronize()
+    ha, hb = _host(ba), _host(bb)
+    for k in STEP:
+        assert _same(np.concatenate([ha[k], hb[k]]), fused[k]), k
+    s2 = _state(two)
+    for k in STATE:
+        assert _same(s2[k], fused[k]), k
+    for got, hh in ((ra, ha), (rb, hb)):
+        want = ec.accounting(hh["reward"], hh["reset"], SLOTS)
+        for k in STATS:
+            assert _same(got[k], want[k]), k
+
+
+@pytest.mark.parametrize("name", ["canonical4-mlp-5sets", "balance-g1-lin-4sets-inf"])
+def test_nonfinite_walkers_are_reset(name):
+    """auto_reset = done | nonfinite: walkers that diverge after a finite snapshot are reset at their first step, and
+    the state is finite from then on; against _Composed(bits = 3) driven by the policy on its own rows."""
+    import torch
+    from oracle.oracle import Oracle
+    from test_gpu_autoreset import _Composed
+    from test_gpu_diverged import _diverge
+    from test_gpu_parity import _close
+    cfg, case = ec.config(name), ec.case_of(name)
+    good = dict(cfg["spec"])
+    good["pos"] = np.array(good["pos"], np.float32).reshape(-1, 3)
+    good["vel"] = np.array(good["vel"], np.float32).reshape(-1, 3)
+    bad = _diverge(good, np.random.default_rng(5), n_dead=40, n_partial=20, n_inf=10, pin=False)
+    env = _env(name, on=("done", "nonfinite"))             # the snapshot: the finite state
+    env.pos = bad["pos"]
+    env.vel = bad["vel"]
+    buf = _buffers(env, 4, case.C)
+    res = env.rollout_episodes(pc.policy_of(case, "cuda:0"), 4, episode_slots=SLOTS, **buf)
+    torch.cuda.synchronize()
+    got = _host(buf)
+    ref = _Composed(bad, cfg["params"], 3, cfg["pool"], snapshot=Oracle(good, cfg["params"]))
+    pol = pc.policy_of(case)
+    obs = ref.orc.observe()["obs"]
+    rewards, resets = [], []
+    for t in range(4):
+        with np.errstate(all="ignore"):
+            a = pol.forward_numpy(obs)
+        out = ref.step(a)
+        obs = out["obs"]
+        st = ref.state()
+        if t == 0:
+            assert out["reset"].sum() >= 70
+        for k in ("pos", "vel", "acc"):
+            assert np.isfinite(st[k]).all()
+        _close(got["action"][t], a)
+        _close(got["obs"][t], obs)
+        _close(got["reward"][t], out["reward"])
+        assert np.array_equal(got["done"][t], np.asarray(out["done"]).astype(np.uint8))
+        assert np.array_equal(got["reset"][t], out["reset"])
+        sel = out["reset"] != 0
+        _close(got["final_obs"][t][sel], ref.final_obs[sel])
+        rewards.append(out["reward"].copy()); resets.append(out["reset"].copy())
+    st = ref.state()
+    _close(env.pos.cpu().numpy(), st["pos"])
+    _close(env.vel.cpu().numpy(), st["vel"])
+    _close(env.acc.cpu().numpy(), st["acc"])
+    _close(env.muscle_x.cpu().numpy(), st["mx"])
+    assert np.array_equal(env.steps.cpu().numpy(), st["steps"])
+    assert np.array_equal(env.batch.episodes.cpu().numpy(), st["episodes"])
+    want = ec.accounting(np.stack(rewards), np.stack(resets), SLOTS)
+    for k in ("length_sum", "episodes", "tail_length", "ep_lengths"):
+        assert np.array_equal(res[k].cpu().numpy(), want[k]), k
+    for k in ("return_sum", "tail_return", "ep_returns"):
+        _close(res[k].cpu().numpy(), want[k])
+
+
+@pytest.mark.parametrize("name", ["canonical4-mlp-5sets", "balance16-mid-mlp-8sets"])
+def test_open_loop_resident_rollout_with_auto_reset(name):
+    """rollout(resident=True) with auto-reset (the resident kernel's AR twin; 4 and 16 walkers per wave) against the
+    composed oracle with given actions."""
+    import torch
+    from test_gpu_autoreset import _Composed
+    cfg, case = ec.config(name), ec.case_of(name)
+    env = _env(name)
+    assert env.resident_ok()
+    geo = env.launch_geometry()
+    assert geo["walkers_per_block"] * 64 // geo["threads"] == case.wpw, geo
+    N, A = cfg["N"], env.batch.A
+    acts = np.random.default_rng(21).uniform(-1, 1, (T, N, A)).astype(np.float32)
+    reset = torch.full((T, N), 255, dtype=torch.uint8, device=env.device)
+    obs, rew, done = env.rollout(torch.from_numpy(acts).to(env.device), resident=True, reset_out=reset)
+    torch.cuda.synchronize()
+    ref = _Composed(cfg["spec"], cfg["params"], 1, cfg["pool"])
+    outs = [ref.step(acts[t]) for t in range(T)]
+    assert _same(obs, np.stack([o["obs"] for o in outs]))
+    assert _same(rew, np.stack([o["reward"] for o in outs]))
+    assert np.array_equal(done.cpu().numpy(), np.stack([np.asarray(o["done"]).astype(np.uint8) for o in outs]))
+    resets = np.stack([o["reset"] for o in outs])
+    assert np.array_equal(reset.cpu().numpy(), resets)
+    assert resets.sum(0).min() >= 2 and resets[-1].any()
+    st, got = ref.state(), _state(env)
+    for k, r in (("pos", "pos"), ("vel", "vel"), ("acc", "acc"), ("muscle_x", "mx"), ("steps", "steps"),
+                 ("episodes", "episodes")):
+        assert _same(got[k], np.asarray(st[r]).reshape(got[k].shape).astype(got[k].dtype)), k
+    assert np.array_equal(got["contact"].astype(np.uint8).ravel(), np.asarray(st["contact"]).astype(np.uint8).ravel())
+
+
+def test_refusals_leave_the_env_usable():
+    import torch
+    from walker_gym_amd.batched_env import BatchedPhysicsEnv
+    from walker_gym_amd.policy import MLPPolicy
+    from walker_gym_amd.synthetic import canonical_walkers, ragged_walkers
+    z = lambda *s: torch.zeros(s, device="cuda:0")
+    rg = BatchedPhysicsEnv(ragged_walkers(200, seed=2), device="cuda:0", in3d=1)
+    with pytest.raises(ValueError, match="policy_loop"):              # a ragged batch
+        rg.rollout_episodes(MLPPolicy(z(rg.obs_dim, 2)), 2)
+    env = BatchedPhysicsEnv(canonical_walkers(256, seed=2), device="cuda:0", in3d=1, max_steps=3)
+    good = MLPPolicy(z(152, 8))
+    with pytest.raises(ValueError, match="rollout_policy"):
+        env.rollout_episodes(good, 2)                                 # auto-reset off
+    env.enable_auto_reset()
+    with pytest.raises(ValueError):
+        env.rollout_episodes(MLPPolicy(z(151, 8)), 2)                 # D
+    with pytest.raises(ValueError):
+        env.rollout_episodes(MLPPolicy(z(152, 9)), 2)                 # C > A
+    with pytest.raises(ValueError):
+        env.rollout_episodes(MLPPolicy(z(3, 152, 8)), 2)              # N % G
+    with pytest.raises(ValueError):
+        env.rollout_episodes(good, 0)                                 # n_steps
+    with pytest.raises(ValueError):
+        env.rollout_episodes(good, 2, episode_slots=-1)
+    with pytest.raises(ValueError):
+        env.rollout_episodes(MLPPolicy(torch.zeros(152, 8)), 2)       # host weights
+    with pytest.raises(ValueError):
+        env.rollout_episodes(good, 2, reward_out=z(3, 256))           # buffer shapes and dtypes
+    with pytest.raises(ValueError):
+        env.rollout_episodes(good, 2, reset_out=z(2, 256))            # (float32, not uint8)
+    with pytest.raises(ValueError):
+        env.rollout_episodes(good, 2, final_obs_out=z(2, 256, 151))
+    with pytest.raises(ValueError):
+        env.rollout_episodes(lambda rows, t: rows[:, :8], 2)          # not an MLPPolicy
+    with pytest.raises(ValueError, match="auto-reset"):
+        env.rollout_policy(good, 2)                                   # (rollout_policy keeps refusing)
+    env.step(z(256, 8))
+    assert "total_energy" in env.info()                               # a refused call marks nothing stale
+    ref = BatchedPhysicsEnv(canonical_walkers(256, seed=2), device="cuda:0", in3d=1, max_steps=3)
+    ref.enable_auto_reset()
+    ref.step(z(256, 8))
+    r = env.rollout_episodes(good, 4)
+    for t in range(4):
+        ref.step(z(256, 8))
+    torch.cuda.synchronize()
+    assert (r["episodes"] == 1).all() and (r["length_sum"] == 2).all() and (r["tail_length"] == 2).all()
+    a, b = _state(env), _state(ref)
+    for k in STATE:
+        assert _same(a[k], b[k]), k
+    assert "total_energy" not in env.info() and _same(env.info()["episodes"], ref.info()["episodes"])
+    obs = env.step(z(256, 8))[0]
+    assert _same(obs, ref.step(z(256, 8))[0]) and "total_energy" in env.info()
+
+
+def test_no_collateral_change():
+    """rollout_policy (auto-reset off) and policy_loop(graph=True) (auto-reset on) still give the bits of step() loops."""
+    import torch
+    from walker_gym_amd.batched_env import BatchedPhysicsEnv
+    name = "canonical4-mlp-5sets"
+    cfg, case = ec.config(name), ec.case_of(name)
+    pol = pc.policy_of(case, "cuda:0")
+    N = cfg["N"]
+    ref = BatchedPhysicsEnv(cfg["spec"], device="cuda:0", **cfg["params"])
+    env = BatchedPhysicsEnv(cfg["spec"], device="cuda:0", **cfg["params"])
+    env.rollout_policy(pol, 6)
+    ref.observe()
+    for t in range(6):
+        ref.step(pol.for_rows(0, N)(ref.obs, t))
+    torch.cuda.synchronize()
+    for k in STATE[:-1]:
+        assert _same(getattr(env, k), getattr(ref, k)), k
+    ref, env = _env(name), _env(name)
+    ref.observe(); env.observe()
+    for t in range(6):
+        ref.step(pol.for_rows(0, N)(ref.obs, t))
+    env.policy_loop(pol, 6, lanes=1, graph=True)
+    torch.cuda.synchronize()
+    a, b = _state(env), _state(ref)
+    for k in STATE:
+        assert _same(a[k], b[k]), k
+    for k in ("obs", "reward", "done", "reset_out", "final_obs"):
+        assert _same(getattr(env, k), getattr(ref, k)), k
+    assert int(b["episodes"].min()) >= 1

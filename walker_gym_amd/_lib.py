@@ -73,10 +73,16 @@ class WgPolicy(C.Structure):
                 ("action_out", _vp), ("action_out_step", C.c_int64), ("return_out", _vp), ("length_out", _vp)]
 
 
+class WgEpisodeStats(C.Structure):
+    """wg_episode_stats: the per-episode accounting of wg_rollout_episodes (every pointer optional)."""
+    _fields_ = [("return_sum", _vp), ("length_sum", _vp), ("episodes_done", _vp), ("tail_return", _vp),
+                ("tail_length", _vp), ("ep_return", _vp), ("ep_length", _vp), ("ep_slots", C.c_int32)]
+
+
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
            "wg_step_simple", "wg_observe_simple", "wg_reset", "wg_reset_noise", "wg_plan_ragged", "wg_plan_waves",
            "wg_wave_edge_passes", "wg_plan_errors", "wg_launch_geometry", "wg_launch_floor", "wg_time_step",
-           "wg_rollout_policy")
+           "wg_rollout_policy", "wg_rollout_episodes")
 
 _lib = None
 _lock = threading.Lock()
@@ -105,6 +111,8 @@ def load(path: str | None = None):
         L.wg_rollout.argtypes = L.wg_step.argtypes
         L.wg_rollout_policy.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), C.POINTER(WgPolicy),
                                         C.POINTER(WgOutputs), C.c_int32, _vp]
+        L.wg_rollout_episodes.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), C.POINTER(WgPolicy),
+                                          C.POINTER(WgOutputs), C.POINTER(WgEpisodeStats), C.c_int32, _vp]
         L.wg_step_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,
                                      C.POINTER(_vp)]
         L.wg_run_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,

@@ -269,8 +269,8 @@ class BatchedPhysicsEnv:
 
         The noise comes from a pool of `noise_rows` draws of randn * sigma over [P, 3] from the env's generator (none
         when sigma == 0); a walker's episode e uses row e % noise_rows, and refresh_reset_noise() redraws the pool.
-        noise [rows, P, 3]: a pool of the caller's instead.  Works with step, run, rollout (per-step launches),
-        policy_loop and graph; prepared runs and graphs made before the call refuse to run.  Only batches the
+        noise [rows, P, 3]: a pool of the caller's instead.  Works with step, run, rollout (resident included),
+        rollout_episodes, policy_loop and graph; prepared runs and graphs made before the call refuse to run.  Only batches the
         barrier-free lean kernel takes (uniform, M dividing 64, spring_mode 0, pair_mode 0): ValueError otherwise."""
         names = (on,) if isinstance(on, str) else tuple(on)
         if not names or any(n not in self._AR_BITS for n in names):
@@ -491,8 +491,9 @@ class BatchedPhysicsEnv:
                 resident: bool = True, reset_out=None):
         """T steps in one C call, no host sync; outputs for every step.  resident (default): wg_rollout, one launch
         for all T steps where the batch allows it (uniform M | 64, no pair forces), each walker's state kept in
-        registers between steps; False: wg_step, one launch per step.  Bit-identical either way.  With auto-reset the
-        steps run as per-step launches either way; reset_out [T, N] uint8 (optional) receives every step's resets."""
+        registers between steps; False: wg_step, one launch per step.  Bit-identical either way.  It is resident with
+        auto-reset too (the reset tail runs inside the launch); reset_out [T, N] uint8 (optional) receives every
+        step's resets."""
         if not isinstance(actions, torch.Tensor):
             actions = torch.as_tensor(np.asarray(actions, dtype=np.float32))
         actions = actions.to(self.device, torch.float32).contiguous()
@@ -596,6 +597,83 @@ class BatchedPhysicsEnv:
         self._steps_at = -1   # (as rollout(): the env's one-step outputs are not this call's; a refused call ran nothing)
         self._stale = frozenset({"centroid_position", "total_energy", "momentum", "nonfinite", "reset", "final_obs"})
         return {"returns": returns, "lengths": lengths}
+
+    def rollout_episodes(self, policy, n_steps: int, obs_out=None, reward_out=None, done_out=None, action_out=None,
+                         reset_out=None, final_obs_out=None, episode_slots: int = 0) -> dict:
+        """n_steps closed-loop steps with episode roll-over in ONE launch (wg_rollout_episodes): rollout_policy's
+        resident kernel with auto-reset (enable_auto_reset first) inside its loop.  A walker whose step ends its episode
+        starts the next one in the same launch, and its next action comes from the fresh observation row.  Bit-identical
+        to `for t: env.step(policy(env.obs, t))` with auto-reset on, per-step outputs, final state and info()['episodes']
+        included.  The per-step buffers are optional and written only when given: obs_out [T, N, D] f32, reward_out
+        [T, N] f32, done_out [T, N] u8, action_out [T, N, C] f32, reset_out [T, N] u8 (the walkers reset at each step),
+        final_obs_out [T, N, D] f32 (the terminal rows of the walkers reset at each step; other rows untouched).
+
+        Returns, per walker and for this call alone: 'return_sum' f32 and 'length_sum' i32 over the episodes finished in
+        the call, 'episodes' i32 their number, 'tail_return' f32 / 'tail_length' i32 the unfinished episode at the end
+        (returns add the rewards in step order in float32).  With episode_slots > 0 also 'ep_returns' [N, slots] f32
+        (NaN where unfilled) and 'ep_lengths' [N, slots] i32 (-1 where unfilled): the call's first `slots` finished
+        episodes of each walker.
+
+        ValueError (nothing launched) with auto-reset off (use rollout_policy), and for everything rollout_policy
+        refuses on its own account: the batch, the policy's fit, the buffers, the LDS budget."""
+        from .policy import MLPPolicy
+        alt = "use policy_loop(policy, n_steps), which closes the loop with one step launch per step on any batch"
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError(f"rollout_episodes needs an MLPPolicy; for another callable {alt}")
+        T, slots = int(n_steps), int(episode_slots)
+        if T < 1:
+            raise ValueError(f"rollout_episodes: n_steps {n_steps} < 1")
+        if slots < 0:
+            raise ValueError(f"rollout_episodes: episode_slots {episode_slots} < 0")
+        if not self.resident_ok():
+            raise ValueError("rollout_episodes: only batches of the resident lean kernel (uniform, M dividing 64 with "
+                             f"M >= 4, spring_mode 0, pair_mode 0, WG_LEAN not 0); {alt}")
+        if not self._ar_mode:
+            raise ValueError("rollout_episodes: auto-reset is off (enable_auto_reset first); without episode roll-over "
+                             "use rollout_policy")
+        if policy.D != self.obs_dim:
+            raise ValueError(f"rollout_episodes: the policy takes {policy.D} inputs, the observation rows have "
+                             f"{self.obs_dim}")
+        if policy.C > self.batch.A:
+            raise ValueError(f"rollout_episodes: the policy has {policy.C} outputs, the walkers {self.batch.A} muscles")
+        if self.N % policy.G != 0:
+            raise ValueError(f"rollout_episodes: {policy.G} parameter sets do not divide N = {self.N}; {alt}")
+        dv, N, D = self.device, self.N, self.obs_dim
+        for name in ("w1", "b1", "w2", "b2"):
+            t = getattr(policy, name)
+            if t is not None:
+                require_tensor(t, f"policy.{name}", dv, torch.float32)
+        for name, t, dt, shape in (("obs_out", obs_out, torch.float32, (T, N, D)),
+                                   ("reward_out", reward_out, torch.float32, (T, N)),
+                                   ("done_out", done_out, torch.uint8, (T, N)),
+                                   ("action_out", action_out, torch.float32, (T, N, policy.C)),
+                                   ("reset_out", reset_out, torch.uint8, (T, N)),
+                                   ("final_obs_out", final_obs_out, torch.float32, (T, N, D))):
+            if t is not None:
+                require_tensor(t, name, dv, dt, shape)
+        res = {"return_sum": torch.empty(N, dtype=torch.float32, device=dv),
+               "length_sum": torch.empty(N, dtype=torch.int32, device=dv),
+               "episodes": torch.empty(N, dtype=torch.int32, device=dv),
+               "tail_return": torch.empty(N, dtype=torch.float32, device=dv),
+               "tail_length": torch.empty(N, dtype=torch.int32, device=dv)}
+        if slots > 0:
+            res["ep_returns"] = torch.full((N, slots), float("nan"), dtype=torch.float32, device=dv)
+            res["ep_lengths"] = torch.full((N, slots), -1, dtype=torch.int32, device=dv)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        pol = _lib.WgPolicy(n_sets=policy.G, obs_dim=policy.D, hidden=policy.H, act_dim=policy.C, w1=p(policy.w1),
+                            b1=p(policy.b1), w2=p(policy.w2), b2=p(policy.b2), act_limit=policy.act_limit,
+                            action_out=p(action_out), action_out_step=N * policy.C, return_out=None, length_out=None)
+        st = _lib.WgEpisodeStats(return_sum=p(res["return_sum"]), length_sum=p(res["length_sum"]),
+                                 episodes_done=p(res["episodes"]), tail_return=p(res["tail_return"]),
+                                 tail_length=p(res["tail_length"]), ep_return=p(res.get("ep_returns")),
+                                 ep_length=p(res.get("ep_lengths")), ep_slots=slots)
+        o = self._outputs(obs_out, reward_out, done_out, None, None, obs_step=N * D, out_step=N, pad_clean=True,
+                          reset=reset_out, final_obs=final_obs_out)
+        _lib.check(_lib.load().wg_rollout_episodes(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
+                                                   C.byref(o), C.byref(st), T, self._stream()), "wg_rollout_episodes")
+        self._steps_at = -1   # (as rollout_policy(): only after the call was accepted)
+        self._stale = frozenset({"centroid_position", "total_energy", "momentum", "nonfinite", "reset", "final_obs"})
+        return res
 
     def run(self, actions, n_steps: int, info: bool = True, lanes: Optional[int] = None, resident: bool = False,
             record: Optional[dict] = None, _only: Optional[int] = None):

@@ -2305,17 +2305,20 @@ __device__ __forceinline__ void lean_obs_rows(float *obs, int stride, const KPar
 // One wave's tile after its loads: the edge lanes leave the spring term t and the damping force df of every
 // edge in LDS, then each mass lane walks its incidence list, dividing by m as the reference does (mass_step).
 // RES (walker_rollout_lean): the tile's state stays in L across steps; it is written to HBM only when `last`.
-// AR (auto-reset, ABI 16; never with RES): after the outputs, the walkers whose episode this step ended are put back to
-// the snapshot (b.init_*) with their reset noise and their fresh observation rows, in a rare wave-uniform branch.
+// AR (auto-reset, ABI 16): after the outputs, the walkers whose episode this step ended are put back to the snapshot
+// (b.init_*) with their reset noise and their fresh observation rows, in a rare wave-uniform branch.  With RES the fresh
+// state becomes the carried state; the walker's episode count lives in LDS (epw[wl * epw_stride], its lane q == 0 reads
+// and writes it) and reaches b.episodes whenever it moves, muscle_x is stored when the tail fires (a muscle that does not
+// act has no other store), and pos / vel / acc / steps, which the last step's stores precede, only when `last`.
 // POL (walker_rollout_policy; with RES): what the policy's next observation row and the episode return need beside the
 // state carried in L leaves in `po` (acc, the position sums; reward and done in the walker's lane q == 0), and reward /
 // done are computed whether or not they are stored.  Dead code in every other instance.
-struct LeanPolOut { float ax, ay, az, sx, sy, sz, reward; int done; };
+struct LeanPolOut { float ax, ay, az, sx, sy, sz, reward; int done; int reset; };   // reset (AR): wg_outputs.reset's flag
 template <bool IN3D, int NE, bool RES = false, bool E8 = false, bool AR = false, bool POL = false>
 __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &kp, const KOut &o,
                                              const LeanGeo &lg, char *sl, const LeanTile &t, int lane,
                                              LeanIn<NE, E8> &L, bool last = true, const KReset &ar = KReset{},
-                                             LeanPolOut *po = nullptr) {
+                                             LeanPolOut *po = nullptr, uint32_t *epw = nullptr, int epw_stride = 1) {
     const bool store = !RES || last;
     const int M = b.M, K = b.K, A = b.A;
     const int w0 = t.w0, nE = t.nE;
@@ -2561,7 +2564,8 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
         lean_obs_rows<IN3D>(o.obs, o.obs_stride, kp, M, A, w0, wl, q, mu_wl, mu_ua, is_mass, is_mus, px, py, pz, vx, vy,
                             vz, ax, ay, az, sx, sy, sz, midx, midy, midz, x);
     // ================= auto-reset (ABI 16): the walkers whose episode this step ended start their next one here
-    if constexpr (AR && !RES) {
+    float rsx = sx, rsy = sy, rsz = sz;   // (POL) the position sums the next row is built from
+    if constexpr (AR) {
         // walker-level events as lane bits: the step's done (lane q == 0 holds it), a non-finite component of the state
         // the step leaves (wg_outputs.nonfinite's test, on the registers; the diverged walkers' NaN included)
         const bool nonf = is_mass && !(__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz) &&
@@ -2571,6 +2575,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
         const unsigned long long hot = ((ar.mode & 1) ? eb : 0ull) | ((ar.mode & 2) ? nb : 0ull);
         const bool selw = is_mass && (hot & gmask) != 0ull;             // this mass lane's walker is reset
         if (ar.reset && is_mass && q == 0) at_u32w(ar.reset, (uint32_t)(w0 + wl)) = (uint8_t)selw;
+        if constexpr (POL) po->reset = selw;
         if (__builtin_expect(hot != 0ull, 0)) {   // wave-uniform, rare: every lane enters (walker_sums, the gathers)
             const unsigned long long mmask = (M == 64) ? ~0ull : (((1ull << M) - 1ull) << ((mu_wl << lg.lgM) & 63));
             const bool selm = is_mus && (hot & mmask) != 0ull;          // this muscle lane's walker is reset
@@ -2580,7 +2585,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
             // the walker's episode count from its lane q == 0, which also writes it back (no lane reads what another
             // lane of the wave stores)
             int ep = 0;
-            if (selw && q == 0) ep = at_u32(b.episodes, 4u * (uint32_t)(w0 + wl));
+            if (selw && q == 0) ep = RES ? (int)epw[wl * epw_stride] : at_u32(b.episodes, 4u * (uint32_t)(w0 + wl));
             ep = __builtin_amdgcn_ds_bpermute(gbase << 2, ep);
             float fx = px, fy = py, fz = pz, fvx = vx, fvy = vy, fvz = vz, fax = ax, fay = ay, faz = az, fxm = x;
             if (selw) {
@@ -2597,14 +2602,20 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
                     fvx = fvx + nz[0]; fvy = fvy + nz[1];
                     if (IN3D) fvz = fvz + nz[2];
                 }
-                float *gpo = WG_ST(b.pos, pl, 3), *gvo = WG_ST(b.vel, pl, 3), *gao = WG_ST(b.acc, pl, 3);
-                gpo[0] = fx; gpo[1] = fy; gpo[2] = fz;
-                gvo[0] = fvx; gvo[1] = fvy; gvo[2] = fvz;
-                gao[0] = fax; gao[1] = fay; gao[2] = faz;
+                if (store) {
+                    float *gpo = WG_ST(b.pos, pl, 3), *gvo = WG_ST(b.vel, pl, 3), *gao = WG_ST(b.acc, pl, 3);
+                    gpo[0] = fx; gpo[1] = fy; gpo[2] = fz;
+                    gvo[0] = fvx; gvo[1] = fvy; gvo[2] = fvz;
+                    gao[0] = fax; gao[1] = fay; gao[2] = faz;
+                }
                 if (q == 0) {
                     const uint32_t wg = (uint32_t)(w0 + wl);
-                    *WG_ST(b.steps, wg, 1) = 0;
+                    if (store) *WG_ST(b.steps, wg, 1) = 0;
                     *WG_ST(b.episodes, wg, 1) = ep + 1;
+                    if constexpr (RES) {
+                        epw[wl * epw_stride] = (uint32_t)(ep + 1);
+                        L.wsteps = 0;
+                    }
                 }
             }
             if (selm) {
@@ -2617,6 +2628,14 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
                                     fvy, fvz, fax, fay, faz, fs.sx, fs.sy, fs.sz, fs.sx * lg.invM, fs.sy * lg.invM,
                                     fs.sz * lg.invM, fxm);
             }
+            if constexpr (RES) {   // the fresh state is the state the next step starts from
+                px = fx; py = fy; pz = fz; vx = fvx; vy = fvy; vz = fvz; x = fxm;
+                if constexpr (POL) {   // ... and what the policy's next row is built from (every lane: walker_sums)
+                    const WalkerSums fs = walker_sums(fx, fy, fz, 0.f, 0.f, 0.f, gbase, M, lane);
+                    ax = fax; ay = fay; az = faz;
+                    if (selw) { rsx = fs.sx; rsy = fs.sy; rsz = fs.sz; }
+                }
+            }
         }
     }
     if (RES) {   // the next step starts from this one's state (Point.pos/v, Muscle.x), in registers
@@ -2626,7 +2645,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     }
     if constexpr (POL) {
         po->ax = ax; po->ay = ay; po->az = az;
-        po->sx = sx; po->sy = sy; po->sz = sz;
+        po->sx = rsx; po->sy = rsy; po->sz = rsz;
         po->done = ep_done;
     }
     STAMP(6);
@@ -2717,12 +2736,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
 // step; each step reads its actions (the next step's are in flight while this one computes) and writes its
 // outputs; pos / vel / acc / contact / muscle x / steps go to HBM after the last step.  Same arithmetic as
 // walker_step_lean, step for step (bit-identical to n_steps single-step launches).
-template <bool IN3D, int NE, bool E8>
+// AR: the auto-reset tail (ABI 16) in the resident loop: a reset walker's fresh state becomes the carried state, and its
+// episode count is kept in one LDS word per walker behind the wave's lean slice (KResetRes.off_ep).
+struct KResetRes {
+    KReset r;           // reset / final_obs of step 0 (strided like KOut's reward / obs), the mode
+    int off_ep;         // byte offset of the walkers' episode counts in the wave's LDS slice
+};
+// the per-step view of the auto-reset outputs
+__device__ __forceinline__ KReset kreset_at(const KReset &r, const KOut &o, int s) {
+    KReset as = r;
+    if (as.reset) as.reset += (size_t)s * o.out_step;
+    if (as.final_obs) as.final_obs += (size_t)s * o.obs_step;
+    return as;
+}
+template <bool IN3D, int NE, bool E8, bool AR = false>
 // (register budget: 5 waves per SIMD since the scalar wave index, 16 B of scratch at NE 3-4: 35.49 against 36.07 us per
 // step at 4, profiles/r04l_ab_resident.json)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4 : 5))) void walker_rollout_lean(
     wg_batch b, KParams kp, const float *__restrict__ action, int action_cols, int action_stride, int64_t action_step,
-    KOut o, int n_steps, LeanGeo lg) {
+    KOut o, int n_steps, LeanGeo lg, typename std::conditional<AR, KResetRes, KNoReset>::type ar) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tile = blockIdx.x * lg.wpb + wv;
@@ -2740,6 +2772,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
 #pragma unroll
         for (int it = 0; it < NE; it++)
             if (lane + 64 * it < t.nE) s_inc[lane + 64 * it] = L.gi[it];
+    }
+    if constexpr (AR) {   // the walkers' episode counts, each in its lane q == 0's LDS word
+        if (t.is_mass && t.q == 0)
+            reinterpret_cast<uint32_t *>(smem + wv * lg.slice + ar.off_ep)[t.wl] =
+                (uint32_t)at_u32(b.episodes, 4u * (uint32_t)(t.w0 + t.wl));
     }
 #pragma clang loop unroll(disable)
     for (int s = 0; s < n_steps; s++) {
@@ -2766,7 +2803,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
             if constexpr (E8) asm volatile("" : "+v"(L.er[it].w), "+v"(L.er[it].rest));
             else asm volatile("" : "+v"(L.er[it].ij), "+v"(L.er[it].rest), "+v"(L.er[it].k), "+v"(L.er[it].c));
         }
-        lean_compute<IN3D, NE, true, E8>(b, kp, os, lg, smem + wv * lg.slice, ts, ln, L, s == n_steps - 1);
+        if constexpr (AR)
+            lean_compute<IN3D, NE, true, E8, true>(b, kp, os, lg, smem + wv * lg.slice, ts, ln, L, s == n_steps - 1,
+                                                   kreset_at(ar.r, o, s), nullptr,
+                                                   reinterpret_cast<uint32_t *>(smem + wv * lg.slice + ar.off_ep), 1);
+        else
+            lean_compute<IN3D, NE, true, E8>(b, kp, os, lg, smem + wv * lg.slice, ts, ln, L, s == n_steps - 1);
         L.a = a_next;
         wave_sync();   // this step's LDS reads stay ahead of the next step's writes
     }
@@ -2845,8 +2887,8 @@ __device__ __forceinline__ void policy_unit2(const float *x, const float *__rest
 // observation row into the wave's LDS slice (lean_obs_rows itself, with the slice as the destination: the rows the
 // policy reads are the rows the step stores, by construction), then the walker's M lanes share the units of each layer,
 // lane q taking units q, q + M, ...; the hidden vector and the actions go through LDS.  Returns the muscle lane's action
-// (0 where the lane does not act).  act_dst: this step's action_out rows, or NULL.
-template <bool IN3D>
+// (0 where the lane does not act).  act_dst: this step's action_out rows, or NULL.  WS: the LDS words of a walker's record.
+template <bool IN3D, int WS = 4>
 __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &kp, const KPolicy &pol, const LeanGeo &lg,
                                              char *smem, char *sl, const LeanTile &t, const float *p3, const float *v3,
                                              const LeanPolOut &ps, float x, float *act_dst) {
@@ -2859,7 +2901,7 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
                         ps.sz * lg.invM, x);
     wave_sync();
     // the walker's parameter set, from its LDS record (a register carried across the step would spill)
-    const uint32_t gset = t.is_mass ? reinterpret_cast<const uint32_t *>(sl + pol.off_w)[4 * t.wl + 3] : 0u;
+    const uint32_t gset = t.is_mass ? reinterpret_cast<const uint32_t *>(sl + pol.off_w)[WS * t.wl + 3] : 0u;
     const float *xin = row + t.wl * D;   // (read by the tile's mass lanes only: t.wl < t.nw)
     int n = D;
     if (H > 0) {   // wave-uniform
@@ -2907,11 +2949,19 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
 // of read from an action array.  The per-step outputs are optional; each walker's return (rewards added in step order
 // up to and including its first done step) and the steps counted are carried in its lane q == 0 and stored after the
 // last step.  The step itself is walker_rollout_lean's, op for op.
-template <bool IN3D, int NE, bool E8>
+// AR (wg_rollout_episodes): the auto-reset tail in the loop, as walker_rollout_lean's AR twin; a reset walker's next row
+// is the fresh state's, since the rows are built from the carried state.  The walker's record grows to eight words:
+// the running episode's return and length, the episodes finished in this call, the parameter set, the finished
+// episodes' return and length sums, the walker's episode count (wg_batch.episodes), one spare.  Lane q == 0 keeps the
+// accounting of wg_episode_stats, stores an ep_return / ep_length slot when an episode ends, the sums after the last step.
+template <bool IN3D, int NE, bool E8, bool AR = false>
 // (register budget: one wave per SIMD fewer than walker_rollout_lean.  The LDS slice with the rows already holds the
 // canonical walker to 4 waves per SIMD, the NE 8 shapes to 2, and the latency-bound NE 1 batches run one)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3 : 4))) void walker_rollout_policy(
-    wg_batch b, KParams kp, KPolicy pol, KOut o, int n_steps, LeanGeo lg) {
+    wg_batch b, KParams kp, KPolicy pol, KOut o, int n_steps, LeanGeo lg,
+    typename std::conditional<AR, KReset, KNoReset>::type ar,
+    typename std::conditional<AR, wg_episode_stats, KNoReset>::type st) {
+    constexpr int WS = AR ? 8 : 4;   // LDS words per walker
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tile = blockIdx.x * lg.wpb + wv;
@@ -2959,9 +3009,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
     // walker still counts (no done yet), and its parameter set (stored walker w uses set w / (N / n_sets); a set
     // boundary may fall inside the tile).  Written and updated by the walker's lane q == 0.
     if (t.is_mass && t.q == 0) {
-        uint32_t *wk = reinterpret_cast<uint32_t *>(sl + pol.off_w) + 4 * t.wl;
-        wk[0] = __float_as_uint(0.f); wk[1] = 0u; wk[2] = 1u;
+        uint32_t *wk = reinterpret_cast<uint32_t *>(sl + pol.off_w) + WS * t.wl;
+        wk[0] = __float_as_uint(0.f); wk[1] = 0u; wk[2] = AR ? 0u : 1u;
         wk[3] = (uint32_t)(t.w0 + t.wl) / (uint32_t)pol.wps;
+        if constexpr (AR) {
+            wk[4] = __float_as_uint(0.f); wk[5] = 0u;
+            wk[6] = (uint32_t)at_u32(b.episodes, 4u * (uint32_t)(t.w0 + t.wl));
+        }
     }
 #pragma clang loop unroll(disable)
     for (int s = 0; s < n_steps; s++) {
@@ -2970,8 +3024,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
         asm volatile("" : "+v"(ln));
         LeanTile ts = lean_tile_of(b, nullptr, pol.C, lg, tile, ln);
         ts.acts = ts.is_mus && ts.mu_ua < pol.C;
-        L.a = lean_policy<IN3D>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x,
-                                pol.action_out ? pol.action_out + (size_t)s * (size_t)pol.action_out_step : nullptr);
+        L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x,
+                                    pol.action_out ? pol.action_out + (size_t)s * (size_t)pol.action_out_step : nullptr);
         KOut os = o;
         if (os.obs) os.obs += (size_t)s * os.obs_step;
         if (os.reward) os.reward += (size_t)s * os.out_step;
@@ -2985,10 +3039,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
             if constexpr (E8) asm volatile("" : "+v"(L.er[it].w), "+v"(L.er[it].rest));
             else asm volatile("" : "+v"(L.er[it].ij), "+v"(L.er[it].rest), "+v"(L.er[it].k), "+v"(L.er[it].c));
         }
-        lean_compute<IN3D, NE, true, E8, false, true>(b, kp, os, lg, sl, ts, ln, L, s == n_steps - 1, KReset{}, &ps);
+        if constexpr (AR)
+            lean_compute<IN3D, NE, true, E8, true, true>(b, kp, os, lg, sl, ts, ln, L, s == n_steps - 1,
+                                                         kreset_at(ar, o, s), &ps,
+                                                         reinterpret_cast<uint32_t *>(sl + pol.off_w) + 6, WS);
+        else
+            lean_compute<IN3D, NE, true, E8, false, true>(b, kp, os, lg, sl, ts, ln, L, s == n_steps - 1, KReset{}, &ps);
         if (ts.is_mass && ts.q == 0) {   // (the lane that holds the walker's reward and done)
-            uint32_t *wk = reinterpret_cast<uint32_t *>(sl + pol.off_w) + 4 * ts.wl;
-            if (wk[2]) {
+            uint32_t *wk = reinterpret_cast<uint32_t *>(sl + pol.off_w) + WS * ts.wl;
+            if constexpr (AR) {   // wg_episode_stats' accounting; ps.reset is wg_outputs.reset's flag of this step
+                float cur = __uint_as_float(wk[0]) + ps.reward;
+                uint32_t len = wk[1] + 1u;
+                if (ps.reset) {
+                    const uint32_t n = wk[2];
+                    if (n < (uint32_t)st.ep_slots) {
+                        const size_t slot = (size_t)(uint32_t)(ts.w0 + ts.wl) * (size_t)st.ep_slots + n;
+                        if (st.ep_return) st.ep_return[slot] = cur;
+                        if (st.ep_length) st.ep_length[slot] = (int32_t)len;
+                    }
+                    wk[4] = __float_as_uint(__uint_as_float(wk[4]) + cur);
+                    wk[5] = wk[5] + len;
+                    wk[2] = n + 1u;
+                    cur = 0.f; len = 0u;
+                }
+                wk[0] = __float_as_uint(cur); wk[1] = len;
+            } else if (wk[2]) {
                 wk[0] = __float_as_uint(__uint_as_float(wk[0]) + ps.reward);
                 wk[1] = wk[1] + 1u;
                 wk[2] = ps.done == 0;
@@ -2997,10 +3072,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
         wave_sync();   // this step's LDS reads stay ahead of the next step's writes
     }
     if (t.is_mass && t.q == 0) {
-        const uint32_t *wk = reinterpret_cast<const uint32_t *>(sl + pol.off_w) + 4 * t.wl;
+        const uint32_t *wk = reinterpret_cast<const uint32_t *>(sl + pol.off_w) + WS * t.wl;
         const uint32_t wg = (uint32_t)(t.w0 + t.wl);
-        if (pol.return_out) pol.return_out[wg] = __uint_as_float(wk[0]);
-        if (pol.length_out) pol.length_out[wg] = (int32_t)wk[1];
+        if constexpr (AR) {
+            if (st.return_sum) st.return_sum[wg] = __uint_as_float(wk[4]);
+            if (st.length_sum) st.length_sum[wg] = (int32_t)wk[5];
+            if (st.episodes_done) st.episodes_done[wg] = (int32_t)wk[2];
+            if (st.tail_return) st.tail_return[wg] = __uint_as_float(wk[0]);
+            if (st.tail_length) st.tail_length[wg] = (int32_t)wk[1];
+        } else {
+            if (pol.return_out) pol.return_out[wg] = __uint_as_float(wk[0]);
+            if (pol.length_out) pol.length_out[wg] = (int32_t)wk[1];
+        }
     }
 }
 
@@ -3679,15 +3762,26 @@ int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const float *a,
     return 0;
 }
 
+// ar_mode != 0: the AR twin, one LDS word per walker (its episode count) behind each wave's slice
 int launch_lean_rollout(const wg_batch *b, const KParams &kp, bool in3d, const float *a, int cols, int astride,
-                        int64_t astep, const wg_outputs &o, int n_steps, const LeanGeo &g, hipStream_t st) {
+                        int64_t astep, const wg_outputs &o, int n_steps, const LeanGeo &g0, hipStream_t st,
+                        int ar_mode = 0) {
+    LeanGeo g = g0;
+    KResetRes ar{kreset(o, ar_mode), g.slice};
+    if (ar_mode) g.slice += align16(g.wpw * 4);
     const int blocks = lean_blocks(b, g);
     const int ne = (g.wpw * b->K + 63) / 64;
     const int lds = g.wpb * g.slice;
     const bool e8 = use_edge8(b, g);
 #define WG_LAUNCH_RO(D3, NE_, E8_)                                                                               \
-    hipLaunchKernelGGL((walker_rollout_lean<D3, NE_, E8_>), dim3(blocks), dim3(64 * g.wpb), lds, st, *b, kp, a,  \
-                       cols, astride, astep, kout(o), n_steps, g)
+    do {                                                                                                         \
+        if (ar_mode)                                                                                             \
+            hipLaunchKernelGGL((walker_rollout_lean<D3, NE_, E8_, true>), dim3(blocks), dim3(64 * g.wpb), lds,   \
+                               st, *b, kp, a, cols, astride, astep, kout(o), n_steps, g, ar);                    \
+        else                                                                                                     \
+            hipLaunchKernelGGL((walker_rollout_lean<D3, NE_, E8_>), dim3(blocks), dim3(64 * g.wpb), lds, st, *b, \
+                               kp, a, cols, astride, astep, kout(o), n_steps, g, KNoReset{});                    \
+    } while (0)
 #define WG_RO_NE(D3, E8_)                                                                                        \
     do {                                                                                                         \
         if (ne <= 1) WG_LAUNCH_RO(D3, 1, E8_);                                                                   \
@@ -3712,40 +3806,67 @@ int obs_row_len(const wg_batch *b, const wg_params *p) {
 
 // wg_rollout_policy: every argument checked, then one walker_rollout_policy launch.  The wave's LDS slice is the lean
 // kernel's plus the walkers' observation rows, hidden vectors and actions.
+// episodes (wg_rollout_episodes): the AR instances, with auto-reset's own checks in place of the auto_reset refusal, the
+// accounting of `st`, and eight words per walker in the slice instead of four.
 int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o, int32_t n_steps,
-                   hipStream_t stream) {
+                   hipStream_t stream, bool episodes = false, const wg_episode_stats *st = nullptr) {
+    const char *fn = episodes ? "wg_rollout_episodes" : "wg_rollout_policy";
     int rc = validate(b);
     if (rc) return rc;
     if (!p) return fail(WG_EINVAL, "null params");
-    if (!pol) return fail(WG_EINVAL, "wg_rollout_policy: null policy");
-    if (!pol->w2) return fail(WG_EINVAL, "wg_rollout_policy: null w2");
-    if (n_steps < 1) return fail(WG_EINVAL, "wg_rollout_policy: n_steps %d < 1", n_steps);
+    if (!pol) return fail(WG_EINVAL, "%s: null policy", fn);
+    if (!pol->w2) return fail(WG_EINVAL, "%s: null w2", fn);
+    if (n_steps < 1) return fail(WG_EINVAL, "%s: n_steps %d < 1", fn, n_steps);
     if (pol->hidden < 0 || pol->hidden > 256)
-        return fail(WG_EINVAL, "wg_rollout_policy: hidden %d outside 0..256", pol->hidden);
-    if (pol->hidden > 0 && !pol->w1) return fail(WG_EINVAL, "wg_rollout_policy: hidden %d with a null w1", pol->hidden);
+        return fail(WG_EINVAL, "%s: hidden %d outside 0..256", fn, pol->hidden);
+    if (pol->hidden > 0 && !pol->w1) return fail(WG_EINVAL, "%s: hidden %d with a null w1", fn, pol->hidden);
     if (pol->act_dim < 1 || pol->act_dim > b->A)
-        return fail(WG_EINVAL, "wg_rollout_policy: act_dim %d outside 1..A = %d", pol->act_dim, b->A);
+        return fail(WG_EINVAL, "%s: act_dim %d outside 1..A = %d", fn, pol->act_dim, b->A);
     if (pol->obs_dim != obs_row_len(b, p))
-        return fail(WG_EINVAL, "wg_rollout_policy: obs_dim %d, the batch's rows have %d values", pol->obs_dim,
+        return fail(WG_EINVAL, "%s: obs_dim %d, the batch's rows have %d values", fn, pol->obs_dim,
                     obs_row_len(b, p));
     if (pol->n_sets < 1 || b->N % pol->n_sets != 0)
-        return fail(WG_EINVAL, "wg_rollout_policy: n_sets %d does not divide N = %d", pol->n_sets, b->N);
-    if (!(pol->act_limit > 0.f)) return fail(WG_EINVAL, "wg_rollout_policy: act_limit must be > 0 (+inf allowed)");
-    if (p->auto_reset != 0)
-        return fail(WG_EINVAL, "wg_rollout_policy: auto_reset %d (the resident loop has no reset tail)", p->auto_reset);
+        return fail(WG_EINVAL, "%s: n_sets %d does not divide N = %d", fn, pol->n_sets, b->N);
+    if (!(pol->act_limit > 0.f)) return fail(WG_EINVAL, "%s: act_limit must be > 0 (+inf allowed)", fn);
+    if (!episodes && p->auto_reset != 0)
+        return fail(WG_EINVAL, "%s: auto_reset %d (the resident loop has no reset tail)", fn, p->auto_reset);
+    if (episodes) {
+        if (p->auto_reset == 0)
+            return fail(WG_EINVAL, "%s: auto_reset is 0 (without episode roll-over use wg_rollout_policy)", fn);
+        // (auto-reset's own checks, as wg_step makes them)
+        if (p->auto_reset & ~3)
+            return fail(WG_EINVAL, "auto_reset %d: bits 1 (done) and 2 (non-finite) only", p->auto_reset);
+        if (!b->init_pos || !b->init_vel || !b->init_acc || !b->init_muscle_x)
+            return fail(WG_EINVAL, "auto_reset needs the snapshot (init_pos, init_vel, init_acc, init_muscle_x)");
+        if (!b->episodes) return fail(WG_EINVAL, "auto_reset needs the episodes array");
+        if (b->reset_noise && b->reset_noise_rows < 1)
+            return fail(WG_EINVAL, "auto_reset: reset_noise with reset_noise_rows %d < 1", b->reset_noise_rows);
+        if (b->reset_noise && b->reset_noise_stride < 3ll * b->N * b->M)
+            return fail(WG_EINVAL, "auto_reset: reset_noise_stride %lld < 3 * P = %lld",
+                        (long long)b->reset_noise_stride, 3ll * b->N * b->M);
+        if (!st) return fail(WG_EINVAL, "%s: null episode stats", fn);
+        if (st->ep_slots < 0) return fail(WG_EINVAL, "%s: ep_slots %d < 0", fn, st->ep_slots);
+        if ((st->ep_return || st->ep_length) && st->ep_slots == 0)
+            return fail(WG_EINVAL, "%s: ep_return / ep_length with ep_slots 0", fn);
+        if (pol->return_out || pol->length_out)
+            return fail(WG_EINVAL, "%s: return_out / length_out are defined by the first done (wg_rollout_policy); "
+                                   "the episode stats replace them", fn);
+    }
     if (p->integrator < 0 || p->integrator > 2) return fail(WG_EINVAL, "integrator must be 0/1 (run1) or 2 (run2)");
     if (!b->muscle_bounds) return fail(WG_EINVAL, "actions need muscle_bounds");
     if (p->action_mode == 1 && !b->muscle_stride) return fail(WG_EINVAL, "discrete actions need muscle_stride");
     wg_outputs out = o ? *o : wg_outputs{};
-    if (out.obs && out.obs_stride < pol->obs_dim)
-        return fail(WG_EINVAL, "wg_rollout_policy: obs_stride %d < obs_dim %d", out.obs_stride, pol->obs_dim);
-    if (out.nonfinite || out.momentum || out.reset || out.final_obs)
-        return fail(WG_EINVAL, "wg_rollout_policy: nonfinite / momentum / reset / final_obs are not produced here");
+    if ((out.obs || (episodes && out.final_obs)) && out.obs_stride < pol->obs_dim)
+        return fail(WG_EINVAL, "%s: obs_stride %d < obs_dim %d", fn, out.obs_stride, pol->obs_dim);
+    if (episodes && (out.nonfinite || out.momentum))
+        return fail(WG_EINVAL, "%s: nonfinite / momentum are not produced here", fn);
+    if (!episodes && (out.nonfinite || out.momentum || out.reset || out.final_obs))
+        return fail(WG_EINVAL, "%s: nonfinite / momentum / reset / final_obs are not produced here", fn);
     LeanGeo lg{};
     if (b->ragged || p->spring_mode != 0 || p->pair_mode != 0 ||
-        !lean_geo(b, out.obs ? out.obs_stride : 0, &lg, p->spring_mode))
-        return fail(WG_EINVAL, "wg_rollout_policy needs a batch the resident lean kernel takes (uniform, M dividing 64, "
-                               "spring_mode 0, pair_mode 0, WG_LEAN not 0)");
+        !lean_geo(b, (out.obs || (episodes && out.final_obs)) ? out.obs_stride : 0, &lg, p->spring_mode))
+        return fail(WG_EINVAL, "%s needs a batch the resident lean kernel takes (uniform, M dividing 64, "
+                               "spring_mode 0, pair_mode 0, WG_LEAN not 0)", fn);
     if (b->N == 0) return 0;
     const KParams kp = make_kparams(*p);
     KPolicy kpol{};
@@ -3760,9 +3881,9 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
     kpol.off_h = kpol.off_row + align16(lg.wpw * kpol.D * 4);
     kpol.off_a = kpol.off_h + align16(std::max(1, lg.wpw * kpol.H) * 4);
     kpol.off_w = kpol.off_a + align16(lg.wpw * kpol.C * 4);
-    lg.slice = kpol.off_w + lg.wpw * 16;
+    lg.slice = kpol.off_w + lg.wpw * (episodes ? 32 : 16);
     int lds = lg.wpb * lg.slice;
-    if (lds > 80 * 1024) return fail(WG_ERANGE, "wg_rollout_policy: workgroup needs %d B of LDS (> 80 KiB)", lds);
+    if (lds > 80 * 1024) return fail(WG_ERANGE, "%s: workgroup needs %d B of LDS (> 80 KiB)", fn, lds);
     // a shared policy's weights staged in LDS where that costs no resident wave: as many workgroups per CU (160 KiB of
     // LDS, the kernel's register budget of 4 waves per SIMD, 3 at NE 8) with the weights as without.  (Staged at the
     // price of occupancy the canonical batch ran 90.6 us per step with H = 32 against 73.8 through L2; the one-wave
@@ -3780,9 +3901,16 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
     }
     const int blocks = lean_blocks(b, lg);
     const bool e8 = use_edge8(b, lg);
+    const KReset ar = kreset(out, p->auto_reset);
 #define WG_LAUNCH_RP(D3, NE_, E8_)                                                                               \
-    hipLaunchKernelGGL((walker_rollout_policy<D3, NE_, E8_>), dim3(blocks), dim3(64 * lg.wpb), lds, stream, *b,  \
-                       kp, kpol, kout(out), n_steps, lg)
+    do {                                                                                                         \
+        if (episodes)                                                                                            \
+            hipLaunchKernelGGL((walker_rollout_policy<D3, NE_, E8_, true>), dim3(blocks), dim3(64 * lg.wpb),     \
+                               lds, stream, *b, kp, kpol, kout(out), n_steps, lg, ar, *st);                      \
+        else                                                                                                     \
+            hipLaunchKernelGGL((walker_rollout_policy<D3, NE_, E8_>), dim3(blocks), dim3(64 * lg.wpb), lds,      \
+                               stream, *b, kp, kpol, kout(out), n_steps, lg, KNoReset{}, KNoReset{});            \
+    } while (0)
 #define WG_RP_NE(D3, E8_)                                                                                        \
     do {                                                                                                         \
         if (ne <= 1) WG_LAUNCH_RP(D3, 1, E8_);                                                                   \
@@ -3937,10 +4065,12 @@ int run(const wg_batch *b, const wg_params *p, const float *action, int32_t cols
     };
     // (the resident rollout keeps the state in registers between steps: with the per-step info extras requested the
     // steps run as per-step launches instead, bit-identical)
-    // (and with auto-reset: the resident kernel has no reset tail)
-    if (resident && use_lean && p->pair_mode == 0 && !extras && !ar_mode)   // one launch for every step, state in registers
+    // (with auto-reset: the resident kernel's AR twin, the reset tail in its loop, where its episode counts fit beside
+    // the slices in the lean kernel's 80 KiB)
+    const bool ar_fits = !ar_mode || lg.wpb * (lg.slice + align16(lg.wpw * 4)) <= 80 * 1024;
+    if (resident && use_lean && p->pair_mode == 0 && !extras && ar_fits)   // one launch for every step, state in registers
         return launch_lean_rollout(b, kp, p->in3d != 0, action, cols, astride, action ? astep : 0, out, n_steps, lg,
-                                   stream);
+                                   stream, ar_mode);
     // acc and contact are read by nothing on the step path and overwritten by the next step: only the call's last step
     // stores them (the info kernel reads acc: with its outputs requested every step does)
     const int s_last = (s_total > 0 ? s_total : s_first + n_steps) - 1;
@@ -4008,6 +4138,11 @@ int wg_rollout(const wg_batch *b, const wg_params *p, const float *action, int32
 int wg_rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o,
                       int32_t n_steps, hipStream_t stream) {
     return rollout_policy(b, p, pol, o, n_steps, stream);
+}
+
+int wg_rollout_episodes(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o,
+                        const wg_episode_stats *st, int32_t n_steps, hipStream_t stream) {
+    return rollout_policy(b, p, pol, o, n_steps, stream, true, st);
 }
 
 int wg_run_ranges(const wg_range *ranges, int32_t n, const wg_params *p, const float *action, int32_t action_cols,
