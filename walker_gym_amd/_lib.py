@@ -82,7 +82,7 @@ class WgEpisodeStats(C.Structure):
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
            "wg_step_simple", "wg_observe_simple", "wg_reset", "wg_reset_noise", "wg_plan_ragged", "wg_plan_waves",
            "wg_wave_edge_passes", "wg_plan_errors", "wg_launch_geometry", "wg_launch_floor", "wg_time_step",
-           "wg_rollout_policy", "wg_rollout_episodes")
+           "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches")
 
 _lib = None
 _lock = threading.Lock()
@@ -132,6 +132,7 @@ def load(path: str | None = None):
         L.wg_time_step.argtypes = L.wg_step.argtypes + [C.POINTER(C.c_float)]   # ABI 14, measurement aid
         for f in EXPORTS[2:]:
             getattr(L, f).restype = C.c_int
+        L.wg_fix_launches.restype = C.c_longlong
         v = L.wg_abi_version()
         if v != ABI_VERSION:
             raise WalkerHipError(f"{p}: ABI version {v}, expected {ABI_VERSION}")

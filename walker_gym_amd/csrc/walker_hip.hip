@@ -24,6 +24,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -1972,19 +1973,21 @@ struct LeanTile {
     bool is_mass, is_mus, acts;
 };
 
+// FIX (the fixed-parameter instance, launch_lean's lean_fix_ok): every tile is full and every muscle acts.
+template <bool FIX = false>
 __device__ __forceinline__ LeanTile lean_tile_of(const wg_batch &b, const float *action, int action_cols,
                                                  const LeanGeo &lg, int tile, int lane) {
     LeanTile t;
     t.w0 = tile * lg.wpw;
-    t.nw = min(lg.wpw, b.N - t.w0);
+    t.nw = FIX ? lg.wpw : min(lg.wpw, b.N - t.w0);
     t.nP = t.nw * b.M; t.nE = t.nw * b.K; t.nU = t.nw * b.A;
     t.P0 = (uint32_t)t.w0 * b.M; t.E0 = (uint32_t)t.w0 * b.K; t.U0 = (uint32_t)t.w0 * b.A;
     t.wl = lane >> lg.lgM; t.q = lane & (b.M - 1);
-    t.is_mass = lane < t.nP;
+    t.is_mass = FIX || lane < t.nP;      // (FIX: wpw * M == 64)
     t.is_mus = lane < t.nU;
-    t.mu_wl = b.A > 0 ? fdiv(lane, b.A, lg.invA) : 0;
+    t.mu_wl = (FIX || b.A > 0) ? fdiv(lane, b.A, lg.invA) : 0;
     t.mu_ua = lane - t.mu_wl * b.A;
-    t.acts = action != nullptr && t.is_mus && t.mu_ua < action_cols;
+    t.acts = FIX ? t.is_mus : action != nullptr && t.is_mus && t.mu_ua < action_cols;
     return t;
 }
 
@@ -2036,9 +2039,51 @@ __device__ __forceinline__ void lean_load_muscles(const wg_batch &b, const KPara
         }
     }
 }
+// FIX: the lanes are the tile's masses and every spring pass but the last is full, so those loads take the lane's own
+// index, as a 32-bit lane offset from the tile's first element (a wave-uniform base: SALU); the muscle lanes load under
+// their exec mask (no clamps, no stride load, no zero-fill: every use of the other lanes' muscle registers is gated by
+// is_mus).  (The tile bases also keep these addresses apart from the stores' base + 32-bit offset: with the same
+// expression on both sides the compiler carried 64-bit store addresses in VGPRs from the loads on, 80 VGPRs and
+// 32 B of scratch.)
 template <int NE, bool E8>
+__device__ __forceinline__ void lean_load_fix(const wg_batch &b, const float *__restrict__ action, int action_stride,
+                                              const LeanTile &t, int lane, LeanIn<NE, E8> &L) {
+    static_assert(E8, "the fixed-parameter instance reads the compact spring records");
+    const uint32_t ln = (uint32_t)lane;
+    const float *gp = &at_u32(b.pos + 3 * (size_t)t.P0, 12u * ln), *gv = &at_u32(b.vel + 3 * (size_t)t.P0, 12u * ln);
+    L.p3[0] = gp[0]; L.p3[1] = gp[1]; L.p3[2] = gp[2];
+    L.v3[0] = gv[0]; L.v3[1] = gv[1]; L.v3[2] = gv[2];
+    const uint2 *ge = reinterpret_cast<const uint2 *>(b.edges8) + t.E0;
+    const uint32_t *gi = reinterpret_cast<const uint32_t *>(b.inc) + t.E0;
+#pragma unroll
+    for (int it = 0; it < NE; it++) {
+        const uint32_t le = it < NE - 1 ? ln + 64u * it : (uint32_t)min(lane + 64 * it, t.nE - 1);
+        const uint2 v = at_u32(ge, 8u * le);
+        L.er[it] = EdgeRec8{v.x, __uint_as_float(v.y)};
+        L.gi[it] = at_u32(gi, 4u * le);
+    }
+    L.mf = at_u32(b.mass + t.P0, 4u * ln);
+    L.pin = 0;
+    const uint32_t io = (uint32_t)t.wl * (b.M + 1) + t.q;
+    const uint16_t *go = b.inc_off + (size_t)t.w0 * (b.M + 1);
+    L.io0 = at_u32(go, 2u * io); L.io1 = at_u32(go, 2u * io + 2u);
+    L.wsteps = at_u32(b.steps + t.w0, 4u * (uint32_t)t.wl);
+    L.x = 0.f; L.lo = 0.f; L.hi = 0.f; L.stp = 0.f; L.a = 0.f;
+    if (t.is_mus) {
+        L.x = at_u32(b.muscle_x + t.U0, 4u * ln);
+        const float2 bd = at_u32(reinterpret_cast<const float2 *>(b.muscle_bounds) + t.U0, 8u * ln);
+        L.lo = bd.x; L.hi = bd.y;
+        L.a = at_u32(action + (size_t)t.w0 * (size_t)action_stride,
+                     4u * ((uint32_t)t.mu_wl * (uint32_t)action_stride + (uint32_t)t.mu_ua));
+    }
+}
+template <int NE, bool E8, bool FIX = false>
 __device__ __forceinline__ void lean_load(const wg_batch &b, const KParams &kp, const float *__restrict__ action,
                                           int action_stride, const LeanTile &t, int lane, LeanIn<NE, E8> &L) {
+    if constexpr (FIX) {
+        lean_load_fix<NE, E8>(b, action, action_stride, t, lane, L);
+        return;
+    }
     // every load unconditional from a clamped (valid) index, issued back to back: no exec-mask branch per load
     // (each with its zero-fill moves), addresses as SGPR base + 32-bit offset.  Lanes past the tile's masses,
     // springs and muscles hold duplicates; every use of them is gated (is_mass, le < nE, is_mus, acts).
@@ -2266,25 +2311,31 @@ __device__ __forceinline__ LeanTerms lean_terms(char *sl, const LeanGeo &lg) {
 // the terminal rows' copy (wg_outputs.final_obs) and the fresh rows of the walkers just reset: mass_on / mus_on select
 // the lanes that store (the mass lanes / muscle lanes of the tile, or of the reset walkers only); s = the walker's
 // position sums, mid = s / M.
-template <bool IN3D>
+// FIX: midform 1, no conmid, unit scales (x * 1.0f is x for every x, denormals kept: no multiplies).
+template <bool IN3D, bool FIX = false>
 __device__ __forceinline__ void lean_obs_rows(float *obs, int stride, const KParams &kp, int M, int A, int w0, int wl,
                                               int q, int mu_wl, int mu_ua, bool mass_on, bool mus_on, float px, float py,
                                               float pz, float vx, float vy, float vz, float ax, float ay, float az,
                                               float sx, float sy, float sz, float midx, float midy, float midz, float x) {
     constexpr int d = IN3D ? 3 : 2, per = 3 * d;
-    const int nmid = kp.conmid ? 3 : 0;
+    const int nmid = (!FIX && kp.conmid) ? 3 : 0;
     typedef float fvd __attribute__((ext_vector_type(d), aligned(4)));
     if (mass_on) {
         const uint32_t row0 = (uint32_t)(w0 + wl) * (uint32_t)stride;   // the row's first element
         // G1 getstat (midform 2, gym/walker.py:88-96) subtracts the SUM of positions
-        const float mm[3] = {kp.midform == 2 ? sx : midx, kp.midform == 2 ? sy : midy, kp.midform == 2 ? sz : midz};
+        const bool sums = !FIX && kp.midform == 2;
+        const float mm[3] = {sums ? sx : midx, sums ? sy : midy, sums ? sz : midz};
         const float pm[3] = {px, py, pz}, vm[3] = {vx, vy, vz}, am[3] = {ax, ay, az};
         fvd vp, vv, va;
 #pragma unroll
         for (int c = 0; c < d; c++) {
-            vp[c] = kp.midform ? (pm[c] - mm[c]) * kp.pk : pm[c] * kp.pk;
-            vv[c] = vm[c] * kp.vk;
-            va[c] = am[c] * kp.ak;
+            if constexpr (FIX) {
+                vp[c] = pm[c] - mm[c]; vv[c] = vm[c]; va[c] = am[c];
+            } else {
+                vp[c] = kp.midform ? (pm[c] - mm[c]) * kp.pk : pm[c] * kp.pk;
+                vv[c] = vm[c] * kp.vk;
+                va[c] = am[c] * kp.ak;
+            }
         }
         float *dst = WG_ST(obs, row0 + per * q, 1);   // (a 3-vector's type is 16 B: no array indexing over fvd)
         *reinterpret_cast<fvd *>(dst) = vp;
@@ -2299,7 +2350,8 @@ __device__ __forceinline__ void lean_obs_rows(float *obs, int stride, const KPar
             for (int r = per * M + nmid + A; r < stride; r++) *WG_ST(obs, row0 + r, 1) = 0.f;
         }
     }
-    if (mus_on) *WG_ST(obs, (uint32_t)(w0 + mu_wl) * (uint32_t)stride + per * M + nmid + mu_ua, 1) = x * kp.mk;
+    if (mus_on)
+        *WG_ST(obs, (uint32_t)(w0 + mu_wl) * (uint32_t)stride + per * M + nmid + mu_ua, 1) = FIX ? x : x * kp.mk;
 }
 
 // One wave's tile after its loads: the edge lanes leave the spring term t and the damping force df of every
@@ -2313,17 +2365,30 @@ __device__ __forceinline__ void lean_obs_rows(float *obs, int stride, const KPar
 // POL (walker_rollout_policy; with RES): what the policy's next observation row and the episode return need beside the
 // state carried in L leaves in `po` (acc, the position sums; reward and done in the walker's lane q == 0), and reward /
 // done are computed whether or not they are stored.  Dead code in every other instance.
+// The parameters the fixed-parameter instance takes as constants (launch_lean's lean_fix_ok tested them on the host).
+__device__ __forceinline__ KParams lean_fix_params(KParams kp) {
+    kp.pk = 1.f; kp.vk = 1.f; kp.ak = 1.f; kp.mk = 1.f;
+    kp.midform = 1; kp.conmid = 0; kp.action_mode = 0; kp.integrator = 0; kp.pair_mode = 0;
+    return kp;
+}
 struct LeanPolOut { float ax, ay, az, sx, sy, sz, reward; int done; int reset; };   // reset (AR): wg_outputs.reset's flag
-template <bool IN3D, int NE, bool RES = false, bool E8 = false, bool AR = false, bool POL = false>
-__device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &kp, const KOut &o,
+// FIX (walker_step_lean's fixed-parameter instance; not RES / AR / POL): full tiles (every lane a mass, le < nE tested
+// in the last spring pass only), continuous actions on every muscle, no pair passes, pins or radii, run1, midform 1
+// without conmid, unit observation scales, obs / reward / done / centroid / energy present (the steps output stays a
+// wave-uniform test).  The same arithmetic in the same order.
+template <bool IN3D, int NE, bool RES = false, bool E8 = false, bool AR = false, bool POL = false, bool FIX = false>
+__device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &kp_in, const KOut &o,
                                              const LeanGeo &lg, char *sl, const LeanTile &t, int lane,
                                              LeanIn<NE, E8> &L, bool last = true, const KReset &ar = KReset{},
                                              LeanPolOut *po = nullptr, uint32_t *epw = nullptr, int epw_stride = 1) {
+    static_assert(!FIX || (E8 && !RES && !AR && !POL && NE <= 4), "FIX: the plain E8 step instance");
+    const KParams kp_fix = FIX ? lean_fix_params(kp_in) : KParams{};
+    const KParams &kp = FIX ? kp_fix : kp_in;
     const bool store = !RES || last;
     const int M = b.M, K = b.K, A = b.A;
     const int w0 = t.w0, nE = t.nE;
     const int wl = t.wl, q = t.q, mu_wl = t.mu_wl, mu_ua = t.mu_ua;
-    const bool is_mass = t.is_mass, is_mus = t.is_mus, acts = t.acts;
+    const bool is_mass = FIX || t.is_mass, is_mus = t.is_mus, acts = FIX ? t.is_mus : t.acts;
     const uint32_t pl = t.P0 + lane, ul = t.U0 + lane;   // this lane's mass / muscle
     // slice: spring terms t (f64 x3) | df (f32 x3) | incidence words | muscle x
     const LeanTerms ts = lean_terms(sl, lg);
@@ -2333,7 +2398,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     uint32_t *s_inc = reinterpret_cast<uint32_t *>(sl + lg.off_inc);
     float *s_x = reinterpret_cast<float *>(sl + lg.off_x);
     const float mf = L.mf;
-    const bool pin = L.pin != 0;
+    const bool pin = !FIX && L.pin != 0;
     // (NE = 1: glibc's powf tables in registers, lane l < 32 holding entry l of each)
     double sq_tl = 0.0, sq_te = 0.0;
     if (NE == 1 && !RES) {   // (not the resident kernel: its carried state holds the registers)
@@ -2345,7 +2410,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     if (!RES) {   // (the resident kernel writes them once, before its first step)
 #pragma unroll
         for (int it = 0; it < NE; it++)
-            if (lane + 64 * it < nE) s_inc[lane + 64 * it] = L.gi[it];
+            if ((FIX && it < NE - 1) || lane + 64 * it < nE) s_inc[lane + 64 * it] = L.gi[it];
         if (lane == 0) s_inc[nE] = 0u;   // the read-ahead pad after the last list (mass_accumulate_v2)
     }
     float x = L.x;
@@ -2435,7 +2500,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
             const float xs = s_x[mus ? (int)__umul24(ewl, A) + ew : 0];
             xr = mus ? xs : e.rest;
         }
-        if (le < nE) {
+        if ((FIX && it < NE - 1) || le < nE) {
             if (WG_ABLATE & 1) {   // profiling builds only: no spring arithmetic
                 ts.put(le, xr + g.v[0] + g.v[3] + g.v[6] + g.v[9], g.v[1] + g.v[4] + g.v[7] + g.v[10],
                        g.v[2] + g.v[5] + g.v[8] + g.v[11], e.k, e.c, 0.f);
@@ -2449,7 +2514,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     for (int it = 0; it < NE; it++) {
         // no early loop exit: it keeps er[] in registers (a reference under a `break` made hipcc park the rest
         // lengths in scratch right after their loads, serialising them)
-        if (64 * it >= nE) continue;                       // wave-uniform
+        if (!FIX && 64 * it >= nE) continue;               // wave-uniform (FIX: NE passes exactly)
         if ((WG_ABLATE & 4096) && it == NE - 1 && it > 0) {   // (ablation: the last spring pass's terms as zeros)
             const int le = lane + 64 * it;
             if (le < nE) ts.put(le, 0.0, 0.0, 0.0, 0.f, 0.f, 0.f);
@@ -2494,7 +2559,8 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
             px = __builtin_nanf(""); py = px; pz = px; vx = px; vy = px; vz = px; ax = px; ay = px; az = px;
             hit = false;
         }
-        if (b.radius && store) b.radius[pl] = hit ? 3.0 : 1.0;   // p.r = 3 / p.r = 1 (gym/optimized_env.py:156,175)
+        // p.r = 3 / p.r = 1 (gym/optimized_env.py:156,175)
+        if (!FIX && b.radius && store) b.radius[pl] = hit ? 3.0 : 1.0;
         nv = np_norm3(vx, vy, vz);
         if (!(NE == 1 && !RES)) ke = dead ? nv : mf * np_sq<NE == 1>(nv);   // p.m * norm(p.v) ** 2 (optimized_env.py:242)
         pe = (float)((double)mf * kp.g) * (py - kp.ground);
@@ -2533,36 +2599,36 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
             const int steps = L.wsteps + 1;
             if (store) *WG_ST(b.steps, wg, 1) = steps;
             if (RES) L.wsteps = steps;
-            if (o.steps) *WG_ST(o.steps, wg, 1) = steps;
+            if (o.steps) *WG_ST(o.steps, wg, 1) = steps;   // (uniform batches in caller order have none)
             const float cy = ysum * lg.invM;
             if constexpr (POL) {   // the same expression, kept for the return
                 const float vpen = (-(vsum * lg.invM)) * 0.1f;
                 po->reward = (cy + vpen) + neg_half_count((int)__popcll(hb & gmask));
                 if (o.reward) *WG_ST(o.reward, wg, 1) = po->reward;
-            } else if (o.reward) {
+            } else if (FIX || o.reward) {
                 const float vpen = (-(vsum * lg.invM)) * 0.1f;
                 *WG_ST(o.reward, wg, 1) = (cy + vpen) + neg_half_count((int)__popcll(hb & gmask));
             }
-            if (o.done || (AR && (ar.mode & 1)) || POL) {
+            if (FIX || o.done || (AR && (ar.mode & 1)) || POL) {
                 int done = steps >= kp.max_steps;
                 if (!done && cy < kp.done_y) done = 1;
                 if (!done && steps > 100) done = (sb & gmask) == gmask;
-                if (o.done) at_u32w(o.done, wg) = (uint8_t)done;
+                if (FIX || o.done) at_u32w(o.done, wg) = (uint8_t)done;
                 ep_done = done;
             }
-            if (o.centroid) {
+            if (FIX || o.centroid) {
                 float *c = WG_ST(o.centroid, wg, 3);
                 c[0] = midx; c[1] = midy; c[2] = midz;
             }
-            if (o.energy) *WG_ST(o.energy, wg, 1) = 0.5f * ksum + psum;
+            if (FIX || o.energy) *WG_ST(o.energy, wg, 1) = 0.5f * ksum + psum;
         }
     }
 
     STAMP(5);
     // ================= observation rows: Creature.getstat (gym/optimized_walker.py:129-162) =========
-    if (o.obs && !(WG_ABLATE & 16))
-        lean_obs_rows<IN3D>(o.obs, o.obs_stride, kp, M, A, w0, wl, q, mu_wl, mu_ua, is_mass, is_mus, px, py, pz, vx, vy,
-                            vz, ax, ay, az, sx, sy, sz, midx, midy, midz, x);
+    if ((FIX || o.obs) && !(WG_ABLATE & 16))
+        lean_obs_rows<IN3D, FIX>(o.obs, o.obs_stride, kp, M, A, w0, wl, q, mu_wl, mu_ua, is_mass, is_mus, px, py, pz,
+                                 vx, vy, vz, ax, ay, az, sx, sy, sz, midx, midy, midz, x);
     // ================= auto-reset (ABI 16): the walkers whose episode this step ended start their next one here
     float rsx = sx, rsy = sy, rsz = sz;   // (POL) the position sums the next row is built from
     if constexpr (AR) {
@@ -2664,7 +2730,8 @@ constexpr int lean_waves(int NE) { return NE >= 8 ? 4 : 6; }
 
 // One tile (64 / M walkers) per wave; waves never wait for one another.  E8: the compact spring records (b.edges8).
 // AR: the auto-reset tail (ABI 16), its arguments in the trailing `ar` (empty otherwise).
-template <bool IN3D, int NE, bool E8, bool AR = false>
+// FIX: the fixed-parameter instance for full tiles on the default path (lean_fix_ok; WG_FIX=0 forces the generic one).
+template <bool IN3D, int NE, bool E8, bool AR = false, bool FIX = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(NE)))) void walker_step_lean(
     typename std::conditional<AR, wg_batch, KBatch15>::type bk, KParams kp, const float *__restrict__ action,
     int action_cols, int action_stride, KOut o, LeanGeo lg, typename std::conditional<AR, KReset, KNoReset>::type ar) {
@@ -2680,15 +2747,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
     const int stamp_wave = tile;
 #endif
     STAMP(0);
-    const LeanTile t = lean_tile_of(b, action, action_cols, lg, tile, lane);
+    const LeanTile t = lean_tile_of<FIX>(b, action, action_cols, lg, tile, lane);
     LeanIn<NE, E8> L;
     // load-phase wave priority: this wave's HBM requests leave before other waves' arithmetic
     if (kp.prio) __builtin_amdgcn_s_setprio(2);
-    lean_load<NE, E8>(b, kp, action, action_stride, t, lane, L);
+    lean_load<NE, E8, FIX>(b, kp, action, action_stride, t, lane, L);
     if (kp.prio) __builtin_amdgcn_s_setprio(0);
     STAMP(1);
     if constexpr (AR) lean_compute<IN3D, NE, false, E8, true>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L, true, ar);
-    else lean_compute<IN3D, NE, false, E8>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
+    else lean_compute<IN3D, NE, false, E8, false, false, FIX>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
 }
 
 // NE = 1, the latency-bound small batches (Balance-4096: 512 waves, one per SIMD, the launch as long as its slowest
@@ -2701,7 +2768,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
 // step, same box, interleaved: round 5's prologue 5.33 us, the same arguments in one scalar round 5.01
 // (profiles/r06b_ab_balance4096_prologue.json), preloaded 2.5 % below that (profiles/r06e_ab_*).
 // E8: `edges` is the batch's compact records (b.edges8) in the same preloaded slot.
-template <bool IN3D, bool E8, bool AR = false>
+// FIX: as walker_step_lean's.
+template <bool IN3D, bool E8, bool AR = false, bool FIX = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(1)))) void walker_step_lean1(
     float *pos, float *vel, const void *edges, const uint16_t *inc, int N, int M, int K, int wpw, int wpb, int nblkx,
     wg_batch b, KParams kp, const float *__restrict__ action, int action_cols, int action_stride, KOut o, LeanGeo lg,
@@ -2721,14 +2789,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
     const int stamp_wave = tile;
 #endif
     STAMP(0);
-    const LeanTile t = lean_tile_of(b, action, action_cols, lg, tile, lane);
+    const LeanTile t = lean_tile_of<FIX>(b, action, action_cols, lg, tile, lane);
     LeanIn<1, E8> L;
     if (kp.prio) __builtin_amdgcn_s_setprio(2);
-    lean_load<1, E8>(b, kp, action, action_stride, t, lane, L);
+    lean_load<1, E8, FIX>(b, kp, action, action_stride, t, lane, L);
     if (kp.prio) __builtin_amdgcn_s_setprio(0);
     STAMP(1);
     if constexpr (AR) lean_compute<IN3D, 1, false, E8, true>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L, true, ar);
-    else lean_compute<IN3D, 1, false, E8>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
+    else lean_compute<IN3D, 1, false, E8, false, false, FIX>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
 }
 
 // n_steps env steps in one launch (wg_rollout): the tile's static inputs (spring records, incidence lists, masses,
@@ -3706,6 +3774,32 @@ bool lean_geo(const wg_batch *b, int obs_stride, LeanGeo *out, int spring_mode =
 // grid of a lean launch: one tile (64 / M walkers) per wave
 int lean_blocks(const wg_batch *b, const LeanGeo &g) { return (b->N + g.wpb * g.wpw - 1) / (g.wpb * g.wpw); }
 
+// The fixed-parameter instance (FIX) runs a launch whose every tile is full and whose batch, parameters, actions and
+// outputs are the default path's: compact records in 1..4 passes, no auto-reset, continuous actions for every muscle,
+// no pair passes, pins or radii, run1, midform 1 without conmid, unit observation scales (by bit pattern), every
+// per-step output but the optional steps asked for.  Anything else takes the generic instance, as a whole launch (a
+// partial last tile too).  WG_FIX=0 (read on every launch, like WG_EDGE8) forces the generic instance: the control arm
+// and the tests' cross-check.
+bool lean_fix_ok(const wg_batch *b, const KParams &kp, const float *a, int cols, int astride, const wg_outputs &o,
+                 const LeanGeo &g, bool e8, int ne, int ar_mode) {
+#ifdef WG_STAMPS
+    return false;
+#endif
+    if (WG_ABLATE != 0 || env_int("WG_FIX", 1) == 0) return false;
+    auto one = [](float f) {
+        uint32_t u;
+        memcpy(&u, &f, sizeof u);
+        return u == 0x3f800000u;
+    };
+    return e8 && ne >= 1 && ne <= 4 && ar_mode == 0 && b->N % g.wpw == 0 && g.wpw * b->M == 64 &&
+           b->A >= 1 && a != nullptr && cols >= b->A && astride >= b->A && kp.action_mode == 0 &&
+           kp.pair_mode == 0 && !b->pinned && !b->radius && kp.integrator != 2 && kp.midform == 1 && kp.conmid == 0 &&
+           one(kp.pk) && one(kp.vk) && one(kp.ak) && one(kp.mk) &&
+           o.obs && o.reward && o.done && o.centroid && o.energy;
+}
+// launches that took the fixed-parameter instance, this process (wg_fix_launches: the tests read which instance ran)
+std::atomic<long long> g_fix_launches{0};
+
 // ar_mode (wg_params.auto_reset) != 0: the AR instances (the auto-reset tail, ABI 16)
 int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const float *a, int cols, int astride,
                 const wg_outputs &o, const LeanGeo &g, hipStream_t st, int ar_mode = 0) {
@@ -3714,6 +3808,33 @@ int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const float *a,
     // WG_LDS_PAD (diagnostic): extra LDS bytes per workgroup, to measure the kernel at lower occupancy
     const int lds = g.wpb * g.slice + std::max(0, env_int("WG_LDS_PAD", 0));
     const bool e8 = use_edge8(b, g);
+    if (lean_fix_ok(b, kp, a, cols, astride, o, g, e8, ne, ar_mode)) {   // (E8, no auto-reset)
+#define WG_LAUNCH_FIX(D3, NE_)                                                                                   \
+    WG_KLAUNCH((walker_step_lean<D3, NE_, true, false, true>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st, \
+               kbatch15(b), kp, a, cols, astride, kout(o), g, KNoReset{})
+#define WG_LAUNCH_FIX1(D3)                                                                                       \
+    WG_KLAUNCH((walker_step_lean1<D3, true, false, true>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st,    \
+               b->pos, b->vel, static_cast<const void *>(b->edges8), b->inc, b->N, b->M, b->K, g.wpw, g.wpb,     \
+               (int)((unsigned)g.nblk | ((unsigned)(kp.xcd & 2) << 29) | ((unsigned)(kp.prio != 0) << 31)), *b,  \
+               kp, a, cols, astride, kout(o), g, KNoReset{})
+        if (in3d) {
+            if (ne == 1) WG_LAUNCH_FIX1(true);
+            else if (ne == 2) WG_LAUNCH_FIX(true, 2);
+            else if (ne == 3) WG_LAUNCH_FIX(true, 3);
+            else WG_LAUNCH_FIX(true, 4);
+        } else {
+            if (ne == 1) WG_LAUNCH_FIX1(false);
+            else if (ne == 2) WG_LAUNCH_FIX(false, 2);
+            else if (ne == 3) WG_LAUNCH_FIX(false, 3);
+            else WG_LAUNCH_FIX(false, 4);
+        }
+#undef WG_LAUNCH_FIX1
+#undef WG_LAUNCH_FIX
+        const hipError_t ef = hipGetLastError();
+        if (ef != hipSuccess) return fail(WG_EHIP, "launch failed: %s", hipGetErrorString(ef));
+        g_fix_launches.fetch_add(1, std::memory_order_relaxed);
+        return 0;
+    }
 #define WG_LAUNCH_LEAN(D3, NE_, E8_)                                                                             \
     do {                                                                                                         \
         if (ar_mode)                                                                                             \
@@ -4351,6 +4472,8 @@ int wg_debug_stamps(unsigned long long *host, int n) {
     return fail(WG_EINVAL, "not a stamps build");
 #endif
 }
+
+long long wg_fix_launches(void) { return g_fix_launches.load(std::memory_order_relaxed); }
 
 int wg_launch_geometry(const wg_batch *b, wg_launch_info *info) {
     int rc = validate(b);

@@ -284,6 +284,9 @@ class DeviceBatch:
                    lds_bytes=info.lds_bytes)
         if self.ragged_kind == 2:
             geo["wave_tiles"] = self.plan_blocks
+        # this process's step launches that took the lean kernel's fixed-parameter instance so far (a counter: the
+        # difference around a call tells which instance ran it; WG_FIX=0 forces the generic one)
+        geo["fix_launches"] = int(_lib.load().wg_fix_launches())
         return geo
 
     KIND = {"pos": "mass", "vel": "mass", "acc": "mass", "contact": "mass", "radius": "mass", "muscle_x": "muscle",
