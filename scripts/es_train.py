@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""Train Balance-v0 with walker_gym_amd.es.EvolutionStrategy for some generations and record the fitness curve: per
+generation the candidates' mean / max / min fitness (the mean return of a candidate's walkers over `--steps` steps from
+the same start state) and the return of the mean policy (theta itself, one shared parameter set).  Nothing is asserted:
+the curve is recorded as it comes.
+
+    python scripts/es_train.py [--walkers 1024] [--population 1024] [--hidden 0] [--generations 30] [--steps 200]
+                               [--sigma 0.001] [--lr 1e-4] [--seed 0] [--out profiles/r10_es_balance_curve.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from walker_gym_amd.batched_env import BatchedPhysicsEnv   # noqa: E402
+from walker_gym_amd.es import EvolutionStrategy            # noqa: E402
+from walker_gym_amd.walker import balance_spec             # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--walkers", type=int, default=1024)
+    ap.add_argument("--population", type=int, default=1024)
+    ap.add_argument("--hidden", type=int, default=0)
+    ap.add_argument("--generations", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--sigma", type=float, default=0.001)
+    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    env = BatchedPhysicsEnv(balance_spec(a.walkers), in3d=0)
+    tr = EvolutionStrategy(env, hidden=a.hidden, population=a.population, sigma=a.sigma, lr=a.lr, seed=a.seed)
+    start = env.batch.state_dict()
+    curve = []
+    t0 = time.perf_counter()
+    for g in range(a.generations):
+        env.batch.load_state_dict(start)
+        mean_ret = env.rollout_policy(tr.mean_policy(), a.steps)["returns"].double().mean()
+        out = tr.generation_step(a.steps)
+        curve.append({"generation": g, "mean_policy_return": float(mean_ret),
+                      "fitness_mean": float(out["fitness_mean"]), "fitness_max": float(out["fitness_max"]),
+                      "fitness_min": float(out["fitness_min"]),
+                      "diverged_candidates": int(torch.isnan(out["fitness"]).sum()),
+                      "grad_norm": float(out["grad"].double().norm())})
+        print(json.dumps(curve[-1]), flush=True)
+    torch.cuda.synchronize()
+    res = {"env": "Balance-v0", "walkers": env.N, "population": tr.G, "hidden": tr.H, "K": tr.K, "steps": a.steps,
+           "sigma": tr.sigma, "lr": tr.lr, "seed": tr.seed, "seconds": time.perf_counter() - t0,
+           "device": torch.cuda.get_device_name(0), "curve": curve}
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+
+
+if __name__ == "__main__":
+    main()

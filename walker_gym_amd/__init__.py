@@ -7,6 +7,8 @@ include/walker_hip.h, HIP kernels for gfx950).  Drop-in facades of the reference
   walker_gym_amd.optimized_env PhysicsEnv, make_env, Environment            (gym/optimized_env.py)
   walker_gym_amd.env           Environment (G1 step(t) API)                  (gym/env.py)
   walker_gym_amd.snapshot      state.pkl read/write without unpickling       (gym/engine.py:199-212)
+Training on the device: walker_gym_amd.policy.MLPPolicy (evaluated inside the rollout kernels) and
+walker_gym_amd.es.EvolutionStrategy (seeded perturb / update kernels, wg_es_* in the header).
 Importing the package needs no GPU; stepping does (no CPU fallback).
 """
 from .engine import Config, DingPoint, Point, to_data  # noqa: F401
@@ -24,6 +26,9 @@ def __getattr__(name):
     if name == "MLPPolicy":
         from . import policy
         return policy.MLPPolicy
+    if name == "EvolutionStrategy":
+        from . import es
+        return es.EvolutionStrategy
     if name in ("PhysicsEnv", "make_env"):
         from . import optimized_env
         return getattr(optimized_env, name)

@@ -79,10 +79,17 @@ class WgEpisodeStats(C.Structure):
                 ("tail_length", _vp), ("ep_return", _vp), ("ep_length", _vp), ("ep_slots", C.c_int32)]
 
 
+class WgEs(C.Structure):
+    """wg_es: the seeded perturbation of wg_es_perturb / wg_es_update (theta's segments: w1, b1, w2, b2)."""
+    _fields_ = [("n_sets", C.c_int32), ("obs_dim", C.c_int32), ("hidden", C.c_int32), ("act_dim", C.c_int32),
+                ("seed", C.c_uint64), ("generation", C.c_uint32), ("sigma", C.c_float), ("theta", _vp),
+                ("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp)]
+
+
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
            "wg_step_simple", "wg_observe_simple", "wg_reset", "wg_reset_noise", "wg_plan_ragged", "wg_plan_waves",
            "wg_wave_edge_passes", "wg_plan_errors", "wg_launch_geometry", "wg_launch_floor", "wg_time_step",
-           "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches")
+           "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches", "wg_es_perturb", "wg_es_update")
 
 _lib = None
 _lock = threading.Lock()
@@ -113,6 +120,8 @@ def load(path: str | None = None):
                                         C.POINTER(WgOutputs), C.c_int32, _vp]
         L.wg_rollout_episodes.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), C.POINTER(WgPolicy),
                                           C.POINTER(WgOutputs), C.POINTER(WgEpisodeStats), C.c_int32, _vp]
+        L.wg_es_perturb.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp]
+        L.wg_es_update.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp, C.c_double, C.c_float, _vp, _vp, _vp, _vp]
         L.wg_step_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,
                                      C.POINTER(_vp)]
         L.wg_run_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,

@@ -19,6 +19,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "walker_hip.hip")
+ES_SRC = os.path.join(HERE, "csrc", "es_hip.hip")   # wg_es_*: a unit of its own, the same flags, the same library
 HDR = os.path.join(ROOT, "include", "walker_hip.h")
 POWF2 = os.path.join(HERE, "csrc", "powf2.h")
 OUT = os.path.join(HERE, "libwalker_hip.so")
@@ -40,14 +41,14 @@ def hipcc() -> str:
 
 
 def command(out: str = OUT) -> list:
-    return [hipcc(), f"--offload-arch={ARCH}", *FLAGS, "-I", os.path.join(ROOT, "include"), "-o", out, SRC]
+    return [hipcc(), f"--offload-arch={ARCH}", *FLAGS, "-I", os.path.join(ROOT, "include"), "-o", out, SRC, ES_SRC]
 
 
 def needs_build(out: str = OUT) -> bool:
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(p) > t for p in (SRC, HDR, POWF2, __file__))
+    return any(os.path.getmtime(p) > t for p in (SRC, ES_SRC, HDR, POWF2, __file__))
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

@@ -1,0 +1,265 @@
+"""Evolution strategies on the device: EvolutionStrategy over wg_es_perturb / wg_es_update (include/walker_hip.h), and
+the numpy restatements of their arithmetic contract, which agree with the kernels bit for bit.
+
+The noise is a pure function of (seed, generation, pair, parameter index), one Philox4x32-10 call per value, so it is
+never stored: the perturb kernel writes the G candidate parameter sets straight into the tensors an MLPPolicy hands to
+rollout_policy / rollout_episodes, and the update kernel regenerates the same noise.  A rank that owns a slice of the
+population needs (seed, generation) and an all-gather of G fitness scalars, nothing else.
+
+theta is a flat float32 [K] vector: w1 (D*H, element (i, h) at i*H + h; only with a hidden layer), b1 (H; only with
+biases), w2 (n2*C with n2 = H or D, element (i, c) at i*C + c), b2 (C; only with biases).  Sets 2j and 2j + 1 are
+theta +- RN32(sigma * eps_j) (antithetic pairs).  The update is the centred-rank estimate
+  grad[k] = scale * sum_j (util[2j] - util[2j+1]) * eps_j[k],   scale = 1 / (2 * n_pairs * sigma),
+summed in float64 in a fixed order (chunks of 256 pairs), then theta += lr * grad in float32.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import _lib
+
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+NOISE_TAG = 0x45530001          # counter word 3 of every noise call
+NOISE_SCALE = np.float32(1.0 / np.sqrt(8 * (65536 ** 2 - 1) / 12))   # bits 0x379CC471
+CHUNK = 256                     # pairs per float64 partial sum of the update
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+# ---------------------------------------------------------------------------------------------------- host restatements
+def philox4x32(counter, key, rounds: int = 10) -> np.ndarray:
+    """Philox4x32 (Random123): counter [..., 4] and key [..., 2] of 32-bit words (broadcast against each other) ->
+    [..., 4] uint32."""
+    c = np.asarray(counter, dtype=np.uint64)
+    k = np.asarray(key, dtype=np.uint64)
+    c0, c1, c2, c3 = (c[..., i] & _M32 for i in range(4))
+    k0, k1 = (k[..., i] & _M32 for i in range(2))
+    m0, m1 = np.uint64(PHILOX_M0), np.uint64(PHILOX_M1)
+    s32 = np.uint64(32)
+    for r in range(rounds):
+        p0, p1 = m0 * c0, m1 * c2                      # 32 x 32 -> 64 bits, exact in uint64
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & _M32, (p0 >> s32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + np.uint64(PHILOX_W0)) & _M32, (k1 + np.uint64(PHILOX_W1)) & _M32
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1).astype(np.uint32)
+
+
+def es_noise_numpy(seed: int, generation: int, first_pair: int, n_pairs: int, K: int) -> np.ndarray:
+    """eps(seed, generation, j, k) for j in [first_pair, first_pair + n_pairs), k in [0, K): float32 [n_pairs, K]."""
+    seed, generation = int(seed), int(generation)
+    if not 0 <= seed < 1 << 64 or not 0 <= generation < 1 << 32:
+        raise ValueError("seed is a uint64 and generation a uint32")
+    j = (np.arange(n_pairs, dtype=np.uint64) + np.uint64(first_pair))[:, None]
+    k = np.arange(K, dtype=np.uint64)[None, :]
+    ctr = np.stack(np.broadcast_arrays(k, j, np.uint64(generation), np.uint64(NOISE_TAG)), axis=-1)
+    out = philox4x32(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)).astype(np.int64)
+    s = ((out & 0xFFFF) + (out >> 16)).sum(axis=-1)    # the eight 16-bit halves
+    return (s - 262140).astype(np.float32) * NOISE_SCALE
+
+
+def es_perturb_numpy(theta, sigma, seed: int, generation: int, first_pair: int, n_pairs: int) -> np.ndarray:
+    """The candidates of pairs [first_pair, first_pair + n_pairs) as flat vectors: float32 [2 * n_pairs, K], row 2i the
+    `+` member of pair first_pair + i, row 2i + 1 its `-` member."""
+    theta = np.ascontiguousarray(theta, dtype=np.float32)
+    d = np.float32(sigma) * es_noise_numpy(seed, generation, first_pair, n_pairs, theta.shape[0])
+    out = np.empty((2 * n_pairs, theta.shape[0]), np.float32)
+    out[0::2] = theta[None, :] + d
+    out[1::2] = theta[None, :] - d
+    return out
+
+
+def es_utilities_numpy(fitness) -> np.ndarray:
+    """Centred ranks in [-0.5, 0.5]: NaN counts as -inf, ties break by index (stable ascending argsort)."""
+    f = np.array(fitness, dtype=np.float32)
+    G = f.shape[0]
+    f[np.isnan(f)] = -np.inf
+    order = np.argsort(f, kind="stable")
+    rank = np.empty(G, np.int64)
+    rank[order] = np.arange(G)
+    return (2 * rank - (G - 1)).astype(np.float32) * np.float32(1.0 / (2 * (G - 1)))
+
+
+def es_update_numpy(theta, util, seed: int, generation: int, first_pair: int, n_pairs: int, scale: float, lr):
+    """wg_es_update's arithmetic: (grad, theta_out), float32 [K] each.  util is indexed by set ([G])."""
+    theta = np.ascontiguousarray(theta, dtype=np.float32)
+    util = np.ascontiguousarray(util, dtype=np.float32)
+    K = theta.shape[0]
+    with np.errstate(all="ignore"):
+        sets = 2 * (first_pair + np.arange(n_pairs))
+        d = (util[sets] - util[sets + 1]).astype(np.float64)
+        S = np.zeros(K, np.float64)
+        for a in range(0, n_pairs, CHUNK):
+            n = min(CHUNK, n_pairs - a)
+            eps = es_noise_numpy(seed, generation, first_pair + a, n, K).astype(np.float64)
+            P = np.zeros(K, np.float64)
+            for i in range(n):
+                P = P + d[a + i] * eps[i]
+            S = S + P
+        grad = (S * np.float64(scale)).astype(np.float32)
+        return grad, theta + np.float32(lr) * grad
+
+
+def param_count(D: int, H: int, Cc: int, biases: bool) -> int:
+    return (D * H + (H if biases else 0) if H else 0) + (H if H else D) * Cc + (Cc if biases else 0)
+
+
+def split_theta(flat, D: int, H: int, Cc: int, biases: bool) -> dict:
+    """Views of the segments of flat [..., K] as {'w1': [..., D, H], 'b1': [..., H], 'w2': [..., n2, C], 'b2': [..., C]}
+    (None for an absent one); works on numpy arrays and torch tensors."""
+    lead, o, out = tuple(flat.shape[:-1]), 0, {}
+    n2 = H if H else D
+    for name, shape, there in (("w1", (D, H), H > 0), ("b1", (H,), H > 0 and biases), ("w2", (n2, Cc), True),
+                               ("b2", (Cc,), biases)):
+        n = int(np.prod(shape)) if there else 0
+        out[name] = flat[..., o:o + n].reshape(lead + shape) if there else None
+        o += n
+    if o != flat.shape[-1]:
+        raise ValueError(f"{flat.shape[-1]} parameters, the shapes take {o}")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- the trainer
+class EvolutionStrategy:
+    """Antithetic evolution strategies with centred-rank utilities over an MLPPolicy of `population` parameter sets on
+    env's device.  ask() -> MLPPolicy of the generation's candidates; tell(fitness) -> the update; generation_step() a
+    whole generation from the state captured at construction."""
+
+    def __init__(self, env, hidden: int = 0, act_dim: Optional[int] = None, biases: bool = True,
+                 population: Optional[int] = None, sigma: float = 0.05, lr: float = 0.05, seed: int = 0,
+                 act_limit: float = 1.0, theta0=None):
+        import torch
+        from .policy import MLPPolicy
+        self.env = env
+        N, D = int(env.N), int(env.obs_dim)
+        H, Cc = int(hidden), int(env.batch.A if act_dim is None else act_dim)
+        G = N if population is None else int(population)
+        if G < 2 or G % 2:
+            raise ValueError(f"population {G} must be even and >= 2 (antithetic pairs)")
+        if N % G:
+            raise ValueError(f"population {G} does not divide N = {N}")
+        if not 0 <= H <= 256:
+            raise ValueError(f"hidden {H} outside 0..256")
+        if Cc < 1:
+            raise ValueError(f"act_dim {Cc} < 1")
+        if not (np.isfinite(sigma) and sigma > 0):
+            raise ValueError(f"sigma must be finite and > 0, got {sigma!r}")
+        if not np.isfinite(lr):
+            raise ValueError(f"lr must be finite, got {lr!r}")
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError("seed is a uint64")
+        self.D, self.H, self.C, self.G, self.biases = D, H, Cc, G, bool(biases)
+        self.K = param_count(D, H, Cc, self.biases)
+        self.sigma, self.lr, self.seed, self.generation = float(np.float32(sigma)), float(np.float32(lr)), int(seed), 0
+        dv = env.device
+        if theta0 is None:
+            self.theta = torch.zeros(self.K, dtype=torch.float32, device=dv)
+        else:
+            t0 = torch.as_tensor(np.asarray(theta0.detach().cpu() if hasattr(theta0, "detach") else theta0,
+                                            dtype=np.float32))
+            if t0.dim() != 1 or t0.numel() != self.K:
+                raise ValueError(f"theta0 has shape {tuple(t0.shape)}, expected ({self.K},)")
+            self.theta = t0.to(dv).contiguous()
+        # the candidates (allocated once, rewritten by every ask()), behind one MLPPolicy
+        n2 = H if H else D
+        e = lambda *s: torch.empty(s, dtype=torch.float32, device=dv)
+        w1 = e(G, D, H) if H else None
+        b1 = e(G, H) if H and self.biases else None
+        b2 = e(G, Cc) if self.biases else None
+        self.policy = MLPPolicy(e(G, n2, Cc), b2, w1, b1, act_limit=act_limit)
+        self.act_limit = self.policy.act_limit
+        self.n_pairs = G // 2
+        self._work = torch.empty((-(-self.n_pairs // CHUNK), self.K), dtype=torch.float64, device=dv)
+        self._grad = torch.empty(self.K, dtype=torch.float32, device=dv)
+        self._state0 = env.batch.state_dict()
+
+    # -------------------------------------------------------------------------------------------- the two kernels
+    def _struct(self) -> _lib.WgEs:
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        pol = self.policy
+        return _lib.WgEs(n_sets=self.G, obs_dim=self.D, hidden=self.H, act_dim=self.C, seed=self.seed,
+                         generation=self.generation, sigma=self.sigma, theta=p(self.theta), w1=p(pol.w1), b1=p(pol.b1),
+                         w2=p(pol.w2), b2=p(pol.b2))
+
+    def ask(self):
+        """Write the generation's candidates (wg_es_perturb over every pair) and return their MLPPolicy (the same
+        object every time: its tensors are rewritten in place)."""
+        es = self._struct()
+        _lib.check(_lib.load().wg_es_perturb(C.byref(es), 0, self.n_pairs, self.env._stream()), "wg_es_perturb")
+        return self.policy
+
+    def utilities(self, fitness):
+        """Centred ranks of fitness [G] on the device (es_utilities_numpy's arithmetic: integer operations and one
+        float32 multiply)."""
+        import torch
+        f = torch.as_tensor(fitness, dtype=torch.float32, device=self.theta.device).reshape(-1)
+        if f.numel() != self.G:
+            raise ValueError(f"fitness has {f.numel()} values, the population {self.G}")
+        f = torch.where(torch.isnan(f), torch.full_like(f, float("-inf")), f)
+        order = torch.argsort(f, stable=True)
+        rank = torch.empty(self.G, dtype=torch.int64, device=f.device)
+        rank[order] = torch.arange(self.G, dtype=torch.int64, device=f.device)
+        return (2 * rank - (self.G - 1)).to(torch.float32) * float(np.float32(1.0 / (2 * (self.G - 1))))
+
+    def tell(self, fitness) -> dict:
+        """Update theta in place from the candidates' fitness [G] (higher is better; NaN ranks lowest) and move to the
+        next generation.  Returns {'grad': [K] f32, the estimate theta moved along (for a caller's own optimiser)}."""
+        util = self.utilities(fitness).contiguous()
+        es = self._struct()
+        scale = 1.0 / (2.0 * self.n_pairs * self.sigma)
+        _lib.check(_lib.load().wg_es_update(C.byref(es), 0, self.n_pairs, C.c_void_p(util.data_ptr()), scale, self.lr,
+                                            C.c_void_p(self._work.data_ptr()), C.c_void_p(self._grad.data_ptr()),
+                                            C.c_void_p(self.theta.data_ptr()), self.env._stream()), "wg_es_update")
+        self.generation += 1
+        return {"grad": self._grad.clone()}
+
+    # -------------------------------------------------------------------------------------------- a whole generation
+    def fitness_of(self, res: dict, n_steps: int):
+        """Per-set fitness [G] f32 of a rollout's result: rollout_policy's mean return of the set's walkers, or
+        rollout_episodes' reward per walker step (finished episodes and the unfinished tail), summed in float64."""
+        import torch
+        wps = self.env.N // self.G
+        if "returns" in res:
+            return (res["returns"].double().view(self.G, wps).sum(dim=1) / wps).to(torch.float32)
+        tot = res["return_sum"].double() + res["tail_return"].double()
+        return (tot.view(self.G, wps).sum(dim=1) / (wps * int(n_steps))).to(torch.float32)
+
+    def generation_step(self, n_steps: int, restore: bool = True) -> dict:
+        """One generation: (restore the state captured at construction,) ask, one closed-loop rollout of every
+        candidate (rollout_policy, or rollout_episodes when the env has auto-reset on), tell.  ValueError for what the
+        rollout refuses (resident batches only).  Returns the generation's number, 'fitness' [G] f32, 'grad' [K] f32
+        and the fitness statistics 'fitness_mean' / 'fitness_max' / 'fitness_min' over the candidates that did not
+        diverge, as 0-d device tensors (nothing here waits for the device)."""
+        import torch
+        env = self.env
+        if restore:
+            env.batch.load_state_dict(self._state0)
+        pol = self.ask()
+        res = env.rollout_episodes(pol, n_steps) if env._ar_mode else env.rollout_policy(pol, n_steps)
+        fit = self.fitness_of(res, n_steps)
+        out = self.tell(fit)
+        nan = torch.isnan(fit)
+        return {"generation": self.generation - 1, "fitness": fit, "grad": out["grad"],
+                "fitness_mean": fit.double().nanmean(),
+                "fitness_max": torch.where(nan, torch.full_like(fit, float("-inf")), fit).max(),
+                "fitness_min": torch.where(nan, torch.full_like(fit, float("inf")), fit).min()}
+
+    def mean_policy(self):
+        """The G = 1 policy of theta (a copy)."""
+        from .policy import MLPPolicy
+        seg = split_theta(self.theta.clone(), self.D, self.H, self.C, self.biases)
+        return MLPPolicy(seg["w2"], seg["b2"], seg["w1"], seg["b1"], act_limit=self.act_limit)
+
+    def state_dict(self) -> dict:
+        return {"theta": self.theta.detach().cpu().clone(), "seed": self.seed, "generation": self.generation,
+                "sigma": self.sigma, "lr": self.lr}
+
+    def load_state_dict(self, sd: dict) -> None:
+        import torch
+        t = torch.as_tensor(sd["theta"], dtype=torch.float32).reshape(-1)
+        if t.numel() != self.K:
+            raise ValueError(f"theta has {t.numel()} elements, expected {self.K}")
+        self.theta.copy_(t.to(self.theta.device))
+        self.seed, self.generation = int(sd["seed"]), int(sd["generation"])
+        self.sigma, self.lr = float(np.float32(sd["sigma"])), float(np.float32(sd["lr"]))
