@@ -30,8 +30,11 @@ NAMES = ["canonical4-mlp-5sets", "canonical4-lin-perwalker-c5-inf", "balance16-m
          "balance-g1-lin-4sets-inf", "canonical-lin-shared", "wide-mlp-shared", "discrete-mlp-4sets-c5"]
 
 
+COVER_NAMES = [c.name for c in pc.COVER]   # instance coverage: every (IN3D, NE, E8) of the AR policy kernel
+
+
 def case_of(name):
-    return next(c for c in pc.CASES if c.name == name)
+    return pc.case_of(name)
 
 
 @functools.lru_cache(maxsize=None)

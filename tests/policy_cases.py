@@ -55,6 +55,9 @@ def spec_of(kind):
         spec["vel"] = vel
         spec["steps"] = (np.arange(n) % 7).astype(np.int32)   # done (steps >= max_steps) at differing steps
         return spec
+    if kind in PASSES:   # instance coverage
+        kw = dict(PASSES[kind])
+        return canonical_walkers(kw.pop("N"), seed=33, **kw)
     raise KeyError(kind)
 
 
@@ -82,6 +85,20 @@ CASES = [
     Case("balance16-mid-mlp-8sets", "balance16", dict(BAL, conmid=1, midform=1), 20, H=24, C=2, G=8, L=1.0, seed=14,
          done=True, wpw=16),
 ]
+
+
+# Instance coverage of the resident policy kernels (one row per (IN3D, NE, E8) of walker_rollout_policy): 512 full standard
+# tiles, so that the launch reads the compact spring records (the 16-byte ones under WG_EDGE8=0), at every spring-pass
+# count: 8,192 walkers of M = 4, K = 4 (16 per wave, one pass) and 512 walkers of M = 64 (one per wave: 120, 150, 200
+# and 300 springs are 2, 3, 4 and 5 passes, the last on the NE 8 instance), in 2-D and 3-D, a shared linear policy.
+PASSES = {"ne1": dict(N=8192, M=4, K=4, A=2), "ne2": dict(N=512, M=64, K=120, A=8), "ne3": dict(N=512, M=64, K=150, A=8),
+          "ne4": dict(N=512, M=64, K=200, A=8), "ne8": dict(N=512, M=64, K=300, A=8)}
+COVER = [Case(f"{kind}-{2 + d}d", kind, dict(in3d=d), 4, H=0, C=kw["A"], G=1, L=1.0, seed=21 + 2 * i + d,
+              wpw=64 // kw["M"]) for i, (kind, kw) in enumerate(PASSES.items()) for d in (0, 1)]
+
+
+def case_of(name):
+    return next(c for c in CASES + COVER if c.name == name)
 
 
 def obs_dim(case):
@@ -118,7 +135,7 @@ def oracle_rollout(name):
     state's observation.  Every step's obs / reward / done / action and the final state, as numpy arrays (shared by the
     tests that need it, never modified)."""
     from oracle.oracle import Oracle
-    case = next(c for c in CASES if c.name == name)
+    case = case_of(name)
     pol = policy_of(case)
     orc = Oracle(spec_of(case.kind), case.params, n_threads=8)
     obs = orc.observe()["obs"]

@@ -259,8 +259,11 @@ def test_build_switches_are_diagnostic_only():
     timeline.  Both still compile for gfx950 (device code only, together)."""
     import re
     import subprocess
-    src = os.path.join(ROOT, "walker_gym_amd", "csrc", "walker_hip.hip")
-    text = open(src).read()
+    csrc = os.path.join(ROOT, "walker_gym_amd", "csrc")
+    src = os.path.join(csrc, "walker_hip.hip")
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert {"walker_hip.hip", "es_hip.hip", "walker_internal.h"} <= set(sources)
+    text = "".join(open(os.path.join(csrc, f)).read() for f in sources)   # every unit and internal header
     switches = re.findall(r"#ifndef (WG_\w+)", text)
     assert switches == ["WG_ABLATE"], switches
     assert set(re.findall(r"#ifdef (WG_\w+)", text)) == {"WG_STAMPS"}

@@ -35,6 +35,14 @@ def _need_gpu():
         pytest.skip("no ROCm GPU")
 
 
+# Instance coverage: 512 full standard tiles (the compact records are read) at every spring-pass count: 8,192 walkers of
+# M = 4, K = 4 (16 per wave, one pass) and 512 walkers of M = 64 (one per wave: 120, 150, 200, 300 springs are 2, 3, 4
+# and 5 passes, the last on the NE 8 instance), each in 2-D and 3-D
+PASSES = [(1, dict(N=8192, M=4, K=4, A=2)), (2, dict(N=512, M=64, K=120, A=8)), (3, dict(N=512, M=64, K=150, A=8)),
+          (4, dict(N=512, M=64, K=200, A=8)), (8, dict(N=512, M=64, K=300, A=8))]
+COVER = [f"ne{ne}-{d}d" for ne, _ in PASSES for d in (2, 3)]
+
+
 # name -> (spec builder, in3d, walkers per wave the lean launch uses)
 def _specs():
     from walker_gym_amd.synthetic import canonical_walkers
@@ -45,6 +53,8 @@ def _specs():
         "balance8195": (lambda: balance_spec(8195), 0, 16),
         "balance2052": (lambda: balance_spec(2052), 0, 4),
         "box3d4099": (lambda: box_spec(4099), 1, 8),
+        **{f"ne{ne}-{2 + d}d": (functools.partial(canonical_walkers, seed=3, **kw), d, 64 // kw["M"])
+           for ne, kw in PASSES for d in (0, 1)},
     }
 
 
@@ -254,6 +264,18 @@ def test_captured_graph_against_composed_oracle():
 @pytest.mark.parametrize("name", ["canonical2051", "balance2052"])
 def test_resident_rollout_falls_back_to_steps(name):
     """Case 3: rollout(resident=True) with auto-reset runs as per-step launches and equals the step loop's reference."""
+    _resident_rollout(name)
+
+
+@pytest.mark.parametrize("edge8", [True, False], ids=["compact", "16-byte"])
+@pytest.mark.parametrize("name", COVER)
+def test_every_auto_reset_instance(name, edge8, monkeypatch):
+    """The AR instance of the step kernel and of the resident kernel at every (IN3D, NE, E8): case 1 and case 3."""
+    _step_loop(name, monkeypatch, edge8=edge8)
+    _resident_rollout(name)
+
+
+def _resident_rollout(name):
     import torch
     ref = _reference(name)
     env, cfg = _env(name)

@@ -233,11 +233,15 @@ def test_run_two_ranges_nonfinite(monkeypatch, n, compact):
 
 @pytest.mark.parametrize("n,compact", [(8, False), (N_CANON, True)])
 def test_resident_rollout(monkeypatch, n, compact):
+    _resident_case(monkeypatch, _canonical(n), dict(in3d=1), compact)
+
+
+def _resident_case(monkeypatch, spec, params, compact):
     import torch
     from oracle.oracle import Oracle
     from walker_gym_amd.batched_env import BatchedPhysicsEnv
-    spec, params = _canonical(n), dict(in3d=1)
-    acts = np.random.default_rng(4).uniform(-1, 1, (3, n, 8)).astype(np.float32)
+    n = len(spec["mass_off"]) - 1
+    acts = np.random.default_rng(4).uniform(-1, 1, (3, n, int(np.max(spec["n_muscles"])))).astype(np.float32)
     orc = Oracle(spec, params, n_threads=8)
     refs = [orc.step(acts[t]) for t in range(3)]
     outs = {}
@@ -258,3 +262,41 @@ def test_resident_rollout(monkeypatch, n, compact):
         outs[edge8] = st
     for k in STATE:
         _bits(outs["1"][k], outs["0"][k], f"{k}: compact vs 16-byte records")
+
+
+# ---- every (IN3D, NE, E8, FIX) instance of the step and resident kernels without auto-reset.  The compact records and
+# the fixed-parameter instance need 512 full standard tiles: 8,192 walkers of M = 4, K = 4 (16 per wave, 64 springs: one
+# pass) and 512 walkers of M = 64 (one per wave, so K alone sets the passes: 120, 150, 200 and 300 springs are 2, 3, 4
+# and 5 passes, the last on the NE 8 instance).  Each case runs the default path (FIX up to four passes, the generic
+# compact instance at NE 8) and WG_EDGE8=0 (the 16-byte records) in _step_case / _resident_case, then the generic
+# compact instance under WG_FIX=0.
+PASSES = [(1, dict(N=8192, M=4, K=4, A=2)), (2, dict(N=512, M=64, K=120, A=8)), (3, dict(N=512, M=64, K=150, A=8)),
+          (4, dict(N=512, M=64, K=200, A=8)), (8, dict(N=512, M=64, K=300, A=8))]
+
+
+def _passes_spec(shape):
+    kw = dict(shape)
+    return _canonical(kw.pop("N"), **kw)
+
+
+@pytest.mark.parametrize("in3d", [0, 1])
+@pytest.mark.parametrize("ne,shape", PASSES, ids=[f"ne{ne}" for ne, _ in PASSES])
+def test_every_step_instance(monkeypatch, in3d, ne, shape):
+    from walker_gym_amd import _lib
+    lib, spec = _lib.load(), _passes_spec(shape)
+    n0 = lib.wg_fix_launches()
+    env = _step_case(monkeypatch, spec, dict(in3d=in3d), 2, True)
+    geo = env.launch_geometry()
+    wpw = geo["walkers_per_block"] // (geo["threads"] // 64)
+    assert (wpw * env.batch.K + 63) // 64 == (ne if ne <= 4 else 5)
+    n1 = lib.wg_fix_launches()
+    assert n1 - n0 == (2 * env._step_lanes() if ne <= 4 else 0)   # the default arm's two steps: the FIX instance
+    monkeypatch.setenv("WG_FIX", "0")
+    _step_case(monkeypatch, spec, dict(in3d=in3d), 2, True)
+    assert lib.wg_fix_launches() == n1
+
+
+@pytest.mark.parametrize("in3d", [0, 1])
+@pytest.mark.parametrize("ne,shape", PASSES, ids=[f"ne{ne}" for ne, _ in PASSES])
+def test_every_resident_instance(monkeypatch, in3d, ne, shape):
+    _resident_case(monkeypatch, _passes_spec(shape), dict(in3d=in3d), True)

@@ -107,6 +107,27 @@ def test_fused_equals_reference_engine(case):
     assert same == tot, f"{tot - same} of {tot} bytes differ from the reference engine"
 
 
+@pytest.mark.parametrize("edge8", [True, False], ids=["compact", "16-byte"])
+@pytest.mark.parametrize("case", pc.COVER, ids=lambda c: c.name)
+def test_every_instance_equals_reference_engine(case, edge8, monkeypatch):
+    """walker_rollout_policy at every (IN3D, NE, E8): the fused rollout's every step and final state, bit for bit."""
+    import torch
+    if not edge8:
+        monkeypatch.setenv("WG_EDGE8", "0")
+    env = _env(case)
+    geo = env.launch_geometry()
+    assert geo["walkers_per_block"] * 64 // geo["threads"] == case.wpw, geo
+    buf = _buffers(env, case.T, case.C)
+    env.rollout_policy(pc.policy_of(case, "cuda:0"), case.T, **buf)
+    torch.cuda.synchronize()
+    fused = dict({k[:-4]: v.cpu().numpy() for k, v in buf.items()}, **_state(env))
+    ref = pc.oracle_rollout(case.name)
+    for k in ("action", "obs", "reward", "done") + STATE:
+        a, b = np.ascontiguousarray(fused[k]), np.ascontiguousarray(ref[k]).reshape(fused[k].shape)
+        assert a.dtype == b.dtype or k in ("contact", "done"), k
+        assert np.array_equal(a.view(np.uint8), b.astype(a.dtype).view(np.uint8)), k
+
+
 @CASES
 def test_no_per_step_buffers(case):
     fused, bare, _ = _runs(case.name)

@@ -108,6 +108,48 @@ def test_wave_kernel_dense_walkers_vs_oracle():
     assert np.array_equal(env.muscle_x.cpu().numpy(), orc.mx)
 
 
+def _wave_spec(ne):
+    """A small mixed batch whose maxima (M, K) give `ne` spring passes of a wave tile: max(ceil(K / 64), ceil(K / M)),
+    five passes on the NE 8 instance."""
+    from walker_gym_amd.synthetic import canonical_walkers, ragged_walkers
+    from walker_gym_amd.walker import concat_specs
+    small = ragged_walkers(20, seed=72, mmin=3, mmax=12)   # K <= 2 M: at most two passes
+    return {1: lambda: concat_specs([canonical_walkers(6, seed=71, M=4, K=4, A=2), canonical_walkers(5, seed=73, M=4, K=4, A=1)]),
+            2: lambda: concat_specs([canonical_walkers(4, seed=71, M=16, K=24, A=4), small]),
+            3: lambda: concat_specs([canonical_walkers(4, seed=71, M=16, K=40, A=8), small]),
+            4: lambda: concat_specs([canonical_walkers(3, seed=71, M=64, K=200, A=12), small]),
+            8: lambda: concat_specs([canonical_walkers(3, seed=71, M=64, K=300, A=12), small])}[ne]()
+
+
+@pytest.mark.parametrize("in3d", [0, 1])
+@pytest.mark.parametrize("ne", [1, 2, 3, 4, 8])
+def test_every_wave_instance_vs_oracle(ne, in3d):
+    """walker_step_waves at every (IN3D, NE), against the oracle in the caller's order."""
+    import torch
+    from oracle.oracle import Oracle
+    from walker_gym_amd import _lib
+    from walker_gym_amd.batched_env import BatchedPhysicsEnv
+    spec = _wave_spec(ne)
+    N = len(spec["mass_off"]) - 1
+    M, K = int(np.diff(spec["mass_off"]).max()), int(np.diff(spec["edge_off"]).max())
+    assert _lib.load().wg_wave_edge_passes(M, K) == ne
+    A = int(np.max(spec["n_muscles"]))
+    acts = np.random.default_rng(74).uniform(-1, 1, (4, N, A)).astype(np.float32)
+    env = BatchedPhysicsEnv(spec, device="cuda:0", in3d=in3d)
+    assert env.batch.ragged_kind == 2
+    orc = Oracle(spec, dict(in3d=in3d))
+    for t in range(4):
+        obs, rew, done, info = env.step(acts[t])
+        ref = orc.step(acts[t])
+    torch.cuda.synchronize()
+    assert np.array_equal(env.pos.cpu().numpy().view(np.uint32), orc.pos.view(np.uint32))
+    assert np.array_equal(env.vel.cpu().numpy().view(np.uint32), orc.vel.view(np.uint32))
+    assert np.array_equal(obs.cpu().numpy().view(np.uint32), ref["obs"].view(np.uint32))
+    assert np.array_equal(rew.cpu().numpy().view(np.uint32), ref["reward"].view(np.uint32))
+    assert np.array_equal(done.cpu().numpy().astype(np.uint8), ref["done"])
+    assert np.array_equal(env.muscle_x.cpu().numpy(), orc.mx)
+
+
 @pytest.mark.parametrize("pair_mode", [7, 31, "4_subset"])
 @pytest.mark.parametrize("case", ["ragged", "uniform_M13", "uniform_M100", "uniform_M100_wide"])
 def test_pair_forces_workgroup_kernel_vs_oracle(case, pair_mode):

@@ -151,6 +151,23 @@ def test_fused_equals_composed_oracle_16_byte_records(monkeypatch):
     _check_against_reference(dict(_host(buf), stats=_stats(res), **_state(env)), ec.reference(name))
 
 
+@pytest.mark.parametrize("edge8", [True, False], ids=["compact", "16-byte"])
+@pytest.mark.parametrize("name", ec.COVER_NAMES)
+def test_every_instance_equals_composed_oracle(name, edge8, monkeypatch):
+    """The AR instance of walker_rollout_policy at every (IN3D, NE, E8), as the test above."""
+    import torch
+    if not edge8:
+        monkeypatch.setenv("WG_EDGE8", "0")
+    case = ec.case_of(name)
+    env = _env(name)
+    geo = env.launch_geometry()
+    assert geo["walkers_per_block"] * 64 // geo["threads"] == case.wpw, geo
+    buf = _buffers(env, T, case.C)
+    res = env.rollout_episodes(pc.policy_of(case, "cuda:0"), T, episode_slots=SLOTS, **buf)
+    torch.cuda.synchronize()
+    _check_against_reference(dict(_host(buf), stats=_stats(res), **_state(env)), ec.reference(name))
+
+
 @CASES
 def test_fused_equals_device_step_loop(name):
     fused, _, loop = _runs(name)

@@ -11,6 +11,7 @@ and one performance flag: -mllvm -amdgpu-kernarg-preload-count=10 (walker_step_l
 from __future__ import annotations
 
 import argparse
+import glob
 import os
 import shutil
 import subprocess
@@ -21,7 +22,6 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "walker_hip.hip")
 ES_SRC = os.path.join(HERE, "csrc", "es_hip.hip")   # wg_es_*: a unit of its own, the same flags, the same library
 HDR = os.path.join(ROOT, "include", "walker_hip.h")
-POWF2 = os.path.join(HERE, "csrc", "powf2.h")
 OUT = os.path.join(HERE, "libwalker_hip.so")
 ARCH = os.environ.get("WALKER_HIP_ARCH", "gfx950")
 
@@ -48,7 +48,9 @@ def needs_build(out: str = OUT) -> bool:
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(p) > t for p in (SRC, ES_SRC, HDR, POWF2, __file__))
+    csrc = os.path.join(HERE, "csrc")
+    inputs = [*glob.glob(os.path.join(csrc, "*.hip")), *glob.glob(os.path.join(csrc, "*.h")), HDR, __file__]
+    return any(os.path.getmtime(p) > t for p in inputs)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

@@ -16,24 +16,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 
 #include "walker_hip.h"
+#include "walker_internal.h"   // wg_fail, wg_launched: the refusals here go to the library's one error message
 
 namespace {
-
-// walker_hip.hip owns the library's thread-local error message (512 bytes behind wg_last_error()); the refusals here
-// are written into the same buffer.
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(const_cast<char *>(wg_last_error()), 256, fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 constexpr int ES_THREADS = 256;
 constexpr int ES_CHUNK = 256;             // pairs per float64 partial sum (the contract's chunk)
@@ -142,33 +130,28 @@ __global__ __launch_bounds__(ES_THREADS) void es_update_tail(const double *__res
 
 // The checks that wg_es_perturb and wg_es_update share; fills the layout and K.
 int es_check(const wg_es *es, int32_t first_pair, int32_t n_pairs, const char *who, EsLayout *lay, int64_t *K) {
-    if (!es) return fail(WG_EINVAL, "%s: null es", who);
-    if (!es->theta) return fail(WG_EINVAL, "%s: null theta", who);
-    if (es->obs_dim < 1) return fail(WG_EINVAL, "%s: obs_dim %d < 1", who, es->obs_dim);
-    if (es->act_dim < 1) return fail(WG_EINVAL, "%s: act_dim %d < 1", who, es->act_dim);
-    if (es->hidden < 0 || es->hidden > 256) return fail(WG_EINVAL, "%s: hidden %d outside 0..256", who, es->hidden);
-    if (es->hidden > 0 && !es->w1) return fail(WG_EINVAL, "%s: hidden %d with a null w1", who, es->hidden);
-    if (es->hidden == 0 && es->b1) return fail(WG_EINVAL, "%s: b1 without a hidden layer", who);
-    if (!es->w2) return fail(WG_EINVAL, "%s: null w2", who);
+    if (!es) return wg_fail(WG_EINVAL, "%s: null es", who);
+    if (!es->theta) return wg_fail(WG_EINVAL, "%s: null theta", who);
+    if (es->obs_dim < 1) return wg_fail(WG_EINVAL, "%s: obs_dim %d < 1", who, es->obs_dim);
+    if (es->act_dim < 1) return wg_fail(WG_EINVAL, "%s: act_dim %d < 1", who, es->act_dim);
+    if (es->hidden < 0 || es->hidden > 256) return wg_fail(WG_EINVAL, "%s: hidden %d outside 0..256", who, es->hidden);
+    if (es->hidden > 0 && !es->w1) return wg_fail(WG_EINVAL, "%s: hidden %d with a null w1", who, es->hidden);
+    if (es->hidden == 0 && es->b1) return wg_fail(WG_EINVAL, "%s: b1 without a hidden layer", who);
+    if (!es->w2) return wg_fail(WG_EINVAL, "%s: null w2", who);
     if (es->n_sets < 2 || (es->n_sets & 1))
-        return fail(WG_EINVAL, "%s: n_sets %d must be even and >= 2 (antithetic pairs)", who, es->n_sets);
-    if (n_pairs < 1) return fail(WG_EINVAL, "%s: n_pairs %d < 1", who, n_pairs);
+        return wg_fail(WG_EINVAL, "%s: n_sets %d must be even and >= 2 (antithetic pairs)", who, es->n_sets);
+    if (n_pairs < 1) return wg_fail(WG_EINVAL, "%s: n_pairs %d < 1", who, n_pairs);
     if (first_pair < 0 || first_pair > es->n_sets / 2 - n_pairs)
-        return fail(WG_EINVAL, "%s: pairs %d .. %lld outside 0 .. %d", who, first_pair,
+        return wg_fail(WG_EINVAL, "%s: pairs %d .. %lld outside 0 .. %d", who, first_pair,
                     (long long)first_pair + n_pairs, es->n_sets / 2);
-    if (!std::isfinite(es->sigma) || !(es->sigma > 0.0f)) return fail(WG_EINVAL, "%s: sigma must be finite and > 0", who);
+    if (!std::isfinite(es->sigma) || !(es->sigma > 0.0f)) return wg_fail(WG_EINVAL, "%s: sigma must be finite and > 0", who);
     const int64_t H = es->hidden, D = es->obs_dim, C = es->act_dim;
     const int64_t n_w1 = D * H, n_b1 = es->b1 ? H : 0, n_w2 = (H > 0 ? H : D) * C, n_b2 = es->b2 ? C : 0;
     *K = n_w1 + n_b1 + n_w2 + n_b2;
-    if (*K > ES_MAX_K) return fail(WG_EINVAL, "%s: %lld parameters (at most 2^23)", who, (long long)*K);
+    if (*K > ES_MAX_K) return wg_fail(WG_EINVAL, "%s: %lld parameters (at most 2^23)", who, (long long)*K);
     lay->n_w1 = (int32_t)n_w1; lay->n_b1 = (int32_t)n_b1; lay->n_w2 = (int32_t)n_w2; lay->n_b2 = (int32_t)n_b2;
     lay->w1 = es->w1; lay->b1 = es->b1; lay->w2 = es->w2; lay->b2 = es->b2;
     return 0;
-}
-
-int launched(const char *who) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(WG_EHIP, "%s: launch failed: %s", who, hipGetErrorString(e));
 }
 
 }  // namespace
@@ -186,7 +169,7 @@ int wg_es_perturb(const wg_es *es, int32_t first_pair, int32_t n_pairs, hipStrea
     es_perturb<<<grid, ES_THREADS, 0, stream>>>(lay, es->theta, K, ppb, (uint32_t)(es->seed & 0xffffffffu),
                                                (uint32_t)(es->seed >> 32), es->generation, es->sigma, first_pair,
                                                n_pairs);
-    return launched("wg_es_perturb");
+    return wg_launched("wg_es_perturb: launch");
 }
 
 int wg_es_update(const wg_es *es, int32_t first_pair, int32_t n_pairs, const float *util, double scale, float lr,
@@ -194,19 +177,19 @@ int wg_es_update(const wg_es *es, int32_t first_pair, int32_t n_pairs, const flo
     EsLayout lay;
     int64_t K64;
     if (const int rc = es_check(es, first_pair, n_pairs, "wg_es_update", &lay, &K64)) return rc;
-    if (!util) return fail(WG_EINVAL, "wg_es_update: null util");
-    if (!workspace) return fail(WG_EINVAL, "wg_es_update: null workspace");
-    if (!std::isfinite(scale)) return fail(WG_EINVAL, "wg_es_update: scale is not finite");
-    if (!std::isfinite(lr)) return fail(WG_EINVAL, "wg_es_update: lr is not finite");
-    if (!grad && !theta_out) return fail(WG_EINVAL, "wg_es_update: grad and theta_out are both null");
+    if (!util) return wg_fail(WG_EINVAL, "wg_es_update: null util");
+    if (!workspace) return wg_fail(WG_EINVAL, "wg_es_update: null workspace");
+    if (!std::isfinite(scale)) return wg_fail(WG_EINVAL, "wg_es_update: scale is not finite");
+    if (!std::isfinite(lr)) return wg_fail(WG_EINVAL, "wg_es_update: lr is not finite");
+    if (!grad && !theta_out) return wg_fail(WG_EINVAL, "wg_es_update: grad and theta_out are both null");
     const int32_t K = (int32_t)K64;
     const int32_t n_chunks = (n_pairs + ES_CHUNK - 1) / ES_CHUNK, kb = (K + ES_THREADS - 1) / ES_THREADS;
     es_update_partial<<<dim3(n_chunks, kb), ES_THREADS, 0, stream>>>(
         util, workspace, K, (uint32_t)(es->seed & 0xffffffffu), (uint32_t)(es->seed >> 32), es->generation, first_pair,
         n_pairs);
-    if (const int rc = launched("wg_es_update (partial sums)")) return rc;
+    if (const int rc = wg_launched("wg_es_update (partial sums): launch")) return rc;
     es_update_tail<<<kb, ES_THREADS, 0, stream>>>(workspace, es->theta, grad, theta_out, K, n_chunks, scale, lr);
-    return launched("wg_es_update (tail)");
+    return wg_launched("wg_es_update (tail): launch");
 }
 
 }  // extern "C"

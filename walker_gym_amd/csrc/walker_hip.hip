@@ -35,19 +35,22 @@
 
 #include "walker_hip.h"
 #include "powf2.h"
+#include "walker_internal.h"
 
 namespace {
-
 thread_local char g_err[512] = "";
+}
 
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char *fmt, ...) {
+// the library's one error message (walker_internal.h): every refusal of either translation unit goes through here
+int wg_fail(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
     return code;
 }
+
+namespace {
 
 constexpr int WG_MAX_M = 1024;      // numpy pairwise recursion unrolled 3 levels (pw_tree<3>)
 constexpr double CONFIG_R = 16e-36;  // gym/engine.py:9 Config.r (distance clamp, Python float)
@@ -3605,22 +3608,22 @@ constexpr int RAG_P = 256, RAG_E = 512, RAG_U = 256, RAG_W = 64;
 constexpr int LDS_LIMIT = 160 * 1024;
 
 int validate(const wg_batch *b) {
-    if (!b) return fail(WG_EINVAL, "null batch");
+    if (!b) return wg_fail(WG_EINVAL, "null batch");
     if (b->N < 0 || b->M < 1 || b->K < 0 || b->A < 0 || b->A > b->K)
-        return fail(WG_EINVAL, "bad sizes N=%d M=%d K=%d A=%d", b->N, b->M, b->K, b->A);
-    if (2 * b->K > 65535) return fail(WG_ERANGE, "K=%d exceeds the u16 incidence encoding", b->K);
-    if (b->M > WG_MAX_M) return fail(WG_ERANGE, "M=%d > %d masses per walker", b->M, WG_MAX_M);
+        return wg_fail(WG_EINVAL, "bad sizes N=%d M=%d K=%d A=%d", b->N, b->M, b->K, b->A);
+    if (2 * b->K > 65535) return wg_fail(WG_ERANGE, "K=%d exceeds the u16 incidence encoding", b->K);
+    if (b->M > WG_MAX_M) return wg_fail(WG_ERANGE, "M=%d > %d masses per walker", b->M, WG_MAX_M);
     if (!b->pos || !b->vel || !b->acc || !b->mass || !b->steps || !b->muscle_x)
-        return fail(WG_EINVAL, "missing state pointer");
-    if (b->K > 0 && (!b->edges || !b->inc || !b->inc_off)) return fail(WG_EINVAL, "missing edge pointer");
-    if (b->M > 32767) return fail(WG_ERANGE, "M=%d exceeds the 15-bit edge endpoint encoding", b->M);
-    if (!b->inc_off) return fail(WG_EINVAL, "missing inc_off");
-    if (b->ragged < 0 || b->ragged > 2) return fail(WG_EINVAL, "ragged must be 0, 1 or 2");
+        return wg_fail(WG_EINVAL, "missing state pointer");
+    if (b->K > 0 && (!b->edges || !b->inc || !b->inc_off)) return wg_fail(WG_EINVAL, "missing edge pointer");
+    if (b->M > 32767) return wg_fail(WG_ERANGE, "M=%d exceeds the 15-bit edge endpoint encoding", b->M);
+    if (!b->inc_off) return wg_fail(WG_EINVAL, "missing inc_off");
+    if (b->ragged < 0 || b->ragged > 2) return wg_fail(WG_EINVAL, "ragged must be 0, 1 or 2");
     if (b->ragged && (!b->mass_off || !b->edge_off || !b->muscle_off))
-        return fail(WG_EINVAL, "ragged batch without offsets");
-    if (!b->ragged && b->row) return fail(WG_EINVAL, "row (a walker permutation) is for ragged batches only");
+        return wg_fail(WG_EINVAL, "ragged batch without offsets");
+    if (!b->ragged && b->row) return wg_fail(WG_EINVAL, "row (a walker permutation) is for ragged batches only");
     if (b->ragged == 2 && !wave_passes(b->M, b->K))
-        return fail(WG_EINVAL, "ragged = 2 (wave tiles) needs M <= 64 and at most 8 spring passes (M=%d K=%d)", b->M, b->K);
+        return wg_fail(WG_EINVAL, "ragged = 2 (wave tiles) needs M <= 64 and at most 8 spring passes (M=%d K=%d)", b->M, b->K);
     return 0;
 }
 
@@ -3678,12 +3681,10 @@ int launch(const wg_batch *b, const KParams &kp, const float *action, int cols, 
     // (+ the static 512 B of the powf tables in LDS)
     const int lds_static = (int)(sizeof(s_pw_log2) + sizeof(s_pw_exp2));
     if (g.lds + lds_static > LDS_LIMIT)
-        return fail(WG_ERANGE, "workgroup needs %d B of LDS (> 160 KiB)", g.lds + lds_static);
+        return wg_fail(WG_ERANGE, "workgroup needs %d B of LDS (> 160 KiB)", g.lds + lds_static);
     WG_KLAUNCH((walker_step_kernel<STEP, RAGGED, IN3D, PWD, SHFL>), dim3(blocks), dim3(g.threads), (uint32_t)g.lds, stream,
                *b, kp, action, cols, astride, kout(o), plan, g);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WG_EHIP, "launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return wg_launched("launch");
 }
 
 // register (shuffle) reductions: every walker's masses are adjacent lanes of one wave
@@ -3731,6 +3732,9 @@ bool u32_bytes(const wg_batch *b) {
 // and their observation rows as 32-bit byte offsets (WG_ST)
 bool obs_u32(const wg_batch *b, int obs_stride) { return (int64_t)b->N * std::max(obs_stride, 1) * 4 < (1ll << 32); }
 
+// spring passes of a lean wave tile: ceil(wpw * K / 64), at most 8 (lean_geo)
+int lean_passes(const LeanGeo &g, const wg_batch *b) { return (g.wpw * b->K + 63) / 64; }
+
 bool lean_geo(const wg_batch *b, int obs_stride, LeanGeo *out, int spring_mode = 0) {
     const int M = b->M;
     if (b->ragged || M < 4 || M > 64 || (64 % M) != 0 || b->K < 1 || !lean_enabled() || (WG_ABLATE & 128)) return false;
@@ -3749,7 +3753,7 @@ bool lean_geo(const wg_batch *b, int obs_stride, LeanGeo *out, int spring_mode =
     if (wcap > 0 && wcap < g.wpw) g.wpw = wcap;
     g.lgM = 0;
     while ((1 << g.lgM) < M) g.lgM++;
-    if ((g.wpw * b->K + 63) / 64 > 8 || g.wpw * b->A > 64) return false;
+    if (lean_passes(g, b) > 8 || g.wpw * b->A > 64) return false;
     // waves per workgroup: 4 (one workgroup per four tiles) unless the batch has no more tiles than the chip has SIMDs,
     // where one wave per workgroup spreads the latency-bound step over twice the CUs (4,096 Balance-v0 walkers: 5.45
     // against 5.60 us, 65,536 canonical: 44.31 against 44.01; profiles/r04m_ab_*_wpb.json); WG_LEAN_WAVES overrides
@@ -3766,13 +3770,50 @@ bool lean_geo(const wg_batch *b, int obs_stride, LeanGeo *out, int spring_mode =
     g.invK = 1.f / (float)b->K;
     g.invA = 1.f / (float)std::max(1, b->A);
     g.invM = 1.f / (float)M;
-    g.nblk = (b->N + g.wpb * g.wpw - 1) / (g.wpb * g.wpw);   // = lean_blocks
+    g.nblk = (b->N + g.wpb * g.wpw - 1) / (g.wpb * g.wpw);   // the grid of a lean launch: one tile per wave
     *out = g;
     return true;
 }
 
-// grid of a lean launch: one tile (64 / M walkers) per wave
-int lean_blocks(const wg_batch *b, const LeanGeo &g) { return (b->N + g.wpb * g.wpw - 1) / (g.wpb * g.wpw); }
+// walker_step_lean1's preloaded word: bits 0..29 the workgroup count, bit 30 the XCD-order flag (WG_XCD bit 1), bit 31
+// the load-phase priority flag (WG_LEAN_PRIO)
+int lean1_nblkx(const LeanGeo &g, const KParams &kp) {
+    return (int)((unsigned)g.nblk | ((unsigned)(kp.xcd & 2) << 29) | ((unsigned)(kp.prio != 0) << 31));
+}
+
+// ---- instance selection: the runtime (in3d, passes, compact records) of a launch as compile-time tags, in one place.
+// A launch site is one call whose generic lambda names its kernel with the tags' values; `if constexpr` in the lambda
+// keeps the instances nobody launches (NE 1 of walker_step_lean, FIX outside E8 and NE 1-4) uninstantiated.
+template <class F>
+void with_flag(bool v, F &&f) {
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
+}
+// the pass count rounded up to an instantiated NE: 1, 2, 3, 4, 8
+template <class F>
+void with_passes(int ne, F &&f) {
+    if (ne <= 1) f(std::integral_constant<int, 1>{});
+    else if (ne == 2) f(std::integral_constant<int, 2>{});
+    else if (ne == 3) f(std::integral_constant<int, 3>{});
+    else if (ne == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
+}
+template <class F>
+void with_instance(bool in3d, int ne, F &&f) {   // f(IN3D, NE)
+    with_flag(in3d, [&](auto d3) { with_passes(ne, [&](auto n) { f(d3, n); }); });
+}
+template <class F>
+void with_instance(bool in3d, int ne, bool e8, F &&f) {   // f(IN3D, NE, E8)
+    with_instance(in3d, ne, [&](auto d3, auto n) { with_flag(e8, [&](auto c8) { f(d3, n, c8); }); });
+}
+
+// The caller's actions: cols values in row w of step s at ptr[s * step + w * stride]; ptr NULL = none
+struct Actions {
+    const float *ptr;
+    int32_t cols, stride;
+    int64_t step;
+    Actions at(int s) const { return Actions{ptr ? ptr + s * step : nullptr, cols, stride, step}; }
+};
 
 // The fixed-parameter instance (FIX) runs a launch whose every tile is full and whose batch, parameters, actions and
 // outputs are the default path's: compact records in 1..4 passes, no auto-reset, continuous actions for every muscle,
@@ -3780,8 +3821,8 @@ int lean_blocks(const wg_batch *b, const LeanGeo &g) { return (b->N + g.wpb * g.
 // per-step output but the optional steps asked for.  Anything else takes the generic instance, as a whole launch (a
 // partial last tile too).  WG_FIX=0 (read on every launch, like WG_EDGE8) forces the generic instance: the control arm
 // and the tests' cross-check.
-bool lean_fix_ok(const wg_batch *b, const KParams &kp, const float *a, int cols, int astride, const wg_outputs &o,
-                 const LeanGeo &g, bool e8, int ne, int ar_mode) {
+bool lean_fix_ok(const wg_batch *b, const KParams &kp, const Actions &a, const wg_outputs &o, const LeanGeo &g, bool e8,
+                 int ne, int ar_mode) {
 #ifdef WG_STAMPS
     return false;
 #endif
@@ -3792,7 +3833,7 @@ bool lean_fix_ok(const wg_batch *b, const KParams &kp, const float *a, int cols,
         return u == 0x3f800000u;
     };
     return e8 && ne >= 1 && ne <= 4 && ar_mode == 0 && b->N % g.wpw == 0 && g.wpw * b->M == 64 &&
-           b->A >= 1 && a != nullptr && cols >= b->A && astride >= b->A && kp.action_mode == 0 &&
+           b->A >= 1 && a.ptr != nullptr && a.cols >= b->A && a.stride >= b->A && kp.action_mode == 0 &&
            kp.pair_mode == 0 && !b->pinned && !b->radius && kp.integrator != 2 && kp.midform == 1 && kp.conmid == 0 &&
            one(kp.pk) && one(kp.vk) && one(kp.ak) && one(kp.mk) &&
            o.obs && o.reward && o.done && o.centroid && o.energy;
@@ -3800,124 +3841,92 @@ bool lean_fix_ok(const wg_batch *b, const KParams &kp, const float *a, int cols,
 // launches that took the fixed-parameter instance, this process (wg_fix_launches: the tests read which instance ran)
 std::atomic<long long> g_fix_launches{0};
 
-// ar_mode (wg_params.auto_reset) != 0: the AR instances (the auto-reset tail, ABI 16)
-int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const float *a, int cols, int astride,
-                const wg_outputs &o, const LeanGeo &g, hipStream_t st, int ar_mode = 0) {
-    const int blocks = lean_blocks(b, g);
-    const int ne = (g.wpw * b->K + 63) / 64;
+// One step of a uniform batch on the lean kernels.  ar_mode (wg_params.auto_reset) != 0: the AR instances (the auto-reset
+// tail, ABI 16); a launch that lean_fix_ok admits: the FIX instances.  One spring pass is walker_step_lean1's, with its
+// leading arguments preloaded (the compact records take the spring records' slot).
+int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const Actions &a, const wg_outputs &o, const LeanGeo &g,
+                hipStream_t st, int ar_mode = 0) {
+    const int ne = lean_passes(g, b);
     // WG_LDS_PAD (diagnostic): extra LDS bytes per workgroup, to measure the kernel at lower occupancy
-    const int lds = g.wpb * g.slice + std::max(0, env_int("WG_LDS_PAD", 0));
+    const uint32_t lds = (uint32_t)(g.wpb * g.slice + std::max(0, env_int("WG_LDS_PAD", 0)));
     const bool e8 = use_edge8(b, g);
-    if (lean_fix_ok(b, kp, a, cols, astride, o, g, e8, ne, ar_mode)) {   // (E8, no auto-reset)
-#define WG_LAUNCH_FIX(D3, NE_)                                                                                   \
-    WG_KLAUNCH((walker_step_lean<D3, NE_, true, false, true>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st, \
-               kbatch15(b), kp, a, cols, astride, kout(o), g, KNoReset{})
-#define WG_LAUNCH_FIX1(D3)                                                                                       \
-    WG_KLAUNCH((walker_step_lean1<D3, true, false, true>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st,    \
-               b->pos, b->vel, static_cast<const void *>(b->edges8), b->inc, b->N, b->M, b->K, g.wpw, g.wpb,     \
-               (int)((unsigned)g.nblk | ((unsigned)(kp.xcd & 2) << 29) | ((unsigned)(kp.prio != 0) << 31)), *b,  \
-               kp, a, cols, astride, kout(o), g, KNoReset{})
-        if (in3d) {
-            if (ne == 1) WG_LAUNCH_FIX1(true);
-            else if (ne == 2) WG_LAUNCH_FIX(true, 2);
-            else if (ne == 3) WG_LAUNCH_FIX(true, 3);
-            else WG_LAUNCH_FIX(true, 4);
+    const bool fix = lean_fix_ok(b, kp, a, o, g, e8, ne, ar_mode);   // (E8, 1..4 passes, no auto-reset)
+    const dim3 grid(g.nblk), block(64 * g.wpb);
+    with_instance(in3d, ne, e8, [&](auto d3, auto n, auto c8) {
+        constexpr bool D3 = decltype(d3)::value, E8 = decltype(c8)::value;
+        constexpr int NE = decltype(n)::value;
+        if constexpr (NE == 1) {
+            const void *recs = E8 ? static_cast<const void *>(b->edges8) : static_cast<const void *>(b->edges);
+            auto go = [&](auto kernel, auto reset) {
+                WG_KLAUNCH(kernel, grid, block, lds, st, b->pos, b->vel, recs, b->inc, b->N, b->M, b->K, g.wpw, g.wpb,
+                           lean1_nblkx(g, kp), *b, kp, a.ptr, a.cols, a.stride, kout(o), g, reset);
+            };
+            if constexpr (E8) {
+                if (fix) return go(walker_step_lean1<D3, true, false, true>, KNoReset{});
+            }
+            if (ar_mode) go(walker_step_lean1<D3, E8, true>, kreset(o, ar_mode));
+            else go(walker_step_lean1<D3, E8>, KNoReset{});
         } else {
-            if (ne == 1) WG_LAUNCH_FIX1(false);
-            else if (ne == 2) WG_LAUNCH_FIX(false, 2);
-            else if (ne == 3) WG_LAUNCH_FIX(false, 3);
-            else WG_LAUNCH_FIX(false, 4);
+            auto go = [&](auto kernel, const auto &batch, auto reset) {
+                WG_KLAUNCH(kernel, grid, block, lds, st, batch, kp, a.ptr, a.cols, a.stride, kout(o), g, reset);
+            };
+            if constexpr (E8 && NE <= 4) {
+                if (fix) return go(walker_step_lean<D3, NE, true, false, true>, kbatch15(b), KNoReset{});
+            }
+            if (ar_mode) go(walker_step_lean<D3, NE, E8, true>, *b, kreset(o, ar_mode));
+            else go(walker_step_lean<D3, NE, E8>, kbatch15(b), KNoReset{});
         }
-#undef WG_LAUNCH_FIX1
-#undef WG_LAUNCH_FIX
-        const hipError_t ef = hipGetLastError();
-        if (ef != hipSuccess) return fail(WG_EHIP, "launch failed: %s", hipGetErrorString(ef));
-        g_fix_launches.fetch_add(1, std::memory_order_relaxed);
-        return 0;
-    }
-#define WG_LAUNCH_LEAN(D3, NE_, E8_)                                                                             \
-    do {                                                                                                         \
-        if (ar_mode)                                                                                             \
-            WG_KLAUNCH((walker_step_lean<D3, NE_, E8_, true>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds,    \
-                       st, *b, kp, a, cols, astride, kout(o), g, kreset(o, ar_mode));                            \
-        else                                                                                                     \
-            WG_KLAUNCH((walker_step_lean<D3, NE_, E8_>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st,      \
-                       kbatch15(b), kp, a, cols, astride, kout(o), g, KNoReset{});                               \
-    } while (0)
-#define WG_LEAN_NE(D3, E8_)                                                    \
-    do {                                                                       \
-        if (ne == 2) WG_LAUNCH_LEAN(D3, 2, E8_);                               \
-        else if (ne == 3) WG_LAUNCH_LEAN(D3, 3, E8_);                          \
-        else if (ne == 4) WG_LAUNCH_LEAN(D3, 4, E8_);                          \
-        else WG_LAUNCH_LEAN(D3, 8, E8_);                                       \
-    } while (0)
-    // (the NE = 1 entry with preloaded arguments; the compact records take the spring records' slot)
-#define WG_LEAN1_ARGS(E8_)                                                                                       \
-    b->pos, b->vel, (E8_) ? static_cast<const void *>(b->edges8) : static_cast<const void *>(b->edges), b->inc,  \
-        b->N, b->M, b->K, g.wpw, g.wpb,                                                                          \
-        (int)((unsigned)g.nblk | ((unsigned)(kp.xcd & 2) << 29) | ((unsigned)(kp.prio != 0) << 31)), *b, kp, a,  \
-        cols, astride, kout(o), g
-#define WG_LAUNCH_LEAN1(D3, E8_)                                                                                 \
-    do {                                                                                                         \
-        if (ar_mode)                                                                                             \
-            WG_KLAUNCH((walker_step_lean1<D3, E8_, true>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st,    \
-                       WG_LEAN1_ARGS(E8_), kreset(o, ar_mode));                                                  \
-        else                                                                                                     \
-            WG_KLAUNCH((walker_step_lean1<D3, E8_>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st,          \
-                       WG_LEAN1_ARGS(E8_), KNoReset{});                                                          \
-    } while (0)
-    if (ne <= 1) {
-        if (in3d) { if (e8) WG_LAUNCH_LEAN1(true, true); else WG_LAUNCH_LEAN1(true, false); }
-        else { if (e8) WG_LAUNCH_LEAN1(false, true); else WG_LAUNCH_LEAN1(false, false); }
-    } else if (in3d) {
-        if (e8) WG_LEAN_NE(true, true); else WG_LEAN_NE(true, false);
-    } else {
-        if (e8) WG_LEAN_NE(false, true); else WG_LEAN_NE(false, false);
-    }
-#undef WG_LAUNCH_LEAN1
-#undef WG_LEAN1_ARGS
-#undef WG_LEAN_NE
-#undef WG_LAUNCH_LEAN
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WG_EHIP, "launch failed: %s", hipGetErrorString(e));
+    });
+    if (const int rc = wg_launched("launch")) return rc;
+    if (fix) g_fix_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }
 
-// ar_mode != 0: the AR twin, one LDS word per walker (its episode count) behind each wave's slice
-int launch_lean_rollout(const wg_batch *b, const KParams &kp, bool in3d, const float *a, int cols, int astride,
-                        int64_t astep, const wg_outputs &o, int n_steps, const LeanGeo &g0, hipStream_t st,
-                        int ar_mode = 0) {
+// n_steps steps of a uniform batch in one launch, the state in registers between them.  ar_mode != 0: the AR twin, one
+// LDS word per walker (its episode count) behind each wave's slice.  (A plain launch: wg_time_step never comes here.)
+int launch_lean_rollout(const wg_batch *b, const KParams &kp, bool in3d, const Actions &a, const wg_outputs &o,
+                        int n_steps, const LeanGeo &g0, hipStream_t st, int ar_mode = 0) {
     LeanGeo g = g0;
-    KResetRes ar{kreset(o, ar_mode), g.slice};
+    const KResetRes ar{kreset(o, ar_mode), g.slice};
     if (ar_mode) g.slice += align16(g.wpw * 4);
-    const int blocks = lean_blocks(b, g);
-    const int ne = (g.wpw * b->K + 63) / 64;
+    const dim3 grid(g.nblk), block(64 * g.wpb);
     const int lds = g.wpb * g.slice;
-    const bool e8 = use_edge8(b, g);
-#define WG_LAUNCH_RO(D3, NE_, E8_)                                                                               \
-    do {                                                                                                         \
-        if (ar_mode)                                                                                             \
-            hipLaunchKernelGGL((walker_rollout_lean<D3, NE_, E8_, true>), dim3(blocks), dim3(64 * g.wpb), lds,   \
-                               st, *b, kp, a, cols, astride, astep, kout(o), n_steps, g, ar);                    \
-        else                                                                                                     \
-            hipLaunchKernelGGL((walker_rollout_lean<D3, NE_, E8_>), dim3(blocks), dim3(64 * g.wpb), lds, st, *b, \
-                               kp, a, cols, astride, astep, kout(o), n_steps, g, KNoReset{});                    \
-    } while (0)
-#define WG_RO_NE(D3, E8_)                                                                                        \
-    do {                                                                                                         \
-        if (ne <= 1) WG_LAUNCH_RO(D3, 1, E8_);                                                                   \
-        else if (ne == 2) WG_LAUNCH_RO(D3, 2, E8_);                                                              \
-        else if (ne == 3) WG_LAUNCH_RO(D3, 3, E8_);                                                              \
-        else if (ne == 4) WG_LAUNCH_RO(D3, 4, E8_);                                                              \
-        else WG_LAUNCH_RO(D3, 8, E8_);                                                                           \
-    } while (0)
-    if (in3d) { if (e8) WG_RO_NE(true, true); else WG_RO_NE(true, false); }
-    else { if (e8) WG_RO_NE(false, true); else WG_RO_NE(false, false); }
-#undef WG_RO_NE
-#undef WG_LAUNCH_RO
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WG_EHIP, "launch failed: %s", hipGetErrorString(e));
+    with_instance(in3d, lean_passes(g, b), use_edge8(b, g), [&](auto d3, auto n, auto c8) {
+        constexpr bool D3 = decltype(d3)::value, E8 = decltype(c8)::value;
+        constexpr int NE = decltype(n)::value;
+        if (ar_mode)
+            hipLaunchKernelGGL((walker_rollout_lean<D3, NE, E8, true>), grid, block, lds, st, *b, kp, a.ptr, a.cols,
+                               a.stride, a.step, kout(o), n_steps, g, ar);
+        else
+            hipLaunchKernelGGL((walker_rollout_lean<D3, NE, E8>), grid, block, lds, st, *b, kp, a.ptr, a.cols, a.stride,
+                               a.step, kout(o), n_steps, g, KNoReset{});
+    });
+    return wg_launched("launch");
+}
+
+// ---- argument checks that run() and rollout_policy() share: 0, or the refusal.  Each entry calls them in the order its
+// callers have always seen (the first of several refusals is part of the contract: tests/test_refusal_order_cpu.py).
+// auto-reset (ABI 16): everything the reset tail reads
+int check_auto_reset(const wg_batch *b, int ar_mode) {
+    if (ar_mode & ~3) return wg_fail(WG_EINVAL, "auto_reset %d: bits 1 (done) and 2 (non-finite) only", ar_mode);
+    if (!b->init_pos || !b->init_vel || !b->init_acc || !b->init_muscle_x)
+        return wg_fail(WG_EINVAL, "auto_reset needs the snapshot (init_pos, init_vel, init_acc, init_muscle_x)");
+    if (!b->episodes) return wg_fail(WG_EINVAL, "auto_reset needs the episodes array");
+    if (b->reset_noise && b->reset_noise_rows < 1)
+        return wg_fail(WG_EINVAL, "auto_reset: reset_noise with reset_noise_rows %d < 1", b->reset_noise_rows);
+    if (b->reset_noise && b->reset_noise_stride < 3ll * b->N * b->M)
+        return wg_fail(WG_EINVAL, "auto_reset: reset_noise_stride %lld < 3 * P = %lld",
+                       (long long)b->reset_noise_stride, 3ll * b->N * b->M);
     return 0;
+}
+int check_integrator(const wg_params *p) {
+    return p->integrator < 0 || p->integrator > 2 ? wg_fail(WG_EINVAL, "integrator must be 0/1 (run1) or 2 (run2)") : 0;
+}
+int check_muscle_bounds(const wg_batch *b) {
+    return b->muscle_bounds ? 0 : wg_fail(WG_EINVAL, "actions need muscle_bounds");
+}
+int check_discrete(const wg_batch *b, const wg_params *p) {
+    return p->action_mode == 1 && !b->muscle_stride ? wg_fail(WG_EINVAL, "discrete actions need muscle_stride") : 0;
 }
 
 // a batch's observation row length under p: Creature.getstat's list (gym/optimized_walker.py:129-162)
@@ -3934,59 +3943,47 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
     const char *fn = episodes ? "wg_rollout_episodes" : "wg_rollout_policy";
     int rc = validate(b);
     if (rc) return rc;
-    if (!p) return fail(WG_EINVAL, "null params");
-    if (!pol) return fail(WG_EINVAL, "%s: null policy", fn);
-    if (!pol->w2) return fail(WG_EINVAL, "%s: null w2", fn);
-    if (n_steps < 1) return fail(WG_EINVAL, "%s: n_steps %d < 1", fn, n_steps);
+    if (!p) return wg_fail(WG_EINVAL, "null params");
+    if (!pol) return wg_fail(WG_EINVAL, "%s: null policy", fn);
+    if (!pol->w2) return wg_fail(WG_EINVAL, "%s: null w2", fn);
+    if (n_steps < 1) return wg_fail(WG_EINVAL, "%s: n_steps %d < 1", fn, n_steps);
     if (pol->hidden < 0 || pol->hidden > 256)
-        return fail(WG_EINVAL, "%s: hidden %d outside 0..256", fn, pol->hidden);
-    if (pol->hidden > 0 && !pol->w1) return fail(WG_EINVAL, "%s: hidden %d with a null w1", fn, pol->hidden);
+        return wg_fail(WG_EINVAL, "%s: hidden %d outside 0..256", fn, pol->hidden);
+    if (pol->hidden > 0 && !pol->w1) return wg_fail(WG_EINVAL, "%s: hidden %d with a null w1", fn, pol->hidden);
     if (pol->act_dim < 1 || pol->act_dim > b->A)
-        return fail(WG_EINVAL, "%s: act_dim %d outside 1..A = %d", fn, pol->act_dim, b->A);
+        return wg_fail(WG_EINVAL, "%s: act_dim %d outside 1..A = %d", fn, pol->act_dim, b->A);
     if (pol->obs_dim != obs_row_len(b, p))
-        return fail(WG_EINVAL, "%s: obs_dim %d, the batch's rows have %d values", fn, pol->obs_dim,
+        return wg_fail(WG_EINVAL, "%s: obs_dim %d, the batch's rows have %d values", fn, pol->obs_dim,
                     obs_row_len(b, p));
     if (pol->n_sets < 1 || b->N % pol->n_sets != 0)
-        return fail(WG_EINVAL, "%s: n_sets %d does not divide N = %d", fn, pol->n_sets, b->N);
-    if (!(pol->act_limit > 0.f)) return fail(WG_EINVAL, "%s: act_limit must be > 0 (+inf allowed)", fn);
+        return wg_fail(WG_EINVAL, "%s: n_sets %d does not divide N = %d", fn, pol->n_sets, b->N);
+    if (!(pol->act_limit > 0.f)) return wg_fail(WG_EINVAL, "%s: act_limit must be > 0 (+inf allowed)", fn);
     if (!episodes && p->auto_reset != 0)
-        return fail(WG_EINVAL, "%s: auto_reset %d (the resident loop has no reset tail)", fn, p->auto_reset);
+        return wg_fail(WG_EINVAL, "%s: auto_reset %d (the resident loop has no reset tail)", fn, p->auto_reset);
     if (episodes) {
         if (p->auto_reset == 0)
-            return fail(WG_EINVAL, "%s: auto_reset is 0 (without episode roll-over use wg_rollout_policy)", fn);
-        // (auto-reset's own checks, as wg_step makes them)
-        if (p->auto_reset & ~3)
-            return fail(WG_EINVAL, "auto_reset %d: bits 1 (done) and 2 (non-finite) only", p->auto_reset);
-        if (!b->init_pos || !b->init_vel || !b->init_acc || !b->init_muscle_x)
-            return fail(WG_EINVAL, "auto_reset needs the snapshot (init_pos, init_vel, init_acc, init_muscle_x)");
-        if (!b->episodes) return fail(WG_EINVAL, "auto_reset needs the episodes array");
-        if (b->reset_noise && b->reset_noise_rows < 1)
-            return fail(WG_EINVAL, "auto_reset: reset_noise with reset_noise_rows %d < 1", b->reset_noise_rows);
-        if (b->reset_noise && b->reset_noise_stride < 3ll * b->N * b->M)
-            return fail(WG_EINVAL, "auto_reset: reset_noise_stride %lld < 3 * P = %lld",
-                        (long long)b->reset_noise_stride, 3ll * b->N * b->M);
-        if (!st) return fail(WG_EINVAL, "%s: null episode stats", fn);
-        if (st->ep_slots < 0) return fail(WG_EINVAL, "%s: ep_slots %d < 0", fn, st->ep_slots);
+            return wg_fail(WG_EINVAL, "%s: auto_reset is 0 (without episode roll-over use wg_rollout_policy)", fn);
+        if ((rc = check_auto_reset(b, p->auto_reset))) return rc;   // (auto-reset's own checks, as wg_step makes them)
+        if (!st) return wg_fail(WG_EINVAL, "%s: null episode stats", fn);
+        if (st->ep_slots < 0) return wg_fail(WG_EINVAL, "%s: ep_slots %d < 0", fn, st->ep_slots);
         if ((st->ep_return || st->ep_length) && st->ep_slots == 0)
-            return fail(WG_EINVAL, "%s: ep_return / ep_length with ep_slots 0", fn);
+            return wg_fail(WG_EINVAL, "%s: ep_return / ep_length with ep_slots 0", fn);
         if (pol->return_out || pol->length_out)
-            return fail(WG_EINVAL, "%s: return_out / length_out are defined by the first done (wg_rollout_policy); "
+            return wg_fail(WG_EINVAL, "%s: return_out / length_out are defined by the first done (wg_rollout_policy); "
                                    "the episode stats replace them", fn);
     }
-    if (p->integrator < 0 || p->integrator > 2) return fail(WG_EINVAL, "integrator must be 0/1 (run1) or 2 (run2)");
-    if (!b->muscle_bounds) return fail(WG_EINVAL, "actions need muscle_bounds");
-    if (p->action_mode == 1 && !b->muscle_stride) return fail(WG_EINVAL, "discrete actions need muscle_stride");
+    if ((rc = check_integrator(p)) || (rc = check_muscle_bounds(b)) || (rc = check_discrete(b, p))) return rc;
     wg_outputs out = o ? *o : wg_outputs{};
     if ((out.obs || (episodes && out.final_obs)) && out.obs_stride < pol->obs_dim)
-        return fail(WG_EINVAL, "%s: obs_stride %d < obs_dim %d", fn, out.obs_stride, pol->obs_dim);
+        return wg_fail(WG_EINVAL, "%s: obs_stride %d < obs_dim %d", fn, out.obs_stride, pol->obs_dim);
     if (episodes && (out.nonfinite || out.momentum))
-        return fail(WG_EINVAL, "%s: nonfinite / momentum are not produced here", fn);
+        return wg_fail(WG_EINVAL, "%s: nonfinite / momentum are not produced here", fn);
     if (!episodes && (out.nonfinite || out.momentum || out.reset || out.final_obs))
-        return fail(WG_EINVAL, "%s: nonfinite / momentum / reset / final_obs are not produced here", fn);
+        return wg_fail(WG_EINVAL, "%s: nonfinite / momentum / reset / final_obs are not produced here", fn);
     LeanGeo lg{};
     if (b->ragged || p->spring_mode != 0 || p->pair_mode != 0 ||
         !lean_geo(b, (out.obs || (episodes && out.final_obs)) ? out.obs_stride : 0, &lg, p->spring_mode))
-        return fail(WG_EINVAL, "%s needs a batch the resident lean kernel takes (uniform, M dividing 64, "
+        return wg_fail(WG_EINVAL, "%s needs a batch the resident lean kernel takes (uniform, M dividing 64, "
                                "spring_mode 0, pair_mode 0, WG_LEAN not 0)", fn);
     if (b->N == 0) return 0;
     const KParams kp = make_kparams(*p);
@@ -4004,14 +4001,14 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
     kpol.off_w = kpol.off_a + align16(lg.wpw * kpol.C * 4);
     lg.slice = kpol.off_w + lg.wpw * (episodes ? 32 : 16);
     int lds = lg.wpb * lg.slice;
-    if (lds > 80 * 1024) return fail(WG_ERANGE, "%s: workgroup needs %d B of LDS (> 80 KiB)", fn, lds);
+    if (lds > 80 * 1024) return wg_fail(WG_ERANGE, "%s: workgroup needs %d B of LDS (> 80 KiB)", fn, lds);
     // a shared policy's weights staged in LDS where that costs no resident wave: as many workgroups per CU (160 KiB of
     // LDS, the kernel's register budget of 4 waves per SIMD, 3 at NE 8) with the weights as without.  (Staged at the
     // price of occupancy the canonical batch ran 90.6 us per step with H = 32 against 73.8 through L2; the one-wave
     // workgroups of a small batch keep their occupancy and run 7.96 against 9.03: profiles/r08_policy_rollout_ab.json.)
     // WG_POLICY_STAGE (read on every call, like WG_LEAN): 0 never, 2 whenever the workgroup stays within 80 KiB
     const int wbytes = 4 * (kpol.D * kpol.H + (kpol.H > 0 ? kpol.H : kpol.D) * kpol.C);
-    const int ne = (lg.wpw * b->K + 63) / 64;
+    const int ne = lean_passes(lg, b);
     const int cap = std::max(1, (ne > 4 ? 12 : 16) / lg.wpb);
     const int stage = env_int("WG_POLICY_STAGE", 1);
     const bool free_stage = std::min(cap, LDS_LIMIT / lds) == std::min(cap, LDS_LIMIT / (lds + wbytes));
@@ -4020,33 +4017,19 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
         kpol.off_wts = lds;
         lds += wbytes;
     }
-    const int blocks = lean_blocks(b, lg);
-    const bool e8 = use_edge8(b, lg);
+    const dim3 grid(lg.nblk), block(64 * lg.wpb);
     const KReset ar = kreset(out, p->auto_reset);
-#define WG_LAUNCH_RP(D3, NE_, E8_)                                                                               \
-    do {                                                                                                         \
-        if (episodes)                                                                                            \
-            hipLaunchKernelGGL((walker_rollout_policy<D3, NE_, E8_, true>), dim3(blocks), dim3(64 * lg.wpb),     \
-                               lds, stream, *b, kp, kpol, kout(out), n_steps, lg, ar, *st);                      \
-        else                                                                                                     \
-            hipLaunchKernelGGL((walker_rollout_policy<D3, NE_, E8_>), dim3(blocks), dim3(64 * lg.wpb), lds,      \
-                               stream, *b, kp, kpol, kout(out), n_steps, lg, KNoReset{}, KNoReset{});            \
-    } while (0)
-#define WG_RP_NE(D3, E8_)                                                                                        \
-    do {                                                                                                         \
-        if (ne <= 1) WG_LAUNCH_RP(D3, 1, E8_);                                                                   \
-        else if (ne == 2) WG_LAUNCH_RP(D3, 2, E8_);                                                              \
-        else if (ne == 3) WG_LAUNCH_RP(D3, 3, E8_);                                                              \
-        else if (ne == 4) WG_LAUNCH_RP(D3, 4, E8_);                                                              \
-        else WG_LAUNCH_RP(D3, 8, E8_);                                                                           \
-    } while (0)
-    if (p->in3d) { if (e8) WG_RP_NE(true, true); else WG_RP_NE(true, false); }
-    else { if (e8) WG_RP_NE(false, true); else WG_RP_NE(false, false); }
-#undef WG_RP_NE
-#undef WG_LAUNCH_RP
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WG_EHIP, "launch failed: %s", hipGetErrorString(e));
-    return 0;
+    with_instance(p->in3d != 0, ne, use_edge8(b, lg), [&](auto d3, auto n, auto c8) {
+        constexpr bool D3 = decltype(d3)::value, E8 = decltype(c8)::value;
+        constexpr int NE = decltype(n)::value;
+        if (episodes)
+            hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8, true>), grid, block, lds, stream, *b, kp, kpol,
+                               kout(out), n_steps, lg, ar, *st);
+        else
+            hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8>), grid, block, lds, stream, *b, kp, kpol, kout(out),
+                               n_steps, lg, KNoReset{}, KNoReset{});
+    });
+    return wg_launched("launch");
 }
 
 // ---- ragged wave kernel (wg_batch.ragged = 2): spring passes, planner, geometry, launch
@@ -4078,28 +4061,15 @@ bool rag_geo(const wg_batch *b, int obs_stride, RagGeo *out) {
     return true;
 }
 
-int launch_waves(const wg_batch *b, const KParams &kp, bool in3d, const float *a, int cols, int astride,
-                 const wg_outputs &o, const int32_t *plan, int ntiles, const RagGeo &g, hipStream_t st) {
-    const int ne = wave_passes(b->M, b->K);
-    const int blocks = (ntiles + g.wpb - 1) / g.wpb;
-    const int lds = g.wpb * g.slice;
-#define WG_LAUNCH_WAVES(D3, NE_)                                                                                  \
-    WG_KLAUNCH((walker_step_waves<D3, NE_>), dim3(blocks), dim3(64 * g.wpb), (uint32_t)lds, st, *b, kp, a, cols,   \
-               astride, kout(o), plan, ntiles, g)
-#define WG_WAVES_NE(D3)                                                        \
-    do {                                                                       \
-        if (ne <= 1) WG_LAUNCH_WAVES(D3, 1);                                   \
-        else if (ne == 2) WG_LAUNCH_WAVES(D3, 2);                              \
-        else if (ne == 3) WG_LAUNCH_WAVES(D3, 3);                              \
-        else if (ne == 4) WG_LAUNCH_WAVES(D3, 4);                              \
-        else WG_LAUNCH_WAVES(D3, 8);                                           \
-    } while (0)
-    if (in3d) WG_WAVES_NE(true); else WG_WAVES_NE(false);
-#undef WG_WAVES_NE
-#undef WG_LAUNCH_WAVES
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WG_EHIP, "launch failed: %s", hipGetErrorString(e));
-    return 0;
+int launch_waves(const wg_batch *b, const KParams &kp, bool in3d, const Actions &a, const wg_outputs &o,
+                 const int32_t *plan, int ntiles, const RagGeo &g, hipStream_t st) {
+    const dim3 grid((ntiles + g.wpb - 1) / g.wpb), block(64 * g.wpb);
+    const uint32_t lds = (uint32_t)(g.wpb * g.slice);
+    with_instance(in3d, wave_passes(b->M, b->K), [&](auto d3, auto n) {
+        WG_KLAUNCH((walker_step_waves<decltype(d3)::value, decltype(n)::value>), grid, block, lds, st, *b, kp, a.ptr,
+                   a.cols, a.stride, kout(o), plan, ntiles, g);
+    });
+    return wg_launched("launch");
 }
 
 int reset_impl(const wg_batch *b, const float *noise, const uint8_t *mask, int zmode, hipStream_t stream) {
@@ -4109,9 +4079,7 @@ int reset_impl(const wg_batch *b, const float *noise, const uint8_t *mask, int z
     const long P = b->ragged ? -1 : (long)b->N * b->M;
     const int blocks = P > 0 ? (int)std::min<long>((P + 255) / 256, 4096) : 1024;
     hipLaunchKernelGGL(walker_reset_kernel, dim3(blocks), dim3(256), 0, stream, *b, noise, mask, zmode);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WG_EHIP, "reset launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return wg_launched("reset launch");
 }
 
 template <bool STEP>
@@ -4121,102 +4089,133 @@ int dispatch(const wg_batch *b, const KParams &kp, bool in3d, const float *a, in
                        : dispatch2<STEP, 3>(b, kp, in3d, a, cols, astride, o, plan, blocks, g, st);
 }
 
-int run(const wg_batch *b, const wg_params *p, const float *action, int32_t cols, int32_t astride,
-        int64_t astep, const wg_outputs *o, int32_t n_steps, const int32_t *plan, int32_t plan_blocks,
-        hipStream_t stream, bool step, bool resident = false, bool check_only = false, int s_first = 0,
-        int s_total = 0) {
-    // s_total: the steps of the caller's whole call when this is one slice of it (wg_run_ranges issues one step per
-    // call), 0 = s_first + n_steps, < 0 = every step keeps its acc / contact stores (wg_time_step)
+// the outputs of step s of a call (rows out_step / obs_step apart; the three-component ones 3 * out_step)
+wg_outputs outputs_at(const wg_outputs &o, int s) {
+    wg_outputs os = o;
+    if (os.obs) os.obs += s * os.obs_step;
+    if (os.reward) os.reward += s * os.out_step;
+    if (os.done) os.done += s * os.out_step;
+    if (os.energy) os.energy += s * os.out_step;
+    if (os.centroid) os.centroid += 3 * s * os.out_step;
+    if (os.steps) os.steps += s * os.out_step;
+    if (os.nonfinite) os.nonfinite += s * os.out_step;
+    if (os.momentum) os.momentum += 3 * s * os.out_step;
+    if (os.reset) os.reset += s * os.out_step;
+    if (os.final_obs) os.final_obs += s * os.obs_step;
+    return os;
+}
+
+// What a run() call is, beside the batch, parameters, outputs and plan.  Every entry fills it by field name.
+struct RunCall {
+    bool step;         // env steps; false: the outputs of the state as it is (wg_observe), one launch
+    bool resident;     // every step in one launch where the batch allows it (wg_rollout); false: a launch per step
+    bool check_only;   // check every argument, launch nothing (wg_run_ranges, wg_time_step: before their first launch)
+    int s_first;       // the index of this call's first step in the caller's whole call (its outputs and actions)
+    int s_total;       // the steps of that whole call when this is one slice of it: 0 = s_first + n_steps, < 0 = every
+                       // step keeps its acc / contact stores (wg_time_step)
+    Actions act;
+};
+
+int run(const wg_batch *b, const wg_params *p, const wg_outputs *o, int32_t n_steps, const int32_t *plan,
+        int32_t plan_blocks, hipStream_t stream, const RunCall &c) {
+    const bool step = c.step;
+    Actions act = c.act;
+    if (!act.ptr) act.step = 0;
     int rc = validate(b);
     if (rc) return rc;
-    if (!p) return fail(WG_EINVAL, "null params");
+    if (!p) return wg_fail(WG_EINVAL, "null params");
     if (b->N == 0 || n_steps <= 0) return 0;
-    if (action && (cols < 0 || astride < cols)) return fail(WG_EINVAL, "bad action stride");
-    if (action && p->action_mode == 1 && !b->muscle_stride) return fail(WG_EINVAL, "discrete actions need muscle_stride");
-    if (p->integrator < 0 || p->integrator > 2) return fail(WG_EINVAL, "integrator must be 0/1 (run1) or 2 (run2)");
-    if (action && !b->muscle_bounds) return fail(WG_EINVAL, "actions need muscle_bounds");
-    if (b->ragged && (!plan || plan_blocks <= 0)) return fail(WG_EINVAL, "ragged batch needs a plan");
+    if (act.ptr && (act.cols < 0 || act.stride < act.cols)) return wg_fail(WG_EINVAL, "bad action stride");
+    if (act.ptr && (rc = check_discrete(b, p))) return rc;
+    if ((rc = check_integrator(p))) return rc;
+    if (act.ptr && (rc = check_muscle_bounds(b))) return rc;
+    if (b->ragged && (!plan || plan_blocks <= 0)) return wg_fail(WG_EINVAL, "ragged batch needs a plan");
     wg_outputs out = o ? *o : wg_outputs{};
-    if (out.obs && out.obs_stride <= 0) return fail(WG_EINVAL, "obs_stride must be > 0");
+    if (out.obs && out.obs_stride <= 0) return wg_fail(WG_EINVAL, "obs_stride must be > 0");
     KParams kp = make_kparams(*p);
     const Geo g = b->ragged ? ragged_geo(b) : uniform_geo(b, out.obs ? out.obs_stride : 0, step && p->pair_mode != 0);
-    if (g.W > g.threads) return fail(WG_ERANGE, "more than %d walkers per workgroup", g.threads);
+    if (g.W > g.threads) return wg_fail(WG_ERANGE, "more than %d walkers per workgroup", g.threads);
     const int blocks = b->ragged ? plan_blocks : (b->N + g.W - 1) / g.W;
     LeanGeo lg{};
-    const bool act_u32 = !action || (int64_t)b->N * astride * 4 < (1ll << 32);   // at_u32 action offsets
+    const bool act_u32 = !act.ptr || (int64_t)b->N * act.stride * 4 < (1ll << 32);   // at_u32 action offsets
     const bool use_lean = step && act_u32 && lean_geo(b, out.obs ? out.obs_stride : 0, &lg, p->spring_mode);
     RagGeo rgeo{};
     const bool use_waves = step && act_u32 && p->spring_mode == 0 && p->pair_mode == 0 && lean_enabled() &&
                            rag_geo(b, out.obs ? out.obs_stride : 0, &rgeo);
     if (p->spring_mode < 0 || p->spring_mode > 2)
-        return fail(WG_EINVAL, "spring_mode %d: 0 (engine.py), 1 (G2 element), 2 (G3 engine) only", p->spring_mode);
+        return wg_fail(WG_EINVAL, "spring_mode %d: 0 (engine.py), 1 (G2 element), 2 (G3 engine) only", p->spring_mode);
     if (step && (p->pair_mode & ~31))
-        return fail(WG_EINVAL, "pair_mode %d: bits 1 (gravity), 2 (coulomb), 4 (bounce), 8 (G2 gravity_vec), "
-                               "16 (electrostatic) only", p->pair_mode);
+        return wg_fail(WG_EINVAL, "pair_mode %d: bits 1 (gravity), 2 (coulomb), 4 (bounce), 8 (G2 gravity_vec), "
+                                  "16 (electrostatic) only", p->pair_mode);
     if (step && p->pair_mode != 0 && p->spring_mode != 0)
-        return fail(WG_EINVAL, "pair_mode %d needs spring_mode 0", p->pair_mode);
+        return wg_fail(WG_EINVAL, "pair_mode %d needs spring_mode 0", p->pair_mode);
     if (step && (p->pair_mode & 4) && !b->radius)
-        return fail(WG_EINVAL, "pair_mode 4 (bounce) needs the radius array");
+        return wg_fail(WG_EINVAL, "pair_mode 4 (bounce) needs the radius array");
     // auto-reset (ABI 16): fused into the lean step kernels only; everything it reads checked here
     const int ar_mode = step ? p->auto_reset : 0;
     if (ar_mode) {
-        if (ar_mode & ~3) return fail(WG_EINVAL, "auto_reset %d: bits 1 (done) and 2 (non-finite) only", ar_mode);
-        if (!b->init_pos || !b->init_vel || !b->init_acc || !b->init_muscle_x)
-            return fail(WG_EINVAL, "auto_reset needs the snapshot (init_pos, init_vel, init_acc, init_muscle_x)");
-        if (!b->episodes) return fail(WG_EINVAL, "auto_reset needs the episodes array");
-        if (b->reset_noise && b->reset_noise_rows < 1)
-            return fail(WG_EINVAL, "auto_reset: reset_noise with reset_noise_rows %d < 1", b->reset_noise_rows);
-        if (b->reset_noise && b->reset_noise_stride < 3ll * b->N * b->M)
-            return fail(WG_EINVAL, "auto_reset: reset_noise_stride %lld < 3 * P = %lld",
-                        (long long)b->reset_noise_stride, 3ll * b->N * b->M);
-        if (p->pair_mode != 0) return fail(WG_EINVAL, "auto_reset needs pair_mode 0 (pair_mode %d)", p->pair_mode);
+        if ((rc = check_auto_reset(b, ar_mode))) return rc;
+        if (p->pair_mode != 0) return wg_fail(WG_EINVAL, "auto_reset needs pair_mode 0 (pair_mode %d)", p->pair_mode);
         if (!use_lean)
-            return fail(WG_EINVAL, "auto_reset needs a batch the lean kernel takes (uniform, M dividing 64, "
-                                   "spring_mode 0, pair_mode 0, WG_LEAN not 0): the ragged wave kernel and the "
-                                   "workgroup kernel have no auto-reset");
+            return wg_fail(WG_EINVAL, "auto_reset needs a batch the lean kernel takes (uniform, M dividing 64, "
+                                      "spring_mode 0, pair_mode 0, WG_LEAN not 0): the ragged wave kernel and the "
+                                      "workgroup kernel have no auto-reset");
     }
-    if (check_only) return 0;   // wg_step_ranges: every range's arguments checked before any range launches
+    if (c.check_only) return 0;
+    const bool in3d = p->in3d != 0;
     const bool extras = out.nonfinite || out.momentum;   // opt-in per-walker info after each step (ABI 10)
     auto info_pass = [&](const wg_outputs &os) -> int {
         if (!(os.nonfinite || os.momentum)) return 0;
         hipLaunchKernelGGL(walker_info_kernel, dim3((b->N + 255) / 256), dim3(256), 0, stream, *b, os.nonfinite,
                            os.momentum, b->ragged ? plan : nullptr, plan_blocks);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : fail(WG_EHIP, "info launch failed: %s", hipGetErrorString(e));
+        return wg_launched("info launch");
     };
     // (the resident rollout keeps the state in registers between steps: with the per-step info extras requested the
     // steps run as per-step launches instead, bit-identical)
     // (with auto-reset: the resident kernel's AR twin, the reset tail in its loop, where its episode counts fit beside
     // the slices in the lean kernel's 80 KiB)
     const bool ar_fits = !ar_mode || lg.wpb * (lg.slice + align16(lg.wpw * 4)) <= 80 * 1024;
-    if (resident && use_lean && p->pair_mode == 0 && !extras && ar_fits)   // one launch for every step, state in registers
-        return launch_lean_rollout(b, kp, p->in3d != 0, action, cols, astride, action ? astep : 0, out, n_steps, lg,
-                                   stream, ar_mode);
+    if (c.resident && use_lean && p->pair_mode == 0 && !extras && ar_fits)   // one launch for every step
+        return launch_lean_rollout(b, kp, in3d, act, out, n_steps, lg, stream, ar_mode);
     // acc and contact are read by nothing on the step path and overwritten by the next step: only the call's last step
     // stores them (the info kernel reads acc: with its outputs requested every step does)
-    const int s_last = (s_total > 0 ? s_total : s_first + n_steps) - 1;
-    for (int s = s_first; s < s_first + n_steps; s++) {   // (s_first: wg_run_ranges issues one step per call)
-        kp.keep_aux = (s_total < 0 || s >= s_last || extras) ? 1 : 0;
-        wg_outputs os = out;
-        if (os.obs) os.obs += s * os.obs_step;
-        if (os.reward) os.reward += s * os.out_step;
-        if (os.done) os.done += s * os.out_step;
-        if (os.energy) os.energy += s * os.out_step;
-        if (os.centroid) os.centroid += 3 * s * os.out_step;
-        if (os.steps) os.steps += s * os.out_step;
-        if (os.nonfinite) os.nonfinite += s * os.out_step;
-        if (os.momentum) os.momentum += 3 * s * os.out_step;
-        if (os.reset) os.reset += s * os.out_step;
-        if (os.final_obs) os.final_obs += s * os.obs_step;
-        const float *a = action ? action + s * astep : nullptr;
-        if (step && use_lean) rc = launch_lean(b, kp, p->in3d != 0, a, cols, astride, os, lg, stream, ar_mode);
-        else if (use_waves) rc = launch_waves(b, kp, p->in3d != 0, a, cols, astride, os, plan, plan_blocks, rgeo, stream);
-        else rc = step ? dispatch<true>(b, kp, p->in3d != 0, a, cols, astride, os, plan, blocks, g, stream)
-                       : dispatch<false>(b, kp, p->in3d != 0, nullptr, 0, 0, os, plan, blocks, g, stream);
+    const int s_last = (c.s_total > 0 ? c.s_total : c.s_first + n_steps) - 1;
+    for (int s = c.s_first; s < c.s_first + n_steps; s++) {
+        kp.keep_aux = (c.s_total < 0 || s >= s_last || extras) ? 1 : 0;
+        const wg_outputs os = outputs_at(out, s);
+        const Actions a = act.at(s);
+        if (use_lean) rc = launch_lean(b, kp, in3d, a, os, lg, stream, ar_mode);
+        else if (use_waves) rc = launch_waves(b, kp, in3d, a, os, plan, plan_blocks, rgeo, stream);
+        else rc = step ? dispatch<true>(b, kp, in3d, a.ptr, a.cols, a.stride, os, plan, blocks, g, stream)
+                       : dispatch<false>(b, kp, in3d, nullptr, 0, 0, os, plan, blocks, g, stream);
         if (rc) return rc;
         if (extras && (rc = info_pass(os))) return rc;
     }
     return 0;
+}
+
+// The greedy packer of wg_plan_waves and wg_plan_ragged: consecutive walkers join a group (a wave tile, a workgroup)
+// while its masses, springs, muscles and walkers stay within the caps; plan[i] .. plan[i + 1] are group i's walkers.
+// A walker over a cap by itself: refused where the group cannot hold it (strict: a wave tile), a group of its own
+// otherwise (the ragged workgroup kernel sizes its LDS from the batch maxima).
+struct PackCaps { int P, E, U, W; };
+int pack_plan(const int32_t *mass_off, const int32_t *edge_off, const int32_t *muscle_off, int N, int32_t *plan,
+              int max_groups, const PackCaps &c, bool strict, const char *unit) {
+    int groups = 0, w = 0;
+    plan[0] = 0;
+    while (w < N) {
+        int P = 0, E = 0, U = 0, n = 0;
+        while (w < N) {
+            const int m = mass_off[w + 1] - mass_off[w], k = edge_off[w + 1] - edge_off[w],
+                      a = muscle_off[w + 1] - muscle_off[w];
+            if (strict && (m > c.P || a > c.U || k > c.E)) return wg_fail(WG_EINVAL, "walker %d does not fit one wave", w);
+            if (n > 0 && (P + m > c.P || E + k > c.E || U + a > c.U || n + 1 > c.W)) break;
+            P += m; E += k; U += a; n++; w++;
+        }
+        if (groups + 1 > max_groups) return wg_fail(WG_ERANGE, "plan needs more than %d %s", max_groups, unit);
+        plan[++groups] = w;
+    }
+    return groups;
 }
 
 // the launch floor beside a small step (bench.py): an empty launch, and one coalesced load + store per thread
@@ -4246,14 +4245,15 @@ const char *wg_last_error(void) { return g_err; }
 int wg_step(const wg_batch *b, const wg_params *p, const float *action, int32_t action_cols,
             int32_t action_stride, int64_t action_step, const wg_outputs *o, int32_t n_steps,
             const int32_t *plan, int32_t plan_blocks, hipStream_t stream) {
-    return run(b, p, action, action_cols, action_stride, action_step, o, n_steps, plan, plan_blocks, stream, true);
+    return run(b, p, o, n_steps, plan, plan_blocks, stream,
+               {.step = true, .act = {action, action_cols, action_stride, action_step}});
 }
 
 int wg_rollout(const wg_batch *b, const wg_params *p, const float *action, int32_t action_cols,
                int32_t action_stride, int64_t action_step, const wg_outputs *o, int32_t n_steps,
                const int32_t *plan, int32_t plan_blocks, hipStream_t stream) {
-    return run(b, p, action, action_cols, action_stride, action_step, o, n_steps, plan, plan_blocks, stream, true,
-               true);
+    return run(b, p, o, n_steps, plan, plan_blocks, stream,
+               {.step = true, .resident = true, .act = {action, action_cols, action_stride, action_step}});
 }
 
 int wg_rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o,
@@ -4268,37 +4268,34 @@ int wg_rollout_episodes(const wg_batch *b, const wg_params *p, const wg_policy *
 
 int wg_run_ranges(const wg_range *ranges, int32_t n, const wg_params *p, const float *action, int32_t action_cols,
                   int32_t action_stride, int64_t action_step, int32_t n_steps, hipEvent_t *events) {
-    if (!ranges || n < 1 || (n > 1 && !events)) return fail(WG_EINVAL, "wg_run_ranges: bad ranges / events");
+    if (!ranges || n < 1 || (n > 1 && !events)) return wg_fail(WG_EINVAL, "wg_run_ranges: bad ranges / events");
+    // `steps` steps of one range from step s_first of the call's n_steps
+    auto run_range = [&](const wg_range &r, int steps, bool check_only, int s_first) -> int {
+        return run(r.batch, p, r.outputs, steps, r.plan, r.plan_blocks, r.stream,
+                   {.step = true, .check_only = check_only, .s_first = s_first, .s_total = n_steps,
+                    .act = {action ? action + r.action_offset : nullptr, action_cols, action_stride, action_step}});
+    };
     // every range checked before the first launch: a bad range fails the call with no walker stepped
-    for (int i = 0; i < n; i++) {
-        const wg_range &r = ranges[i];
-        const int rc = run(r.batch, p, action ? action + r.action_offset : nullptr, action_cols, action_stride,
-                           action_step, r.outputs, n_steps, r.plan, r.plan_blocks, r.stream, true, false, true);
-        if (rc) return rc;
-    }
+    for (int i = 0; i < n; i++)
+        if (const int rc = run_range(ranges[i], n_steps, true, 0)) return rc;
     if (n_steps <= 0) return 0;
     hipStream_t s0 = ranges[0].stream;
-    if (n > 1 && hipEventRecord(events[0], s0) != hipSuccess) return fail(WG_EHIP, "fork event record failed");
+    if (n > 1 && hipEventRecord(events[0], s0) != hipSuccess) return wg_fail(WG_EHIP, "fork event record failed");
     for (int i = 1; i < n; i++)   // (a failed wait leaves nothing issued on the side streams yet: nothing to join)
-        if (hipStreamWaitEvent(ranges[i].stream, events[0], 0) != hipSuccess) return fail(WG_EHIP, "fork wait failed");
+        if (hipStreamWaitEvent(ranges[i].stream, events[0], 0) != hipSuccess) return wg_fail(WG_EHIP, "fork wait failed");
     // step s of every range is issued before step s + 1 of any: the ranges start together and stay side by side in
     // the hardware queues (range by range, the second range would start only after the host had issued all of the
     // first range's launches).  (Range 0 issued a few steps ahead, or the other ranges started after a timed wait,
     // measured no better: profiles/r04jj_issue_ab.jsonl.)
-    auto issue = [&](int i, int s) -> int {
-        const wg_range &r = ranges[i];
-        return run(r.batch, p, action ? action + r.action_offset : nullptr, action_cols, action_stride, action_step,
-                   r.outputs, 1, r.plan, r.plan_blocks, r.stream, true, false, false, s, n_steps);
-    };
     // A launch-time failure (hipGetLastError after a launch) can still stop the issue part-way, after other ranges or
     // steps went out: the call then returns that error with a partially stepped batch, but the side streams are joined
     // back to ranges[0].stream first, so the caller's stream never runs ahead of work the call did issue.
     int rc = 0;
     for (int s = 0; s < n_steps && !rc; s++)
-        for (int i = 0; i < n && !rc; i++) rc = issue(i, s);
+        for (int i = 0; i < n && !rc; i++) rc = run_range(ranges[i], 1, false, s);
     for (int i = 1; i < n; i++)
         if (hipEventRecord(events[i], ranges[i].stream) != hipSuccess || hipStreamWaitEvent(s0, events[i], 0) != hipSuccess)
-            return rc ? rc : fail(WG_EHIP, "join event failed");
+            return rc ? rc : wg_fail(WG_EHIP, "join event failed");
     return rc;
 }
 
@@ -4309,22 +4306,22 @@ int wg_step_ranges(const wg_range *ranges, int32_t n, const wg_params *p, const 
 
 int wg_observe(const wg_batch *b, const wg_params *p, const wg_outputs *o, const int32_t *plan,
                int32_t plan_blocks, hipStream_t stream) {
-    if (!o) return fail(WG_EINVAL, "null outputs");
-    return run(b, p, nullptr, 0, 0, 0, o, 1, plan, plan_blocks, stream, false);
+    if (!o) return wg_fail(WG_EINVAL, "null outputs");
+    return run(b, p, o, 1, plan, plan_blocks, stream, {.step = false});
 }
 
 // SURVEY §8(b)'s declared signatures (ABI 13): uniform batches only (a ragged batch needs a plan)
 int wg_step_simple(const wg_batch *b, const float *action, const wg_params *p, int32_t n_steps, hipStream_t stream) {
-    if (b && b->ragged) return fail(WG_EINVAL, "wg_step_simple: uniform batches only (ragged: wg_step with a plan)");
+    if (b && b->ragged) return wg_fail(WG_EINVAL, "wg_step_simple: uniform batches only (ragged: wg_step with a plan)");
     const int32_t A = b ? b->A : 0;
     const int64_t step = b ? (int64_t)b->N * A : 0;
-    return run(b, p, A > 0 ? action : nullptr, A, A, step, nullptr, n_steps, nullptr, 0, stream, true);
+    return run(b, p, nullptr, n_steps, nullptr, 0, stream, {.step = true, .act = {A > 0 ? action : nullptr, A, A, step}});
 }
 
 int wg_observe_simple(const wg_batch *b, const wg_obs_cfg *cfg, float *obs, float *reward, uint8_t *done,
                       float *centroid, float *energy, hipStream_t stream) {
-    if (b && b->ragged) return fail(WG_EINVAL, "wg_observe_simple: uniform batches only (ragged: wg_observe with a plan)");
-    if (!b || !cfg) return fail(WG_EINVAL, "null batch / cfg");
+    if (b && b->ragged) return wg_fail(WG_EINVAL, "wg_observe_simple: uniform batches only (ragged: wg_observe with a plan)");
+    if (!b || !cfg) return wg_fail(WG_EINVAL, "null batch / cfg");
     wg_outputs o{};
     o.obs = obs;
     o.obs_stride = 3 * (cfg->in3d ? 3 : 2) * b->M + (cfg->conmid ? 3 : 0) + b->A;
@@ -4332,7 +4329,7 @@ int wg_observe_simple(const wg_batch *b, const wg_obs_cfg *cfg, float *obs, floa
     o.done = done;
     o.centroid = centroid;
     o.energy = energy;
-    return run(b, cfg, nullptr, 0, 0, 0, &o, 1, nullptr, 0, stream, false);
+    return run(b, cfg, &o, 1, nullptr, 0, stream, {.step = false});
 }
 
 // ABI 14, a measurement aid (bench.py's roofline): wg_step's n_steps, one launch per step, each step kernel launched with
@@ -4341,27 +4338,27 @@ int wg_observe_simple(const wg_batch *b, const wg_obs_cfg *cfg, float *obs, floa
 int wg_time_step(const wg_batch *b, const wg_params *p, const float *action, int32_t action_cols, int32_t action_stride,
                  int64_t action_step, const wg_outputs *o, int32_t n_steps, const int32_t *plan, int32_t plan_blocks,
                  hipStream_t stream, float *ms_per_launch) {
-    if (!ms_per_launch || n_steps < 1) return fail(WG_EINVAL, "wg_time_step: n_steps >= 1 and ms_per_launch required");
-    int rc = run(b, p, action, action_cols, action_stride, action_step, o, n_steps, plan, plan_blocks, stream, true,
-                 false, true);   // every argument checked before the first launch
+    if (!ms_per_launch || n_steps < 1) return wg_fail(WG_EINVAL, "wg_time_step: n_steps >= 1 and ms_per_launch required");
+    const Actions act{action, action_cols, action_stride, action_step};
+    int rc = run(b, p, o, n_steps, plan, plan_blocks, stream,
+                 {.step = true, .check_only = true, .act = act});   // every argument checked before the first launch
     if (rc) return rc;
-    if (b->N == 0) return fail(WG_EINVAL, "wg_time_step: empty batch (no launch to time)");
+    if (b->N == 0) return wg_fail(WG_EINVAL, "wg_time_step: empty batch (no launch to time)");
     std::vector<hipEvent_t> ev((size_t)2 * n_steps, nullptr);
     for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { rc = fail(WG_EHIP, "wg_time_step: event create failed"); break; }
+        if (hipEventCreate(&e) != hipSuccess) { rc = wg_fail(WG_EHIP, "wg_time_step: event create failed"); break; }
     for (int s = 0; s < n_steps && !rc; s++) {
         g_kev_start = ev[2 * s]; g_kev_stop = ev[2 * s + 1];
-        rc = run(b, p, action, action_cols, action_stride, action_step, o, 1, plan, plan_blocks, stream, true, false,
-                 false, s, -1);
+        rc = run(b, p, o, 1, plan, plan_blocks, stream, {.step = true, .s_first = s, .s_total = -1, .act = act});
     }
     g_kev_start = g_kev_stop = nullptr;
     double total = 0.0;
     // (after a failure part-way, the launches already issued still hold their events: wait for them before destroying)
-    if (hipStreamSynchronize(stream) != hipSuccess && !rc) rc = fail(WG_EHIP, "wg_time_step: stream sync failed");
+    if (hipStreamSynchronize(stream) != hipSuccess && !rc) rc = wg_fail(WG_EHIP, "wg_time_step: stream sync failed");
     for (int s = 0; s < n_steps && !rc; s++) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, ev[2 * s], ev[2 * s + 1]) != hipSuccess)
-            rc = fail(WG_EHIP, "wg_time_step: elapsed time of step %d unavailable", s);
+            rc = wg_fail(WG_EHIP, "wg_time_step: elapsed time of step %d unavailable", s);
         total += ms;
     }
     for (auto e : ev)
@@ -4371,7 +4368,7 @@ int wg_time_step(const wg_batch *b, const wg_params *p, const float *action, int
 }
 
 int wg_reset(const wg_batch *b, const wg_params *p, const float *noise, const uint8_t *mask, hipStream_t stream) {
-    if (!p) return fail(WG_EINVAL, "null params");
+    if (!p) return wg_fail(WG_EINVAL, "null params");
     return reset_impl(b, noise, mask, p->in3d ? 1 : 0, stream);
 }
 
@@ -4385,11 +4382,11 @@ int wg_wave_edge_passes(int32_t M, int32_t K) { return wave_passes(M, K); }
 int wg_plan_errors(int32_t clear) {
     int v = 0;
     if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_plan_error), sizeof v, 0, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(WG_EHIP, "plan error flag copy failed");
+        return wg_fail(WG_EHIP, "plan error flag copy failed");
     if (clear && v) {
         const int z = 0;
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_plan_error), &z, sizeof z, 0, hipMemcpyHostToDevice) != hipSuccess)
-            return fail(WG_EHIP, "plan error flag reset failed");
+            return wg_fail(WG_EHIP, "plan error flag reset failed");
     }
     return v;
 }
@@ -4397,50 +4394,23 @@ int wg_plan_errors(int32_t clear) {
 int wg_plan_waves(const int32_t *mass_off, const int32_t *edge_off, const int32_t *muscle_off, int32_t N,
                   int32_t *plan, int32_t max_tiles) {
     if (!mass_off || !edge_off || !muscle_off || !plan || N < 0 || max_tiles < 1)
-        return fail(WG_EINVAL, "bad plan args");
+        return wg_fail(WG_EINVAL, "bad plan args");
     int Mmax = 1, Kmax = 0;
     for (int w = 0; w < N; w++) {
         Mmax = std::max(Mmax, mass_off[w + 1] - mass_off[w]);
         Kmax = std::max(Kmax, edge_off[w + 1] - edge_off[w]);
     }
     const int ne = wave_passes(Mmax, Kmax);
-    if (!ne) return fail(WG_EINVAL, "a walker does not fit one wave (M=%d K=%d)", Mmax, Kmax);
-    int tiles = 0, w = 0;
-    plan[0] = 0;
-    while (w < N) {
-        int P = 0, E = 0, U = 0, n = 0;
-        while (w < N) {
-            const int m = mass_off[w + 1] - mass_off[w], k = edge_off[w + 1] - edge_off[w],
-                      a = muscle_off[w + 1] - muscle_off[w];
-            if (m > 64 || a > 64 || k > 64 * ne) return fail(WG_EINVAL, "walker %d does not fit one wave", w);
-            if (n > 0 && (P + m > 64 || E + k > 64 * ne || U + a > 64 || n + 1 > RW_MAXW)) break;
-            P += m; E += k; U += a; n++; w++;
-        }
-        if (tiles + 1 > max_tiles) return fail(WG_ERANGE, "plan needs more than %d tiles", max_tiles);
-        plan[++tiles] = w;
-    }
-    return tiles;
+    if (!ne) return wg_fail(WG_EINVAL, "a walker does not fit one wave (M=%d K=%d)", Mmax, Kmax);
+    return pack_plan(mass_off, edge_off, muscle_off, N, plan, max_tiles, PackCaps{64, 64 * ne, 64, RW_MAXW}, true, "tiles");
 }
 
 int wg_plan_ragged(const int32_t *mass_off, const int32_t *edge_off, const int32_t *muscle_off,
                    int32_t N, int32_t *plan, int32_t max_blocks) {
     if (!mass_off || !edge_off || !muscle_off || !plan || N < 0 || max_blocks < 1)
-        return fail(WG_EINVAL, "bad plan args");
-    int blocks = 0;
-    plan[0] = 0;
-    int w = 0;
-    while (w < N) {
-        int P = 0, E = 0, U = 0, n = 0;
-        while (w < N) {
-            const int m = mass_off[w + 1] - mass_off[w], k = edge_off[w + 1] - edge_off[w],
-                      a = muscle_off[w + 1] - muscle_off[w];
-            if (n > 0 && (P + m > RAG_P || E + k > RAG_E || U + a > RAG_U || n + 1 > RAG_W)) break;
-            P += m; E += k; U += a; n++; w++;
-        }
-        if (blocks + 1 > max_blocks) return fail(WG_ERANGE, "plan needs more than %d blocks", max_blocks);
-        plan[++blocks] = w;
-    }
-    return blocks;
+        return wg_fail(WG_EINVAL, "bad plan args");
+    return pack_plan(mass_off, edge_off, muscle_off, N, plan, max_blocks, PackCaps{RAG_P, RAG_E, RAG_U, RAG_W}, false,
+                     "blocks");
 }
 
 // the launch floor beside a small step (bench.py)
@@ -4448,7 +4418,7 @@ int wg_launch_floor(int32_t mode, int32_t blocks, int32_t threads, const float *
                     hipStream_t stream) {
     if (blocks < 1 || threads < 1 || threads > 1024 || n_launches < 0 || mode < 0 || mode > 2 ||
         (mode >= 1 && (!in || !out)))
-        return fail(WG_EINVAL, "bad floor launch (mode %d, %d x %d)", mode, blocks, threads);
+        return wg_fail(WG_EINVAL, "bad floor launch (mode %d, %d x %d)", mode, blocks, threads);
     for (int i = 0; i < n_launches; i++) {
         if (mode == 0)
             hipLaunchKernelGGL(floor_empty_kernel, dim3(blocks), dim3(threads), 0, stream, out);
@@ -4457,7 +4427,7 @@ int wg_launch_floor(int32_t mode, int32_t blocks, int32_t threads, const float *
         else
             hipLaunchKernelGGL(floor_busy_kernel, dim3(blocks), dim3(threads), 0, stream, in, out);
     }
-    return hipGetLastError() == hipSuccess ? 0 : fail(WG_EHIP, "floor launch failed");
+    return hipGetLastError() == hipSuccess ? 0 : wg_fail(WG_EHIP, "floor launch failed");
 }
 
 // diagnostic builds (-DWG_STAMPS): copy n lean-wave stamp records (8 x u64 each) to host memory; WG_EINVAL otherwise
@@ -4465,11 +4435,11 @@ int wg_debug_stamps(unsigned long long *host, int n) {
 #ifdef WG_STAMPS
     if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), (size_t)n * 8 * sizeof(unsigned long long), 0,
                             hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(WG_EHIP, "stamp copy failed");
+        return wg_fail(WG_EHIP, "stamp copy failed");
     return 0;
 #else
     (void)host; (void)n;
-    return fail(WG_EINVAL, "not a stamps build");
+    return wg_fail(WG_EINVAL, "not a stamps build");
 #endif
 }
 
@@ -4478,12 +4448,12 @@ long long wg_fix_launches(void) { return g_fix_launches.load(std::memory_order_r
 int wg_launch_geometry(const wg_batch *b, wg_launch_info *info) {
     int rc = validate(b);
     if (rc) return rc;
-    if (!info) return fail(WG_EINVAL, "null info");
+    if (!info) return wg_fail(WG_EINVAL, "null info");
     LeanGeo lg{};
     if (lean_geo(b, 0, &lg)) {   // the step kernel of uniform M | 64 batches
         info->threads = 64 * lg.wpb;
         info->walkers_per_block = lg.wpb * lg.wpw;
-        info->blocks = lean_blocks(b, lg);
+        info->blocks = lg.nblk;
         info->lds_bytes = lg.wpb * lg.slice;
         return 0;
     }
