@@ -130,6 +130,53 @@ def test_step_ranges_validates_every_range_before_launching():
     assert torch.equal(env.pos, before) and torch.equal(env.steps, steps0)
 
 
+def test_walker_range_structs_point_at_the_ranges_rows(monkeypatch):
+    """The wg_range structs step() (two ranges: WG_STEP_LANES=2) and prepare_run(lanes=2) hand the library, against
+    pointers computed here from the tensors: a uniform range's outputs and batch view are the tensors advanced by its
+    first walker's rows (130 walkers: ranges of 128 and 2), a ragged batch's ranges share the one batch struct and the
+    one outputs struct and differ in their slice of the plan."""
+    import ctypes as C
+    import torch
+    from walker_gym_amd.batched_env import BatchedPhysicsEnv
+    from walker_gym_amd.synthetic import canonical_walkers, ragged_walkers
+    monkeypatch.setenv("WG_STEP_LANES", "2")
+    monkeypatch.delenv("WG_RANGE_ISSUE", raising=False)
+    env = BatchedPhysicsEnv(canonical_walkers(130, seed=3), device="cuda:0", in3d=1, info_extras=True)
+    env.enable_auto_reset(final_obs=True)
+    b, D, M, cols = env.batch, env.obs_dim, env.batch.M, env.batch.A
+    acts = torch.zeros((1, env.N, cols), device="cuda:0")
+    row_bytes = {"obs": (env.obs, 4 * D), "final_obs": (env.final_obs, 4 * D), "reward": (env.reward, 4),
+                 "energy": (env.energy, 4), "done": (env.done, 1), "nonfinite": (env.nonfinite, 1),
+                 "reset": (env.reset_out, 1), "centroid": (env.centroid, 12), "momentum": (env.momentum, 12)}
+    for what, rng in (("step", env._step_plan(cols)["ranges"]), ("run", env.prepare_run(acts, 1, lanes=2)._args[0])):
+        assert len(rng) == 2, what
+        for i, (w0, n) in enumerate(((0, 128), (128, 2))):
+            o, sub = rng[i].outputs.contents, rng[i].batch.contents
+            for name, (t, nbytes) in row_bytes.items():
+                assert getattr(o, name) == t.data_ptr() + w0 * nbytes, (what, i, name)
+            assert o.steps is None and o.obs_stride == D, (what, i)      # (a uniform batch has no steps output)
+            assert sub.N == n and sub.pos == b.pos.data_ptr() + 12 * M * w0, (what, i)
+            assert rng[i].action_offset == w0 * cols and rng[i].plan is None and rng[i].plan_blocks == 0, (what, i)
+
+    env = BatchedPhysicsEnv(ragged_walkers(3000, seed=41, mmin=4, mmax=32), device="cuda:0", in3d=1)
+    b, cols = env.batch, env.batch.A
+    acts = torch.zeros((1, env.N, cols), device="cuda:0")
+    bounds = [0, b.plan_blocks // 2, b.plan_blocks]
+    for what, rng in (("step", env._step_plan(cols)["ranges"]), ("run", env.prepare_run(acts, 1, lanes=2)._args[0])):
+        assert len(rng) == 2, what
+        assert C.addressof(rng[0].outputs.contents) == C.addressof(rng[1].outputs.contents), what
+        assert rng[0].outputs.contents.obs == env.obs.data_ptr(), what
+        for i in range(2):
+            assert C.addressof(rng[i].batch.contents) == C.addressof(b.struct), (what, i)
+            assert rng[i].plan == b.plan.data_ptr() + 4 * bounds[i], (what, i)
+            assert rng[i].plan_blocks == bounds[i + 1] - bounds[i] and rng[i].action_offset == 0, (what, i)
+    # policy_loop's ranges: the same, split at _caller_bounds' blocks
+    bb = env._caller_bounds(2)[0]
+    for i, r in enumerate(env._ranges(2, env._own_outputs(), caller_rows=True)):
+        assert r.batch is b.struct and r.plan == b.plan.data_ptr() + 4 * bb[i] and r.plan_blocks == bb[i + 1] - bb[i]
+        assert r.action_offset == 0 and r.row0 == int(b.plan_host[bb[i]])
+
+
 @pytest.mark.parametrize("workload", ["canonical", "balance2d"])
 def test_survey_signature_entry_points_bit_exact(workload):
     """SURVEY §8(b)'s declared signatures (ABI 13): wg_step_simple(batch, action, params, n_steps, stream) for T steps

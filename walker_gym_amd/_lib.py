@@ -149,6 +149,11 @@ def load(path: str | None = None):
         return L
 
 
+def ptr(t):
+    """A device tensor's address as a C pointer argument (None stays NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def check(rc: int, what: str) -> int:
     if rc < 0:
         msg = load().wg_last_error().decode(errors="replace")

@@ -22,6 +22,12 @@ import torch
 from . import _lib
 from .device import DeviceBatch
 from .layout import HostLayout, pack
+from .ranges import WalkerRange, block_bounds, caller_bounds, uniform_bounds
+
+# info() keys a call leaves stale: the per-step info of a run with info=False or record buffers, and everything that is
+# "not this call's outputs" after a rollout into the caller's buffers
+_INFO_STALE = frozenset({"centroid_position", "total_energy", "momentum", "nonfinite"})
+_ROLLOUT_STALE = _INFO_STALE | {"reset", "final_obs"}
 
 
 @dataclass
@@ -104,7 +110,7 @@ class WalkerGraph:
         self.actions = actions            # kept alive: the graph reads it on every replay
         # the replayed steps write info['steps'] in caller order (env.steps_out) only when captured with info
         self._writes_steps = bool(info) and env.steps_out is not None
-        self._stale = frozenset() if info else frozenset({"centroid_position", "total_energy", "momentum", "nonfinite"})
+        self._stale = frozenset() if info else _INFO_STALE
 
     def replay(self) -> None:
         env = self._env
@@ -144,8 +150,7 @@ class PreparedRun:
     """run()'s C call with its arguments already built (BatchedPhysicsEnv.prepare_run): calling it issues the prepared
     steps again.  Like a WalkerGraph it refuses to run once the env's parameters or buffers have changed."""
 
-    def __init__(self, env: "BatchedPhysicsEnv", entry: str, fn, args, keep, steps_valid: bool, stale: set,
-                 thunk=None):
+    def __init__(self, env: "BatchedPhysicsEnv", entry: str, fn, args, keep, steps_valid: bool, stale, thunk=None):
         self._env, self._gen, self._struct = env, env._generation, env.batch.struct
         self._entry, self._fn, self._args, self._keep, self._thunk = entry, fn, args, keep, thunk
         self._steps_valid, self._stale = steps_valid, frozenset(stale)
@@ -196,6 +201,9 @@ class BatchedPhysicsEnv:
         # opt-in info (ABI 10): info['momentum'] (Point.momentum per walker, gym/engine.py:160-166) and
         # info['nonfinite'] (a walker whose state holds an inf / NaN; done is left as the reference computes it)
         self._extras = bool(info_extras)
+        # caches, each rebuilt when its key moves: step()'s arguments (_step_plan), the uniform walker-range views
+        # (_range_batches), wg_run_ranges' events (_range_events); and the last captured policy_loop
+        self._plan_cache = self._range_cache = self._run_events = self._policy_graph = None
         self._alloc_outputs()
         # the side streams of the default walker ranges, created now: a stream's hardware queue is bound when it is
         # created, and a process has few of them (GPU_MAX_HW_QUEUES = 4).  Created after an RCCL communicator
@@ -247,7 +255,7 @@ class BatchedPhysicsEnv:
         self._steps_at = -1
         self.momentum = torch.zeros((N, 3), dtype=torch.float32, device=dv) if self._extras else None
         self.nonfinite = torch.zeros(N, dtype=torch.bool, device=dv) if self._extras else None
-        if getattr(self, "final_obs", None) is not None:   # (auto-reset's terminal rows follow the row length)
+        if self.final_obs is not None:   # (auto-reset's terminal rows follow the row length)
             self.final_obs = torch.zeros((N, D), dtype=torch.float32, device=dv)
 
     def _make_pstruct(self) -> _lib.WgParams:
@@ -318,12 +326,9 @@ class BatchedPhysicsEnv:
         if pool is not None:
             pool.copy_(torch.randn(pool.shape, generator=self._gen, device=self.device) * self.sigma)
 
-    def _ar_out(self, w0: int = 0, w1: Optional[int] = None) -> dict:
-        """Auto-reset's outputs of walkers [w0, w1) (or none)."""
-        if not self._ar_mode:
-            return {}
-        w1 = self.N if w1 is None else w1
-        return {"reset": self.reset_out[w0:w1], "final_obs": None if self.final_obs is None else self.final_obs[w0:w1]}
+    def _ar_out(self) -> dict:
+        """Auto-reset's outputs (or none)."""
+        return {"reset": self.reset_out, "final_obs": self.final_obs} if self._ar_mode else {}
 
     def enable_info_extras(self) -> None:
         """Start producing info['momentum'] and info['nonfinite'] every step (one small per-walker pass after the
@@ -338,11 +343,16 @@ class BatchedPhysicsEnv:
 
     def _outputs(self, obs=None, reward=None, done=None, centroid=None, energy=None, obs_step=0, out_step=0,
                  pad_clean=False, steps=None, nonfinite=None, momentum=None, reset=None, final_obs=None):
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        p = _lib.ptr
         return _lib.WgOutputs(obs=p(obs), obs_stride=self.obs_dim, reward=p(reward), done=p(done),
                               centroid=p(centroid), energy=p(energy), obs_step=obs_step, out_step=out_step,
                               obs_pad_clean=int(pad_clean), steps=p(steps), nonfinite=p(nonfinite),
                               momentum=p(momentum), reset=p(reset), final_obs=p(final_obs))
+
+    def _own_outputs(self, pad_clean: bool = True, auto_reset: bool = True):
+        """The whole batch's WgOutputs over the env's own one-step tensors (step, policy_loop, observe)."""
+        return self._outputs(self.obs, self.reward, self.done, self.centroid, self.energy, pad_clean=pad_clean,
+                             steps=self.steps_out, **self._extra_out(), **(self._ar_out() if auto_reset else {}))
 
     @staticmethod
     def _range_outputs(o, w0: int):
@@ -358,12 +368,9 @@ class BatchedPhysicsEnv:
                               nonfinite=adv(o.nonfinite, w0), momentum=adv(o.momentum, 12 * w0),
                               reset=adv(o.reset, w0), final_obs=adv(o.final_obs, 4 * w0 * o.obs_stride))
 
-    def _extra_out(self, w0: int = 0, w1: Optional[int] = None) -> dict:
-        """The opt-in info outputs of walkers [w0, w1) (or none)."""
-        if not self._extras:
-            return {}
-        w1 = self.N if w1 is None else w1
-        return {"nonfinite": self.nonfinite[w0:w1], "momentum": self.momentum[w0:w1]}
+    def _extra_out(self) -> dict:
+        """The opt-in info outputs (or none)."""
+        return {"nonfinite": self.nonfinite, "momentum": self.momentum} if self._extras else {}
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -443,49 +450,56 @@ class BatchedPhysicsEnv:
         action columns): one wg_range per walker range (uniform: offset batch views; ragged: plan slices), the
         outputs, the action element offset of each range, its stream, and the fork / join events."""
         key = (self._generation, id(self.batch.struct), cols)
-        cached = getattr(self, "_plan_cache", None)
+        cached = self._plan_cache
         if cached is not None and cached["key"] == key:
             return cached
         lanes = self._step_lanes() if cols >= 0 else 1
-        self.reserve_streams(lanes)
-        b = self.batch
-        keep = []                                  # the ctypes structs the ranges point at
-        rng = (_lib.WgRange * lanes)()
-
-        def out(w0, w1):
-            o = self._outputs(self.obs[w0:w1], self.reward[w0:w1], self.done[w0:w1], self.centroid[w0:w1],
-                              self.energy[w0:w1], pad_clean=True,
-                              steps=None if self.steps_out is None else self.steps_out[w0:w1],
-                              **self._extra_out(w0, w1), **self._ar_out(w0, w1))
-            keep.append(o)
-            return C.pointer(o)
-        if lanes == 1 or b.ragged:
-            nb = b.plan_blocks
-            bounds = [nb * i // lanes for i in range(lanes)] + [nb]
-            o = out(0, self.N)
-            for i in range(lanes):
-                rng[i].batch, rng[i].outputs, rng[i].action_offset = C.pointer(b.struct), o, 0
-                rng[i].plan = None if b.plan is None else b.plan.data_ptr() + 4 * bounds[i]
-                rng[i].plan_blocks = bounds[i + 1] - bounds[i] if b.plan is not None else 0
-        else:
-            bounds = [0] + [((self.N * i // lanes) + 63) // 64 * 64 for i in range(1, lanes)] + [self.N]
-            for i in range(lanes):
-                w0, w1 = bounds[i], bounds[i + 1]
-                sub = b.sub_struct(w0, w1)
-                keep.append(sub)
-                rng[i].batch, rng[i].outputs = C.pointer(sub), out(w0, w1)
-                rng[i].action_offset, rng[i].plan, rng[i].plan_blocks = w0 * max(cols, 0), None, 0
-        side = self._side[:lanes - 1]
-        for i, st in enumerate(side):
-            rng[i + 1].stream = st.cuda_stream
-        events = [torch.cuda.Event() for _ in range(lanes)]
-        for ev in events:
-            ev.record()                            # materialise the hipEvent handle
+        ranges = self._ranges(lanes, self._own_outputs(), max(cols, 0))
+        events = self._make_events(lanes)
         self._pref = C.byref(self._pstruct)
-        self._plan_cache = {"key": key, "fn": _lib.load().wg_step_ranges, "ranges": rng, "n": lanes, "side": side,
-                            "keep": keep, "events_obj": events,
-                            "events": (C.c_void_p * lanes)(*[ev.cuda_event for ev in events])}
+        self._plan_cache = {"key": key, "fn": _lib.load().wg_step_ranges, "ranges": self._wg_ranges(ranges), "n": lanes,
+                            "side": self._side[:lanes - 1], "keep": ranges, "events_obj": events[0], "events": events[1]}
         return self._plan_cache
+
+    def _ranges(self, lanes: int, o_full, cols: int = 0, caller_rows: bool = False) -> list:
+        """The one description of the batch as `lanes` walker ranges (ranges.WalkerRange) writing to o_full, the whole
+        batch's WgOutputs, and reading [N, cols] actions: step, run (both issue orders) and policy_loop all step these.
+        A uniform batch splits at walker bounds: each range has its cached WgBatch view, o_full advanced to its first
+        walker and its action offset.  A ragged batch splits its block -> walker plan: every range has the one batch
+        struct and o_full (the kernels index both by caller row), and a slice of the plan; caller_rows moves the splits
+        to where the ranges are slices of caller rows (_caller_bounds; policy_loop hands each range its own rows)."""
+        b = self.batch
+        self.reserve_streams(lanes)
+        if b.ragged:
+            bb, contiguous = self._caller_bounds(lanes) if caller_rows else \
+                (block_bounds(b.plan_blocks, lanes), [None] * lanes)
+            first, plan = [int(b.plan_host[k]) for k in bb], b.plan.data_ptr()
+            return [WalkerRange(b.struct, o_full, plan + 4 * bb[i], bb[i + 1] - bb[i], 0, first[i],
+                                first[i + 1] - first[i], contiguous[i], i) for i in range(lanes)]
+        if lanes == 1:
+            return [WalkerRange(b.struct, o_full, None, 0, 0, 0, self.N, True, 0)]
+        bounds = uniform_bounds(self.N, lanes)
+        subs = self._range_batches(lanes, bounds)
+        return [WalkerRange(subs[i], self._range_outputs(o_full, w0), None, 0, w0 * cols, w0, bounds[i + 1] - w0, True, i)
+                for i, w0 in enumerate(bounds[:-1])]
+
+    def _wg_ranges(self, ranges):
+        """The wg_range array of wg_step_ranges / wg_run_ranges over `ranges` (which it points into: keep them), range
+        0 on the current stream."""
+        streams = [torch.cuda.current_stream(self.device)] + self._side
+        rng = (_lib.WgRange * len(ranges))()
+        for g, r in zip(rng, ranges):
+            g.batch, g.outputs, g.action_offset = C.pointer(r.batch), C.pointer(r.outputs), r.action_offset
+            g.plan, g.plan_blocks, g.stream = r.plan, r.plan_blocks, streams[r.slot].cuda_stream
+        return rng
+
+    @staticmethod
+    def _make_events(n: int):
+        """n torch events and the array of their hipEvent handles (fork / join events of the range entries)."""
+        objs = [torch.cuda.Event() for _ in range(n)]
+        for e in objs:
+            e.record()                       # materialise the hipEvent handle
+        return objs, (C.c_void_p * n)(*[e.cuda_event for e in objs])
 
     def rollout(self, actions, obs_out=None, reward_out=None, done_out=None, lanes: Optional[int] = None,
                 resident: bool = True, reset_out=None):
@@ -503,7 +517,7 @@ class BatchedPhysicsEnv:
         dv = self.device
         self._steps_at = -1   # the step counters move without the steps output: info() gathers them afterwards
         # (the per-step outputs went to the rollout's buffers: the env's own centroid / energy / extras are not current)
-        self._stale = frozenset({"centroid_position", "total_energy", "momentum", "nonfinite", "reset", "final_obs"})
+        self._stale = _ROLLOUT_STALE
         # zero-filled: a ragged batch's short rows then need only their own values written each step
         clean = obs_out is None
         obs_out = torch.zeros((T, self.N, self.obs_dim), dtype=torch.float32, device=dv) if obs_out is None else obs_out
@@ -528,9 +542,7 @@ class BatchedPhysicsEnv:
             return obs_out, reward_out, done_out
         _lib.check(getattr(_lib.load(), entry)(
             C.byref(self.batch.struct), C.byref(self._pstruct), C.c_void_p(actions.data_ptr()), cols, cols,
-            self.N * cols, C.byref(o), T,
-            None if self.batch.plan is None else C.c_void_p(self.batch.plan.data_ptr()),
-            self.batch.plan_blocks, self._stream()), entry)
+            self.N * cols, C.byref(o), T, *self.batch.plan_args(), self._stream()), entry)
         return obs_out, reward_out, done_out
 
     def rollout_policy(self, policy, n_steps: int, obs_out=None, reward_out=None, done_out=None,
@@ -551,52 +563,61 @@ class BatchedPhysicsEnv:
         MLPPolicy's parameter sets to each walker range's caller rows).  Also ValueError (WG_ERANGE) when the rows,
         hidden vectors and actions of a workgroup's walkers beside the kernel's own LDS pass 80 KiB (very wide walkers
         with a large hidden layer)."""
+        N, dv = self.N, self.device
+        pol, o, T = self._resident_policy("rollout_policy", False, policy, n_steps, None, obs_out, reward_out, done_out,
+                                          action_out)
+        returns = torch.empty(N, dtype=torch.float32, device=dv)
+        lengths = torch.empty(N, dtype=torch.int32, device=dv)
+        pol.return_out, pol.length_out = _lib.ptr(returns), _lib.ptr(lengths)
+        _lib.check(_lib.load().wg_rollout_policy(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
+                                                 C.byref(o), T, self._stream()), "wg_rollout_policy")
+        self._steps_at = -1   # (as rollout(): the env's one-step outputs are not this call's; a refused call ran nothing)
+        self._stale = _ROLLOUT_STALE
+        return {"returns": returns, "lengths": lengths}
+
+    def _resident_policy(self, entry: str, auto_reset: bool, policy, n_steps, episode_slots, obs_out, reward_out,
+                         done_out, action_out, reset_out=None, final_obs_out=None):
+        """The shared prelude of rollout_policy / rollout_episodes (`entry`, which needs auto-reset off / on): every
+        refusal in one order, then (the WgPolicy struct, the WgOutputs over the optional [T, ...] buffers, T)."""
         from .policy import MLPPolicy
         alt = "use policy_loop(policy, n_steps), which closes the loop with one step launch per step on any batch"
         if not isinstance(policy, MLPPolicy):
-            raise ValueError(f"rollout_policy needs an MLPPolicy; for another callable {alt}")
+            raise ValueError(f"{entry} needs an MLPPolicy; for another callable {alt}")
         T = int(n_steps)
         if T < 1:
-            raise ValueError(f"rollout_policy: n_steps {n_steps} < 1")
+            raise ValueError(f"{entry}: n_steps {n_steps} < 1")
+        if episode_slots is not None and int(episode_slots) < 0:
+            raise ValueError(f"{entry}: episode_slots {episode_slots} < 0")
         if not self.resident_ok():
-            raise ValueError("rollout_policy: only batches of the resident lean kernel (uniform, M dividing 64 with "
+            raise ValueError(f"{entry}: only batches of the resident lean kernel (uniform, M dividing 64 with "
                              f"M >= 4, spring_mode 0, pair_mode 0, WG_LEAN not 0); {alt}")
-        if self._ar_mode:
-            raise ValueError(f"rollout_policy: auto-reset is enabled and the resident loop has no reset tail; {alt}")
+        if self._ar_mode and not auto_reset:
+            raise ValueError(f"{entry}: auto-reset is enabled and the resident loop has no reset tail; {alt}")
+        if auto_reset and not self._ar_mode:
+            raise ValueError(f"{entry}: auto-reset is off (enable_auto_reset first); without episode roll-over "
+                             "use rollout_policy")
         if policy.D != self.obs_dim:
-            raise ValueError(f"rollout_policy: the policy takes {policy.D} inputs, the observation rows have "
-                             f"{self.obs_dim}")
+            raise ValueError(f"{entry}: the policy takes {policy.D} inputs, the observation rows have {self.obs_dim}")
         if policy.C > self.batch.A:
-            raise ValueError(f"rollout_policy: the policy has {policy.C} outputs, the walkers {self.batch.A} muscles")
+            raise ValueError(f"{entry}: the policy has {policy.C} outputs, the walkers {self.batch.A} muscles")
         if self.N % policy.G != 0:
-            raise ValueError(f"rollout_policy: {policy.G} parameter sets do not divide N = {self.N}; {alt}")
-        dv, N = self.device, self.N
+            raise ValueError(f"{entry}: {policy.G} parameter sets do not divide N = {self.N}; {alt}")
+        dv, N, D = self.device, self.N, self.obs_dim
         for name in ("w1", "b1", "w2", "b2"):
             t = getattr(policy, name)
             if t is not None:
                 require_tensor(t, f"policy.{name}", dv, torch.float32)
-        if obs_out is not None:
-            require_tensor(obs_out, "obs_out", dv, torch.float32, (T, N, self.obs_dim))
-        if reward_out is not None:
-            require_tensor(reward_out, "reward_out", dv, torch.float32, (T, N))
-        if done_out is not None:
-            require_tensor(done_out, "done_out", dv, torch.uint8, (T, N))
-        if action_out is not None:
-            require_tensor(action_out, "action_out", dv, torch.float32, (T, N, policy.C))
-        returns = torch.empty(N, dtype=torch.float32, device=dv)
-        lengths = torch.empty(N, dtype=torch.int32, device=dv)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        pol = _lib.WgPolicy(n_sets=policy.G, obs_dim=policy.D, hidden=policy.H, act_dim=policy.C, w1=p(policy.w1),
-                            b1=p(policy.b1), w2=p(policy.w2), b2=p(policy.b2), act_limit=policy.act_limit,
-                            action_out=p(action_out), action_out_step=N * policy.C, return_out=p(returns),
-                            length_out=p(lengths))
-        o = self._outputs(obs_out, reward_out, done_out, None, None, obs_step=N * self.obs_dim, out_step=N,
-                          pad_clean=True)
-        _lib.check(_lib.load().wg_rollout_policy(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
-                                                 C.byref(o), T, self._stream()), "wg_rollout_policy")
-        self._steps_at = -1   # (as rollout(): the env's one-step outputs are not this call's; a refused call ran nothing)
-        self._stale = frozenset({"centroid_position", "total_energy", "momentum", "nonfinite", "reset", "final_obs"})
-        return {"returns": returns, "lengths": lengths}
+        for name, t, dt, shape in (("obs_out", obs_out, torch.float32, (T, N, D)),
+                                   ("reward_out", reward_out, torch.float32, (T, N)),
+                                   ("done_out", done_out, torch.uint8, (T, N)),
+                                   ("action_out", action_out, torch.float32, (T, N, policy.C)),
+                                   ("reset_out", reset_out, torch.uint8, (T, N)),
+                                   ("final_obs_out", final_obs_out, torch.float32, (T, N, D))):
+            if t is not None:
+                require_tensor(t, name, dv, dt, shape)
+        o = self._outputs(obs_out, reward_out, done_out, None, None, obs_step=N * D, out_step=N, pad_clean=True,
+                          reset=reset_out, final_obs=final_obs_out)
+        return policy.struct(N, action_out), o, T
 
     def rollout_episodes(self, policy, n_steps: int, obs_out=None, reward_out=None, done_out=None, action_out=None,
                          reset_out=None, final_obs_out=None, episode_slots: int = 0) -> dict:
@@ -616,41 +637,10 @@ class BatchedPhysicsEnv:
 
         ValueError (nothing launched) with auto-reset off (use rollout_policy), and for everything rollout_policy
         refuses on its own account: the batch, the policy's fit, the buffers, the LDS budget."""
-        from .policy import MLPPolicy
-        alt = "use policy_loop(policy, n_steps), which closes the loop with one step launch per step on any batch"
-        if not isinstance(policy, MLPPolicy):
-            raise ValueError(f"rollout_episodes needs an MLPPolicy; for another callable {alt}")
-        T, slots = int(n_steps), int(episode_slots)
-        if T < 1:
-            raise ValueError(f"rollout_episodes: n_steps {n_steps} < 1")
-        if slots < 0:
-            raise ValueError(f"rollout_episodes: episode_slots {episode_slots} < 0")
-        if not self.resident_ok():
-            raise ValueError("rollout_episodes: only batches of the resident lean kernel (uniform, M dividing 64 with "
-                             f"M >= 4, spring_mode 0, pair_mode 0, WG_LEAN not 0); {alt}")
-        if not self._ar_mode:
-            raise ValueError("rollout_episodes: auto-reset is off (enable_auto_reset first); without episode roll-over "
-                             "use rollout_policy")
-        if policy.D != self.obs_dim:
-            raise ValueError(f"rollout_episodes: the policy takes {policy.D} inputs, the observation rows have "
-                             f"{self.obs_dim}")
-        if policy.C > self.batch.A:
-            raise ValueError(f"rollout_episodes: the policy has {policy.C} outputs, the walkers {self.batch.A} muscles")
-        if self.N % policy.G != 0:
-            raise ValueError(f"rollout_episodes: {policy.G} parameter sets do not divide N = {self.N}; {alt}")
-        dv, N, D = self.device, self.N, self.obs_dim
-        for name in ("w1", "b1", "w2", "b2"):
-            t = getattr(policy, name)
-            if t is not None:
-                require_tensor(t, f"policy.{name}", dv, torch.float32)
-        for name, t, dt, shape in (("obs_out", obs_out, torch.float32, (T, N, D)),
-                                   ("reward_out", reward_out, torch.float32, (T, N)),
-                                   ("done_out", done_out, torch.uint8, (T, N)),
-                                   ("action_out", action_out, torch.float32, (T, N, policy.C)),
-                                   ("reset_out", reset_out, torch.uint8, (T, N)),
-                                   ("final_obs_out", final_obs_out, torch.float32, (T, N, D))):
-            if t is not None:
-                require_tensor(t, name, dv, dt, shape)
+        N, dv = self.N, self.device
+        pol, o, T = self._resident_policy("rollout_episodes", True, policy, n_steps, episode_slots, obs_out, reward_out,
+                                          done_out, action_out, reset_out, final_obs_out)
+        slots = int(episode_slots)
         res = {"return_sum": torch.empty(N, dtype=torch.float32, device=dv),
                "length_sum": torch.empty(N, dtype=torch.int32, device=dv),
                "episodes": torch.empty(N, dtype=torch.int32, device=dv),
@@ -659,20 +649,15 @@ class BatchedPhysicsEnv:
         if slots > 0:
             res["ep_returns"] = torch.full((N, slots), float("nan"), dtype=torch.float32, device=dv)
             res["ep_lengths"] = torch.full((N, slots), -1, dtype=torch.int32, device=dv)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        pol = _lib.WgPolicy(n_sets=policy.G, obs_dim=policy.D, hidden=policy.H, act_dim=policy.C, w1=p(policy.w1),
-                            b1=p(policy.b1), w2=p(policy.w2), b2=p(policy.b2), act_limit=policy.act_limit,
-                            action_out=p(action_out), action_out_step=N * policy.C, return_out=None, length_out=None)
+        p = _lib.ptr
         st = _lib.WgEpisodeStats(return_sum=p(res["return_sum"]), length_sum=p(res["length_sum"]),
                                  episodes_done=p(res["episodes"]), tail_return=p(res["tail_return"]),
                                  tail_length=p(res["tail_length"]), ep_return=p(res.get("ep_returns")),
                                  ep_length=p(res.get("ep_lengths")), ep_slots=slots)
-        o = self._outputs(obs_out, reward_out, done_out, None, None, obs_step=N * D, out_step=N, pad_clean=True,
-                          reset=reset_out, final_obs=final_obs_out)
         _lib.check(_lib.load().wg_rollout_episodes(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
                                                    C.byref(o), C.byref(st), T, self._stream()), "wg_rollout_episodes")
         self._steps_at = -1   # (as rollout_policy(): only after the call was accepted)
-        self._stale = frozenset({"centroid_position", "total_energy", "momentum", "nonfinite", "reset", "final_obs"})
+        self._stale = _ROLLOUT_STALE
         return res
 
     def run(self, actions, n_steps: int, info: bool = True, lanes: Optional[int] = None, resident: bool = False,
@@ -709,12 +694,12 @@ class BatchedPhysicsEnv:
         entry = "wg_rollout" if resident else "wg_step"
         so = self.steps_out if info else None
         rew, done, cen, en, out_step = self.reward, self.done, self.centroid, self.energy, 0
-        stale = set()
+        stale = frozenset()
         if record is not None:
             S = int(n_steps)
             if S < 1:
                 raise ValueError("run(record=...) needs n_steps >= 1")
-            stale = {"centroid_position", "total_energy", "momentum", "nonfinite"}
+            stale = _INFO_STALE
             rew, done = record["reward"], record["done"]
             require_tensor(rew, "record['reward']", self.device, torch.float32, (S, self.N))
             if not isinstance(done, torch.Tensor) or done.dtype not in (torch.bool, torch.uint8):
@@ -730,7 +715,7 @@ class BatchedPhysicsEnv:
             so, out_step = None, self.N   # (the steps output would need [n_steps, N] too: info() gathers them)
         if not info:
             cen = en = None
-            stale |= {"centroid_position", "total_energy", "momentum", "nonfinite"}
+            stale = _INFO_STALE
         # the opt-in info extras follow the last step only when the outputs are overwritten each step (no record)
         # (auto-reset's outputs likewise: a record run strides its outputs per step, so it takes record['reset'] [n_steps,
         # N] uint8 / bool, if given, and no final_obs)
@@ -766,8 +751,7 @@ class BatchedPhysicsEnv:
         # (a resident launch writes the steps output only where the resident kernel runs: uniform batches, which
         # have no steps_out)
         args = (C.byref(self.batch.struct), C.byref(self._pstruct), actions.data_ptr(), cols, cols,
-                0 if T == 1 else self.N * cols, C.byref(o), n_steps,
-                None if self.batch.plan is None else self.batch.plan.data_ptr(), self.batch.plan_blocks,
+                0 if T == 1 else self.N * cols, C.byref(o), n_steps, *self.batch.plan_args(),
                 torch.cuda.current_stream(self.device).cuda_stream)
         return PreparedRun(self, entry, getattr(_lib.load(), entry), args, [o] + pins, steps_valid, stale)
 
@@ -821,18 +805,10 @@ class BatchedPhysicsEnv:
         """The per-range WgBatch views of a uniform batch, cached per batch struct (rebuilt whenever the batch's
         arrays are: enable_radius) and walker ranges; the cache holds the struct, so its identity is not reused."""
         key, st = (self._generation, tuple(bounds)), self.batch.struct
-        cached = getattr(self, "_range_cache", None)
+        cached = self._range_cache
         if cached is None or cached[0] != key or cached[1] is not st:
             cached = self._range_cache = (key, st, [self.batch.sub_struct(bounds[i], bounds[i + 1]) for i in range(lanes)])
         return cached[2]
-
-    def _range_bounds(self, lanes: int) -> list:
-        """Walker ranges of run(): plan-block bounds (ragged: the same batch, a slice of its block -> walker plan) or
-        walker bounds on multiples of 64 (uniform)."""
-        if self.batch.ragged:
-            nb = self.batch.plan_blocks
-            return [nb * i // lanes for i in range(lanes)] + [nb]
-        return [0] + [((self.N * i // lanes) + 63) // 64 * 64 for i in range(1, lanes)] + [self.N]
 
     def _run_ranges_args(self, actions, n_steps: int, o_full, lanes: int):
         """wg_run_ranges' arguments for n_steps of `lanes` walker ranges on the calling stream and the side streams:
@@ -840,27 +816,11 @@ class BatchedPhysicsEnv:
         wg_step call each: the last range then starts only after the host has issued every launch of the ranges
         before it; scripts/issue_ab.sh).  Returns (function, arguments, the ctypes objects they point at)."""
         T, n, cols = actions.shape
-        cur = torch.cuda.current_stream(self.device)
-        self.reserve_streams(lanes)
-        ragged = self.batch.ragged
-        bounds = self._range_bounds(lanes)
-        rng, keep = (_lib.WgRange * lanes)(), []
-        subs = None if ragged else self._range_batches(lanes, bounds)
-        for i in range(lanes):
-            w0, w1 = bounds[i], bounds[i + 1]
-            if ragged:
-                o, rng[i].batch, rng[i].action_offset = o_full, C.pointer(self.batch.struct), 0
-                rng[i].plan, rng[i].plan_blocks = self.batch.plan.data_ptr() + 4 * w0, w1 - w0
-            else:
-                o, rng[i].batch, rng[i].action_offset = self._range_outputs(o_full, w0), C.pointer(subs[i]), w0 * cols
-                rng[i].plan, rng[i].plan_blocks = None, 0
-            keep.append(o)
-            rng[i].outputs = C.pointer(o)
-            rng[i].stream = (cur if i == 0 else self._side[i - 1]).cuda_stream
-        keep += [rng, o_full, actions, subs]
+        ranges = self._ranges(lanes, o_full, cols)
+        rng = self._wg_ranges(ranges)
         args = (rng, lanes, C.byref(self._pstruct), actions.data_ptr(), cols, cols, 0 if T == 1 else self.N * cols,
                 n_steps, self._range_events(lanes))
-        return _lib.load().wg_run_ranges, args, keep
+        return _lib.load().wg_run_ranges, args, [ranges, rng, o_full, actions]
 
     def _run_lanes(self, actions, n_steps: int, o_full, lanes: int, entry: str = "wg_step", only: Optional[int] = None):
         """n_steps with the walkers split into `lanes` contiguous ranges, each stepped by its own stream, one C call
@@ -872,29 +832,20 @@ class BatchedPhysicsEnv:
         alone, on the calling stream (graph() captures one graph per range)."""
         T, n, cols = actions.shape
         cur = torch.cuda.current_stream(self.device)
-        self.reserve_streams(lanes)
-        L = _lib.load()
-        ragged = self.batch.ragged
-        bounds = self._range_bounds(lanes)
+        fn = getattr(_lib.load(), entry)
+        ranges = self._ranges(lanes, o_full, cols)
         capturing = torch.cuda.is_current_stream_capturing()
         start = torch.cuda.Event()
         if only is None:
             start.record(cur)
         done = []
-        for i in (range(lanes) if only is None else [only]):
-            w0, w1 = bounds[i], bounds[i + 1]
-            st = cur if (i == 0 or only is not None) else self._side[i - 1]
+        for r in (ranges if only is None else [ranges[only]]):
+            st = cur if (r.slot == 0 or only is not None) else self._side[r.slot - 1]
             if st is not cur:
                 st.wait_event(start)
-            if ragged:
-                sub, o, act = self.batch.struct, o_full, C.c_void_p(actions.data_ptr())
-                plan, nblk = C.c_void_p(self.batch.plan.data_ptr() + 4 * w0), w1 - w0
-            else:
-                sub, o = self.batch.sub_struct(w0, w1), self._range_outputs(o_full, w0)
-                act, plan, nblk = C.c_void_p(actions.data_ptr() + 4 * w0 * cols), None, 0
-            _lib.check(getattr(L, entry)(C.byref(sub), C.byref(self._pstruct), act, cols, cols,
-                                         0 if T == 1 else self.N * cols, C.byref(o), n_steps, plan, nblk,
-                                         C.c_void_p(st.cuda_stream)), entry)
+            _lib.check(fn(C.byref(r.batch), C.byref(self._pstruct), C.c_void_p(actions.data_ptr() + 4 * r.action_offset),
+                          cols, cols, 0 if T == 1 else self.N * cols, C.byref(r.outputs), n_steps, r.plan,
+                          r.plan_blocks, C.c_void_p(st.cuda_stream)), entry)
             if st is not cur:
                 if not capturing:
                     actions.record_stream(st)   # the allocator must not recycle it before the side stream is done
@@ -907,13 +858,9 @@ class BatchedPhysicsEnv:
     def _range_events(self, lanes: int):
         """wg_run_ranges' fork / join events (hipEvent handles of torch events, created once per env and reused: each
         call records and waits on them stream-ordered)."""
-        ev = getattr(self, "_run_events", None)
-        if ev is None or len(ev[0]) < lanes:
-            objs = [torch.cuda.Event() for _ in range(lanes)]
-            for e in objs:
-                e.record()                       # materialise the hipEvent handle
-            ev = self._run_events = (objs, (C.c_void_p * lanes)(*[e.cuda_event for e in objs]))
-        return ev[1]
+        if self._run_events is None or len(self._run_events[0]) < lanes:
+            self._run_events = self._make_events(lanes)
+        return self._run_events[1]
 
     def policy_loop(self, policy, n_steps: int, lanes: Optional[int] = None, graph: bool = False):
         """A closed loop with a per-walker policy, the walker ranges pipelined: at every step, each range computes its
@@ -947,48 +894,26 @@ class BatchedPhysicsEnv:
         ranges (one range runs on the calling stream as it is)."""
         b = self.batch
         lanes = self._lanes(lanes)
-        self.reserve_streams(lanes)
         L = _lib.load()
         pref, dev, f32 = C.byref(self._pstruct), self.device, torch.float32
-        args = []   # per range: (obs rows or None, row index or None, n_r, batch ref, outputs ref, plan ptr, blocks)
-        keep = []   # the ctypes structs the refs point at
-        aoff = []   # per range: the caller row its actions start at (the kernel indexes a ragged batch's actions by
-        #             caller row, so a slice's action pointer is moved back by that many rows)
-        if b.ragged:
-            bb, contiguous = self._caller_bounds(lanes)
-            o = self._outputs(self.obs, self.reward, self.done, self.centroid, self.energy, pad_clean=True,
-                              steps=self.steps_out, **self._extra_out())
-            keep.append(o)
-            for i in range(lanes):
-                s0, s1 = int(b.plan_host[bb[i]]), int(b.plan_host[bb[i + 1]])
-                if contiguous[i]:   # caller rows s0 .. s1 - 1: a row slice
-                    obs_r, idx = self.obs[s0:s1], None
-                else:               # the caller rows of stored walkers s0 .. s1 - 1, scattered
-                    obs_r, idx = None, b._perm["row"][s0:s1]
-                aoff.append(s0)
-                args.append((obs_r, idx, s1 - s0, C.byref(b.struct), C.byref(o),
-                             C.c_void_p(b.plan.data_ptr() + 4 * bb[i]), bb[i + 1] - bb[i]))
-        else:
-            bounds = [0] + [((self.N * i // lanes) + 63) // 64 * 64 for i in range(1, lanes)] + [self.N]
-            for i in range(lanes):
-                w0, w1 = bounds[i], bounds[i + 1]
-                sub = b.sub_struct(w0, w1)
-                o = self._outputs(self.obs[w0:w1], self.reward[w0:w1], self.done[w0:w1], self.centroid[w0:w1],
-                                  self.energy[w0:w1], pad_clean=True, **self._extra_out(w0, w1),
-                                  **self._ar_out(w0, w1))
-                keep += [sub, o]
-                args.append((self.obs[w0:w1], None, w1 - w0, C.byref(sub), C.byref(o), None, 0))
-                aoff.append(0)   # (a sub-batch indexes its actions from its own first walker)
+        # (a ragged batch has no auto-reset: its _own_outputs hold none of auto-reset's outputs)
+        ranges = self._ranges(lanes, self._own_outputs(), caller_rows=True)
+        # per range: (obs rows or None, row index or None, n_r, batch ref, outputs ref, plan ptr, blocks): its caller
+        # rows are a slice of obs, or (a ragged range of scattered rows) the rows its stored walkers name
+        args = [(self.obs[r.row0:r.row0 + r.n] if r.contiguous else None,
+                 None if r.contiguous else b._perm["row"][r.row0:r.row0 + r.n], r.n, C.byref(r.batch),
+                 C.byref(r.outputs), None if r.plan is None else C.c_void_p(r.plan), r.plan_blocks) for r in ranges]
+        # per range: the caller row its actions start at: the kernel indexes a ragged batch's actions by caller row, so
+        # a slice's action pointer is moved back by that many rows (a uniform range's view indexes from its own first)
+        aoff = [r.row0 if b.ragged else 0 for r in ranges]
 
         # a policy whose output depends on the walker index (MLPPolicy with G > 1): one bound policy per range, made
         # here (outside any capture), for the range's caller rows: a slice [row0, row0 + n_r), or a scattered ragged
         # range's row index
         pols = [policy] * lanes
         if hasattr(policy, "for_rows") and hasattr(policy, "for_row_index"):
-            row0 = [int(b.plan_host[bb[i]]) for i in range(lanes)] if b.ragged else bounds[:lanes]
-            pols = [policy.for_rows(row0[i], self.N, args[i][2]) if args[i][1] is None
-                    else policy.for_row_index(args[i][1], self.N)
-                    for i in range(lanes)]
+            pols = [policy.for_rows(r.row0, self.N, r.n) if r.contiguous else policy.for_row_index(a[1], self.N)
+                    for r, a in zip(ranges, args)]
 
         def check(a, n_r):
             require_tensor(a, "policy actions", dev, f32)
@@ -1066,9 +991,17 @@ class BatchedPhysicsEnv:
         if not graph:
             body(cur)
             return
-        # one graph per walker range, each replayed on a stream of its own: the ranges share nothing, and two graphs
-        # on two streams overlap as the eager ranges do (one graph with the ranges as parallel branches replayed them
-        # one after the other: 48.1 against 38.1 us per canonical step, round 4)
+        # (kept until the next call: the replay may still be running)
+        self._policy_graph = self._capture_ranges(lanes, lambda st, r: body(st, only=r))
+        self._policy_graph.replay()
+        return self._policy_graph   # replay() runs the same n_steps again from the current state
+
+    def _capture_ranges(self, lanes: int, body) -> _RangeGraphs:
+        """One HIP graph per walker range, body(stream, r) captured on a stream of its own (off the default stream, as
+        torch requires): the ranges share nothing, and two graphs on two streams overlap as the eager ranges do (one
+        graph with the ranges as parallel branches replayed them one after the other: 48.1 against 38.1 us per canonical
+        step, round 4)."""
+        cur = torch.cuda.current_stream(self.device)
         parts = []
         for r in range(lanes):
             g = torch.cuda.CUDAGraph()
@@ -1076,36 +1009,16 @@ class BatchedPhysicsEnv:
             st.wait_stream(cur)
             with torch.cuda.stream(st):
                 with torch.cuda.graph(g, stream=st):
-                    body(st, only=r)
+                    body(st, r)
             cur.wait_stream(st)
             parts.append((g, st))
-        self._policy_graph = _RangeGraphs(parts, cur)   # (kept until the next call: the replay may still be running)
-        self._policy_graph.replay()
-        return self._policy_graph   # replay() runs the same n_steps again from the current state
+        return _RangeGraphs(parts, cur)
 
     def _caller_bounds(self, lanes: int):
-        """Plan-block bounds of `lanes` ragged walker ranges, each split moved to the nearest block whose stored prefix
-        holds exactly the caller rows before it (within an eighth of a range), and per range whether its walkers are a
-        contiguous slice of caller rows."""
+        """Plan-block bounds of `lanes` ragged walker ranges with the splits moved to where the ranges are slices of
+        caller rows, and per range whether it is one (ranges.caller_bounds)."""
         b = self.batch
-        nb, plan = b.plan_blocks, b.plan_host
-        if b.row is None:
-            ok = np.ones(nb + 1, bool)   # identity order: every block boundary
-        else:
-            rowmax = np.maximum.accumulate(b.host.row)
-            ok = np.zeros(nb + 1, bool)
-            ok[0] = ok[nb] = True
-            s = plan[1:nb].astype(np.int64)
-            ok[1:nb] = rowmax[s - 1] == s - 1
-        good = np.flatnonzero(ok)
-        bb = [0]
-        for i in range(1, lanes):
-            t = nb * i // lanes
-            c = int(good[np.argmin(np.abs(good - t))])
-            bb.append(c if abs(c - t) <= max(1, nb // (8 * lanes)) and bb[-1] < c < nb else t)
-        bb.append(nb)
-        contiguous = [bool(ok[bb[i]] and ok[bb[i + 1]]) for i in range(lanes)]
-        return bb, contiguous
+        return caller_bounds(b.plan_blocks, b.plan_host, b.host.row, lanes)
 
     def graph(self, actions, n_steps: int, info: bool = True, lanes: Optional[int] = None):
         """Capture run(actions, n_steps) into a HIP graph (torch.cuda.CUDAGraph over the ROCm runtime) and
@@ -1114,28 +1027,16 @@ class BatchedPhysicsEnv:
         refilled in place); the graph reads the batch and output tensors this env owns and the parameters as
         captured, so set_params() (or any reallocation of the outputs) makes replay() raise."""
         lanes = self._lanes(lanes)
-        cur = torch.cuda.current_stream(self.device)
         steps_at, stale = self._steps_at, self._stale   # capture runs nothing: the outputs' validity is unchanged
-        parts = []
-        for r in range(lanes):   # one graph per walker range, each replayed on a stream of its own (_RangeGraphs)
-            g = torch.cuda.CUDAGraph()
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):           # capture off the default stream, as torch requires
-                with torch.cuda.graph(g, stream=side):
-                    self.run(actions, n_steps, info=info, lanes=lanes, _only=r if lanes > 1 else None)
-            cur.wait_stream(side)
-            parts.append((g, side))
+        graphs = self._capture_ranges(lanes, lambda st, r: self.run(actions, n_steps, info=info, lanes=lanes,
+                                                                    _only=r if lanes > 1 else None))
         self._steps_at, self._stale = steps_at, stale
-        return WalkerGraph(self, _RangeGraphs(parts, cur), actions, info=info)
+        return WalkerGraph(self, graphs, actions, info=info)
 
     def observe(self):
-        o = self._outputs(self.obs, self.reward, self.done, self.centroid, self.energy, steps=self.steps_out,
-                          **self._extra_out())
-        _lib.check(_lib.load().wg_observe(
-            C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(o),
-            None if self.batch.plan is None else C.c_void_p(self.batch.plan.data_ptr()),
-            self.batch.plan_blocks, self._stream()), "wg_observe")
+        o = self._own_outputs(pad_clean=False, auto_reset=False)
+        _lib.check(_lib.load().wg_observe(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(o),
+                                          *self.batch.plan_args(), self._stream()), "wg_observe")
         self._steps_at = self.batch.version
         self._stale = frozenset()
         return self.obs, self.reward, self.done, self.info()
@@ -1152,8 +1053,7 @@ class BatchedPhysicsEnv:
             mask = self.batch.to_stored("walker", torch.as_tensor(mask).to(self.device, torch.uint8)).contiguous()
         _lib.check(_lib.load().wg_reset(
             C.byref(self.batch.struct), C.byref(self._pstruct),
-            None if noise is None else C.c_void_p(noise.data_ptr()),
-            None if mask is None else C.c_void_p(mask.data_ptr()), self._stream()), "wg_reset")
+            _lib.ptr(noise), _lib.ptr(mask), self._stream()), "wg_reset")
         return self.observe()[0]
 
     def seed(self, seed: Optional[int] = None) -> Sequence[int]:

@@ -25,10 +25,6 @@ def _to_dev(a: np.ndarray, device) -> torch.Tensor:
     return t.to(device, non_blocking=False).contiguous()
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 class DeviceBatch:
     """All walker arrays as device tensors (owned here, borrowed by the kernel per launch)."""
 
@@ -222,11 +218,11 @@ class DeviceBatch:
                     reset_noise_stride=0 if nz is None else 3 * self.P)
 
     def _p(self, t):
-        if t is None:
-            return None
-        if t.numel() == 0:
-            return C.c_void_p(self._dummy.data_ptr())
-        return C.c_void_p(t.data_ptr())
+        return _lib.ptr(self._dummy if t is not None and t.numel() == 0 else t)
+
+    def plan_args(self):
+        """(the launch plan's device pointer or None, its blocks): the last two batch arguments of a C entry."""
+        return _lib.ptr(self.plan), self.plan_blocks
 
     def _make_struct(self) -> _lib.WgBatch:
         r = self.ragged

@@ -176,8 +176,7 @@ class EvolutionStrategy:
 
     # -------------------------------------------------------------------------------------------- the two kernels
     def _struct(self) -> _lib.WgEs:
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        pol = self.policy
+        p, pol = _lib.ptr, self.policy
         return _lib.WgEs(n_sets=self.G, obs_dim=self.D, hidden=self.H, act_dim=self.C, seed=self.seed,
                          generation=self.generation, sigma=self.sigma, theta=p(self.theta), w1=p(pol.w1), b1=p(pol.b1),
                          w2=p(pol.w2), b2=p(pol.b2))
@@ -208,9 +207,9 @@ class EvolutionStrategy:
         util = self.utilities(fitness).contiguous()
         es = self._struct()
         scale = 1.0 / (2.0 * self.n_pairs * self.sigma)
-        _lib.check(_lib.load().wg_es_update(C.byref(es), 0, self.n_pairs, C.c_void_p(util.data_ptr()), scale, self.lr,
-                                            C.c_void_p(self._work.data_ptr()), C.c_void_p(self._grad.data_ptr()),
-                                            C.c_void_p(self.theta.data_ptr()), self.env._stream()), "wg_es_update")
+        p = _lib.ptr
+        _lib.check(_lib.load().wg_es_update(C.byref(es), 0, self.n_pairs, p(util), scale, self.lr, p(self._work),
+                                            p(self._grad), p(self.theta), self.env._stream()), "wg_es_update")
         self.generation += 1
         return {"grad": self._grad.clone()}
 

@@ -19,6 +19,8 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import _lib
+
 
 def _as_tensor(t, name: str):
     if isinstance(t, np.ndarray):
@@ -120,6 +122,14 @@ class MLPPolicy:
     @property
     def device(self):
         return self.w2.device
+
+    def struct(self, n_walkers: int, action_out=None) -> _lib.WgPolicy:
+        """wg_policy of this policy over a batch of n_walkers, writing every step's actions to action_out [T, N, C] f32
+        if given; return_out / length_out (rollout_policy's per-walker sums) start NULL."""
+        p = _lib.ptr
+        return _lib.WgPolicy(n_sets=self.G, obs_dim=self.D, hidden=self.H, act_dim=self.C, w1=p(self.w1), b1=p(self.b1),
+                             w2=p(self.w2), b2=p(self.b2), act_limit=self.act_limit, action_out=p(action_out),
+                             action_out_step=n_walkers * self.C, return_out=None, length_out=None)
 
     def to(self, device) -> "MLPPolicy":
         mv = lambda t: None if t is None else t.to(device)
