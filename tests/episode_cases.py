@@ -31,6 +31,11 @@ NAMES = ["canonical4-mlp-5sets", "canonical4-lin-perwalker-c5-inf", "balance16-m
 
 
 COVER_NAMES = [c.name for c in pc.COVER]   # instance coverage: every (IN3D, NE, E8) of the AR policy kernel
+# policy shapes through the AR instance (its eight-word walker record holds the parameter set at another stride): M = 16
+# at H = 33 with a set boundary inside a tile and at H = 40 shared, M = 4 at H = 9 with 16 walkers per wave, and the six
+# action columns on four lanes
+SHAPE_NAMES = [pc.shape("m16", 33, G=5).name, pc.shape("m16", 40).name, pc.shape("m4", 9).name,
+               pc.shape("six", 9, C=6).name]
 
 
 def case_of(name):

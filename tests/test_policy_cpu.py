@@ -219,7 +219,7 @@ def test_info_outputs_are_refused(lib):
 
 
 # ------------------------------------------------------------------ the GPU parity cases stay finite on the CPU
-@pytest.mark.parametrize("case", pc.CASES, ids=lambda c: c.name)
+@pytest.mark.parametrize("case", pc.CASES + pc.SHAPES, ids=lambda c: c.name)
 def test_closed_loop_cases_stay_finite(case):
     """Oracle.step(policy.forward_numpy(obs)) for every (spec, params, policy, T) that the GPU tests compare bit for
     bit: no walker ends non-finite; with act_limit 1 the clip engages; in the done cases every walker's done fires
@@ -238,3 +238,77 @@ def test_closed_loop_cases_stay_finite(case):
     if case.done:
         first = np.where(r["done"].any(axis=0), r["done"].argmax(axis=0), case.T)
         assert (first < case.T - 1).all() and len(np.unique(first)) >= 2
+
+
+# ------------------------------------------------------------------ the policy-shape cases can see what they are there for
+def _masses(case):
+    mo = pc.spec_of(case.kind)["mass_off"]
+    return int(mo[1] - mo[0])
+
+
+def test_shapes_cover_the_widths_of_every_tile():
+    """The list itself: T = 3, no clip, distinct seeds, each tile's widths, G = 1 / a few / N at least twice per tile
+    (N once on the M = 64 tile, whose only width of at most 33 is 1), H = 256 with one and with two sets."""
+    assert len({c.seed for c in pc.CASES + pc.COVER + pc.SHAPES}) == len(pc.CASES + pc.COVER + pc.SHAPES)
+    assert len({c.name for c in pc.SHAPES}) == len(pc.SHAPES)
+    widths = {"m4": [1, 3, 4, 5, 8, 9, 256], "m16": [1, 15, 16, 17, 32, 33, 40, 64, 255, 256],
+              "m64": [1, 63, 64, 65, 128, 129, 256], "six": [0, 9]}
+    dims = {"m4": (4, 26, 2), "m16": (16, 155, 8), "m64": (64, 596, 20), "six": (4, 42, 6)}
+    for tile, want in widths.items():
+        cases = [c for c in pc.SHAPES if c.name.startswith(tile + "-")]
+        N = len(pc.spec_of(cases[0].kind)["mass_off"]) - 1
+        M, D, A = dims[tile]
+        assert sorted({c.H for c in cases}) == want, tile
+        for c in cases:
+            assert (c.T, c.L, c.oracle) == (3, float("inf"), True) and (_masses(c), pc.obs_dim(c)) == (M, D), c
+            assert c.wpw == (8 if tile == "six" else 64 // M) and N % c.G == 0 and 1 <= c.C <= A, c
+            assert c.G < N or c.H <= 33, c
+        if tile != "six":
+            assert sorted(c.G for c in cases if c.H == 256) == [1, 2], tile
+            assert sum(c.C < A for c in cases) == 1, tile
+            assert sum(c.G == 1 for c in cases) >= 2 and sum(1 < c.G < N for c in cases) >= 2, tile
+            assert sum(c.G == N for c in cases) >= (1 if tile == "m64" else 2), tile
+            if M < 64:   # a set boundary inside a wave tile
+                assert sum((N // c.G) % c.wpw != 0 for c in cases if 1 < c.G < N) >= 2, tile
+    assert [(c.H, c.C) for c in pc.SHAPES if c.name.startswith("six-")] == [(0, 6), (9, 5), (9, 6)]
+
+
+def _hidden0(case, w1, b1):
+    """Step 0's hidden vectors [N, H], the contract restated: the bias, then the inputs in ascending order."""
+    x = pc.entry_rows(case.name)
+    sets = np.arange(x.shape[0]) // (x.shape[0] // case.G)
+    z = np.zeros((x.shape[0], case.H), f32) if b1 is None else b1[sets].copy()
+    for i in range(x.shape[1]):
+        z = z + x[:, i:i + 1] * w1[sets, i]
+    return np.where(z > 0, z, f32(0.0)).astype(f32)
+
+
+@pytest.mark.parametrize("case", pc.SHAPES, ids=lambda c: c.name)
+def test_shape_cases_can_see_a_wrong_column(case):
+    """Conditions on the inputs, from the reference alone: both biases on the odd seeds and neither on the even; every
+    hidden unit is on for some walker and off for some walker at step 0; doubling one unit's column of w1 (the first,
+    the last, the last one of lane q = 0) changes the bits of some action of step 0; and where C > M, the columns a
+    lane takes on its second round differ from those of its first."""
+    import torch
+    from walker_gym_amd.policy import MLPPolicy
+    r = pc.oracle_rollout(case.name)
+    w2, b2, w1, b1 = pc.weights(case)
+    M = _masses(case)
+    assert (b2 is not None) == bool(case.seed % 2)
+    rows = pc.entry_rows(case.name)
+    act0 = pc.policy_of(case).forward_numpy(rows)
+    assert np.array_equal(act0.view(np.uint32), r["action"][0].view(np.uint32))
+    if case.H:
+        assert (b1 is not None) == bool(case.seed % 2)
+        h = _hidden0(case, w1, b1)
+        assert (h > 0).any(axis=0).all() and (h == 0).any(axis=0).all()
+        t = lambda a: None if a is None else torch.from_numpy(a)
+        for j in sorted({0, case.H - 1, (case.H - 1) // M * M}):
+            wp = w1.copy()
+            wp[:, :, j] *= f32(2.0)
+            got = MLPPolicy(t(w2), t(b2), t(wp), t(b1), act_limit=case.L).forward_numpy(rows)
+            assert not np.array_equal(got.view(np.uint32), act0.view(np.uint32)), j
+    if case.C > M:
+        a = r["action"]
+        assert (a[:, :, M:] != a[:, :, :case.C - M]).any(axis=(0, 1)).all()
+        assert not np.array_equal(a[0][:, M:], a[0][:, :case.C - M])

@@ -16,7 +16,7 @@ f32 = np.float32
 
 
 # ------------------------------------------------------------------ the cases cannot pass vacuously
-@pytest.mark.parametrize("name", ec.NAMES)
+@pytest.mark.parametrize("name", ec.NAMES + ec.SHAPE_NAMES)
 def test_cases_reset_often_and_stay_finite(name):
     cfg, ref = ec.config(name), ec.reference(name)
     case, N = cfg["case"], cfg["N"]
