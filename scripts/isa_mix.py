@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Static instruction mix of one kernel in a device assembly file (profiling aid, not product).
 
-    hipcc --offload-arch=gfx950 <build.py flags> --offload-device-only -S -o k.s walker_hip.hip
+    hipcc --offload-arch=gfx950 <build.py flags> --offload-device-only -S -o k.s walker_gym_amd/csrc/walker_hip.hip
+    (scripts/isa_identity.py compares two trees' files)
     python scripts/isa_mix.py k.s 'walker_step_leanILb1ELi3E' [--dump out.s] [--blocks]
 
 Counts the instructions of the kernel's body by class (VALU f64 / f32 / int / cvt / mov-cmp-sel / DPP, LDS,

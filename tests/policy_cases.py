@@ -169,7 +169,7 @@ def case_of(name):
 
 
 def lds_bytes(case, episodes=False):
-    """The host's LDS arithmetic for a case restated (lean_geo and rollout_policy in csrc/walker_hip.hip): the
+    """The host's LDS arithmetic for a case restated (lean_geo and rollout_policy in csrc/wg_host.h): the
     workgroup's bytes without staged weights, the weights' bytes, and whether WG_POLICY_STAGE = 0 / 1 / 2 stages them."""
     spec = spec_of(case.kind)
     N, K = len(spec["mass_off"]) - 1, int(spec["edge_off"][1] - spec["edge_off"][0])

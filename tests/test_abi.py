@@ -174,7 +174,7 @@ def test_launch_geometry_wave_tiles(lib):
 
 
 def test_launch_geometry_wide_workgroups(lib, monkeypatch):
-    """M > 64: the workgroup size in 256..512 threads that leaves the fewest idle lanes (walker_hip.hip
+    """M > 64: the workgroup size in 256..512 threads that leaves the fewest idle lanes (csrc/wg_host.h
     uniform_geo), halved back while the grid has fewer than 512 workgroups; WG_WIDE=0 keeps 256."""
     def geo(N, M, K):
         b = _lib.WgBatch(N=N, M=M, K=K, A=0, ragged=0)
@@ -192,7 +192,7 @@ def test_launch_geometry_wide_workgroups(lib, monkeypatch):
 
 
 def test_wave_edge_passes(lib):
-    """Spring passes of a wave tile (walker_hip.hip wave_passes): enough for the longest walker and for 64 masses of
+    """Spring passes of a wave tile (csrc/wg_host.h wave_passes): enough for the longest walker and for 64 masses of
     the densest one, rounded to an instantiated count; 0 = the batch cannot use the wave kernel."""
     for (M, K), ne in {(32, 64): 2, (16, 40): 3, (4, 5): 2, (8, 4): 1, (64, 300): 8, (64, 512): 8,
                        (65, 10): 0, (4, 600): 0, (2, 20): 0}.items():

@@ -110,7 +110,7 @@ def test_concat_specs_matches_creatures_to_spec():
 
 
 def test_wave_edge_passes_matches_library():
-    """layout.wave_edge_passes restates walker_hip.hip wave_passes (wg_wave_edge_passes)."""
+    """layout.wave_edge_passes restates wg_host.h wave_passes (wg_wave_edge_passes)."""
     import ctypes as C
     from walker_gym_amd import _lib
     from walker_gym_amd.layout import wave_edge_passes

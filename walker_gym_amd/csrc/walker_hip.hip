@@ -19,6 +19,7 @@
 //     as one contiguous coalesced block.
 // Compiled with -ffp-contract=off and IEEE f32/f64 division/sqrt (build.py), so each float op rounds
 // exactly as numpy's does.
+// The host side (argument checks, launch geometry, instance selection, launchers) lives in wg_host.h, included below.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -37,9 +38,7 @@
 #include "powf2.h"
 #include "walker_internal.h"
 
-namespace {
-thread_local char g_err[512] = "";
-}
+static thread_local char g_err[512] = "";
 
 // the library's one error message (walker_internal.h): every refusal of either translation unit goes through here
 int wg_fail(int code, const char *fmt, ...) {
@@ -188,16 +187,28 @@ struct Geo {
 
 // Diagnostic builds only (-DWG_STAMPS, scripts/stamps.py): lane 0 of every lean wave records s_memtime at its
 // phase boundaries into g_stamps[wave][8] with a vector store; wg_debug_stamps copies them out.  Never in the
-// product build.
+// product build.  STAMP_WAVE(i) names the wave's record in a scope (its tile index), STAMP(k) fills slot k,
+// STAMP_HW(lane) slot 7: HW_ID (gfx9 hwreg 4) | XCC_ID (gfx940+ hwreg 20) << 32.
 #ifdef WG_STAMPS
 __device__ unsigned long long g_stamps[(1 << 16) * 8];
+#define STAMP_WAVE(i) const int stamp_wave = (i)
 #define STAMP(k)                                                                                          \
     do {                                                                                                  \
         const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                      \
         if ((threadIdx.x & 63) == 0 && stamp_wave < (1 << 16)) g_stamps[stamp_wave * 8 + (k)] = t_;      \
     } while (0)
+#define STAMP_HW(lane)                                                                                    \
+    do {                                                                                                  \
+        if (lane == 0 && stamp_wave < (1 << 16)) {                                                        \
+            const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);                                \
+            const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);                              \
+            g_stamps[stamp_wave * 8 + 7] = (unsigned long long)hw | ((unsigned long long)xcc << 32);      \
+        }                                                                                                 \
+    } while (0)
 #else
+#define STAMP_WAVE(i) do {} while (0)
 #define STAMP(k) do {} while (0)
+#define STAMP_HW(lane) do {} while (0)
 #endif
 
 struct Carve {
@@ -446,8 +457,6 @@ __device__ __forceinline__ double rcp64_nr(double d) {
 // the range, both signs (scripts/check_rcp64.hip, profiles/r04_rcp64_exhaustive.json) — 5 VALU instead of the ~12 of
 // the IEEE division, and a shorter dependent chain; any other m (0, subnormal, inf, NaN, outside the range) takes the
 // IEEE division, so the guarded paths see exactly what they saw before.
-__device__ __forceinline__ double rcp64_nr(double d);
-__device__ __forceinline__ bool divisor_ok(float m);
 __device__ __forceinline__ double recip_m(float mf) {
     const double md = (double)mf;
     double y = rcp64_nr(md);
@@ -572,6 +581,15 @@ __device__ inline EdgeRec load_edge(const wg_edge *__restrict__ e, size_t i) {
 __device__ inline int edge_i(uint32_t ij) { return (int)(ij & 0x7fffu); }
 __device__ inline int edge_j(uint32_t ij) { return (int)((ij >> 16) & 0x7fffu); }
 __device__ inline bool edge_string(uint32_t ij) { return (ij >> 31) != 0u; }
+
+// Muscle.act / actdisp, then the regulation (gym/optimized_walker.py:27-43,164-172): the muscle's new rest length from
+// its action a (action_mode 1: a discrete step of stp up or down)
+__device__ __forceinline__ float muscle_act(int action_mode, float x, float a, float stp, float lo, float hi) {
+    x = (action_mode == 1) ? ((a != 0.f) ? x + stp : x - stp) : x + a;
+    if (lo > x) x = lo;     // Python max(x, originx*minl)
+    if (hi < x) x = hi;     // Python min(x, originx*maxl)
+    return x;
+}
 
 // ------------------------------------------------------------------ per-edge and per-mass physics
 // Spring term and damping force of edge `le` (block-local; masses at LDS index lm + i/j):
@@ -1009,6 +1027,38 @@ __device__ __forceinline__ void mass_step(const KParams &kp, const double *st, c
     const float ymf = (float)(1.0 / (double)mf);
     mass_tail(kp, mf, ymf, p3, v3, px, py, pz, vx, vy, vz, ax, ay, az, hit, pinned);
 }
+
+// ------------------------------------------------------------------ per-walker phases every step kernel shares
+// The done rule (gym/optimized_env.py:189-248): the step limit, the walker's mean height cy below done_y, or, after
+// 100 steps, every mass stopped (|v| < 0.1), into the caller's `int done`.  steps, cy and kp are names.  (A macro, not an
+// inline function: a function evaluates all_stopped before the call instead of under the rule's last test, and compiled
+// to different code in the lean and wave kernels.)
+#define WG_EPISODE_DONE(done, steps, cy, all_stopped, kp)   \
+    do {                                                    \
+        done = steps >= kp.max_steps;                       \
+        if (!done && cy < kp.done_y) done = 1;              \
+        if (!done && steps > 100) done = (all_stopped);     \
+    } while (0)
+// A mass of a diverged walker after the integrator (the wave kernels stepped a finite stand-in): what the reference
+// computes, NaN in every component and no contact
+__device__ __forceinline__ void nan_state(float &px, float &py, float &pz, float &vx, float &vy, float &vz, float &ax,
+                                          float &ay, float &az, bool &hit) {
+    px = __builtin_nanf(""); py = px; pz = px; vx = px; vy = px; vz = px; ax = px; ay = px; az = px;
+    hit = false;
+}
+// The wave kernels' state stores of mass pl after a step (32-bit byte offsets, WG_ST): pos and vel, and with `aux`
+// (wave-uniform) acc and, where the batch has the array, the contact flag.  (A macro: as an inline function, with the
+// batch by reference or its arrays as arguments, it changed the register allocation of every wave kernel.)
+#define WG_STORE_STATE(b, pl, px, py, pz, vx, vy, vz, ax, ay, az, aux, hit)                            \
+    {                                                                                                  \
+        float *gpo = WG_ST(b.pos, pl, 3), *gvo = WG_ST(b.vel, pl, 3), *gao = WG_ST(b.acc, pl, 3);      \
+        gpo[0] = px; gpo[1] = py; gpo[2] = pz;                                                         \
+        gvo[0] = vx; gvo[1] = vy; gvo[2] = vz;                                                         \
+        if (aux) {                                                                                     \
+            gao[0] = ax; gao[1] = ay; gao[2] = az;                                                     \
+            if (b.contact) at_u32w(b.contact, pl) = (uint8_t)hit;                                      \
+        }                                                                                              \
+    }
 
 // ------------------------------------------------------------------ cross-lane reductions
 // A walker's M masses are M adjacent lanes of one wave when M divides 64 (uniform batches): numpy's
@@ -1530,7 +1580,7 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(wg_kernel_
                     a = action[(size_t)caller_row(b, w0 + wl) * action_stride + ua];
                 }
                 if (kp.action_mode == 1) x = (a != 0.f) ? x + st : x - st;
-                else x = x + a;
+                else x = x + a;   // (written out: muscle_act compiles to different code here)
                 if (lo > x) x = lo;     // Python max(x, originx*minl)
                 if (hi < x) x = hi;     // Python min(x, originx*maxl)
                 b.muscle_x[U0 + u] = x;
@@ -1686,9 +1736,8 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(wg_kernel_
                 o.reward[wg] = (cy + vpen) + (float)(-(double)hits * 0.5);
             }
             if (o.done) {
-                int done = steps >= kp.max_steps;
-                if (!done && cy < kp.done_y) done = 1;
-                if (!done && steps > 100) done = all_stopped;
+                int done;
+                WG_EPISODE_DONE(done, steps, cy, all_stopped, kp);
                 o.done[wg] = (uint8_t)done;
             }
             if (o.centroid) { o.centroid[3 * wg] = midx; o.centroid[3 * wg + 1] = midy; o.centroid[3 * wg + 2] = midz; }
@@ -1753,9 +1802,8 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(wg_kernel_
                 o.reward[wg] = (cy + vpen) + cpen;
             }
             if (o.done) {
-                int done = steps >= kp.max_steps;
-                if (!done && cy < kp.done_y) done = 1;
-                if (!done && steps > 100) done = all;
+                int done;
+                WG_EPISODE_DONE(done, steps, cy, all, kp);
                 o.done[wg] = (uint8_t)done;
             }
             if (o.centroid) {
@@ -1968,6 +2016,11 @@ struct LeanIn {
     int io0, io1, wsteps, pin;   // incidence range; step counter (q == 0 lanes); DingPoint flag
     float x, lo, hi, stp, a;     // this lane's muscle: Muscle.x, regulation bounds, stride, action
 };
+// This lane's incidence words gi[NE] into the wave's LDS lists (nE: the tile's springs; FULL, the fixed-parameter
+// instance: every pass but the last is full).  (A macro: a function changed the lean and resident kernels at NE > 1.)
+#define WG_INC_TO_LDS(s_inc, gi, lane, nE, NE, FULL) \
+    _Pragma("unroll") for (int it = 0; it < NE; it++) \
+        if ((FULL && it < NE - 1) || lane + 64 * it < nE) s_inc[lane + 64 * it] = gi[it]
 
 // A wave's tile: its walker range and the lane roles in it (no memory access).
 struct LeanTile {
@@ -2395,9 +2448,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     const uint32_t pl = t.P0 + lane, ul = t.U0 + lane;   // this lane's mass / muscle
     // slice: spring terms t (f64 x3) | df (f32 x3) | incidence words | muscle x
     const LeanTerms ts = lean_terms(sl, lg);
-#ifdef WG_STAMPS
-    const int stamp_wave = t.w0 / lg.wpw;   // (the tile index, as the kernel's own stamps use)
-#endif
+    STAMP_WAVE(t.w0 / lg.wpw);   // (the tile index, as the kernel's own stamps use)
     uint32_t *s_inc = reinterpret_cast<uint32_t *>(sl + lg.off_inc);
     float *s_x = reinterpret_cast<float *>(sl + lg.off_x);
     const float mf = L.mf;
@@ -2411,16 +2462,12 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
 
     // ================= act (gym/optimized_walker.py:27-43,164-172); the incidence lists go to LDS first
     if (!RES) {   // (the resident kernel writes them once, before its first step)
-#pragma unroll
-        for (int it = 0; it < NE; it++)
-            if ((FIX && it < NE - 1) || lane + 64 * it < nE) s_inc[lane + 64 * it] = L.gi[it];
+        WG_INC_TO_LDS(s_inc, L.gi, lane, nE, NE, FIX);
         if (lane == 0) s_inc[nE] = 0u;   // the read-ahead pad after the last list (mass_accumulate_v2)
     }
     float x = L.x;
     if (acts) {
-        x = (kp.action_mode == 1) ? ((L.a != 0.f) ? x + L.stp : x - L.stp) : x + L.a;
-        if (L.lo > x) x = L.lo;     // Python max(x, originx*minl)
-        if (L.hi < x) x = L.hi;     // Python min(x, originx*maxl)
+        x = muscle_act(kp.action_mode, x, L.a, L.stp, L.lo, L.hi);
         if (store) *WG_ST(b.muscle_x, ul, 1) = x;
     }
     if (is_mus) s_x[lane] = x;
@@ -2558,10 +2605,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     if (is_mass) {
         mass_tail(kp, mf, (float)ym, L.p3, L.v3, px, py, pz, vx, vy, vz, ax, ay, az, hit, pin,
                   !RES ? &et : nullptr);
-        if (dead) {   // (a diverged walker, above: what the reference computes)
-            px = __builtin_nanf(""); py = px; pz = px; vx = px; vy = px; vz = px; ax = px; ay = px; az = px;
-            hit = false;
-        }
+        if (dead) nan_state(px, py, pz, vx, vy, vz, ax, ay, az, hit);   // (a diverged walker, above)
         // p.r = 3 / p.r = 1 (gym/optimized_env.py:156,175)
         if (!FIX && b.radius && store) b.radius[pl] = hit ? 3.0 : 1.0;
         nv = np_norm3(vx, vy, vz);
@@ -2586,17 +2630,9 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     const float midx = sx * lg.invM, midy = sy * lg.invM, midz = sz * lg.invM;
     int ep_done = 0;   // (AR) the step's done, in lane q == 0 of each walker
     if (is_mass) {
-        if (store) {
-            float *gpo = WG_ST(b.pos, pl, 3), *gvo = WG_ST(b.vel, pl, 3), *gao = WG_ST(b.acc, pl, 3);
-            gpo[0] = px; gpo[1] = py; gpo[2] = pz;
-            gvo[0] = vx; gvo[1] = vy; gvo[2] = vz;
-            // wave-uniform: not in the steps of a multi-step call before its last (run(); the resident kernel stores
-            // after its last step only)
-            if (RES || kp.keep_aux) {
-                gao[0] = ax; gao[1] = ay; gao[2] = az;
-                if (b.contact) at_u32w(b.contact, pl) = (uint8_t)hit;
-            }
-        }
+        // acc and contact (wave-uniform): not in the steps of a multi-step call before its last (run(); the resident
+        // kernel stores after its last step only)
+        if (store) WG_STORE_STATE(b, pl, px, py, pz, vx, vy, vz, ax, ay, az, RES || kp.keep_aux, hit)
         if (q == 0) {
             const uint32_t wg = (uint32_t)(w0 + wl);
             const int steps = L.wsteps + 1;
@@ -2613,9 +2649,8 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
                 *WG_ST(o.reward, wg, 1) = (cy + vpen) + neg_half_count((int)__popcll(hb & gmask));
             }
             if (FIX || o.done || (AR && (ar.mode & 1)) || POL) {
-                int done = steps >= kp.max_steps;
-                if (!done && cy < kp.done_y) done = 1;
-                if (!done && steps > 100) done = (sb & gmask) == gmask;
+                int done;
+                WG_EPISODE_DONE(done, steps, cy, (sb & gmask) == gmask, kp);
                 if (FIX || o.done) at_u32w(o.done, wg) = (uint8_t)done;
                 ep_done = done;
             }
@@ -2718,13 +2753,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
         po->done = ep_done;
     }
     STAMP(6);
-#ifdef WG_STAMPS
-    if (lane == 0 && stamp_wave < (1 << 16)) {   // slot 7: HW_ID (gfx9 hwreg 4) | XCC_ID (gfx940+ hwreg 20) << 32
-        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-        const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        g_stamps[stamp_wave * 8 + 7] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-    }
-#endif
+    STAMP_HW(lane);
 }
 
 // NE spring passes per wave need up to 8 x 16-B records in registers: 6 waves per SIMD hold up to NE 4 without
@@ -2746,9 +2775,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
     const int blk = (kp.xcd & 2) ? xcd_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int tile = blk * lg.wpb + wv;
     if (tile * lg.wpw >= b.N) return;
-#ifdef WG_STAMPS
-    const int stamp_wave = tile;
-#endif
+    STAMP_WAVE(tile);
     STAMP(0);
     const LeanTile t = lean_tile_of<FIX>(b, action, action_cols, lg, tile, lane);
     LeanIn<NE, E8> L;
@@ -2788,9 +2815,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
     const int blk = (nblkx & 0x40000000) ? xb : bid;
     const int tile = blk * lg.wpb + wv;
     if (tile * lg.wpw >= b.N) return;
-#ifdef WG_STAMPS
-    const int stamp_wave = tile;
-#endif
+    STAMP_WAVE(tile);
     STAMP(0);
     const LeanTile t = lean_tile_of<FIX>(b, action, action_cols, lg, tile, lane);
     LeanIn<1, E8> L;
@@ -2820,6 +2845,26 @@ __device__ __forceinline__ KReset kreset_at(const KReset &r, const KOut &o, int 
     if (as.final_obs) as.final_obs += (size_t)s * o.obs_step;
     return as;
 }
+// The resident loops' per-step pieces (macros: as inline functions they changed both loops' register allocation).
+// KOut os: the outputs of step s (rows out_step / obs_step apart; the three-component centroid 3 * out_step)
+#define WG_KOUT_AT(os, o, s)                                          \
+    KOut os = o;                                                      \
+    if (os.obs) os.obs += (size_t)s * os.obs_step;                    \
+    if (os.reward) os.reward += (size_t)s * os.out_step;              \
+    if (os.done) os.done += (size_t)s * os.out_step;                  \
+    if (os.energy) os.energy += (size_t)s * os.out_step;              \
+    if (os.centroid) os.centroid += 3 * (size_t)s * os.out_step;      \
+    if (os.steps) os.steps += (size_t)s * os.out_step
+// the tile's static inputs made opaque each step: what derives from them (the mass's 1/m, the springs' endpoint
+// indices) is recomputed in the step instead of being hoisted out of the loop and held in registers (spilled)
+#define WG_PIN_STATIC(L, NE, E8)                                                                                      \
+    {                                                                                                                 \
+        asm volatile("" : "+v"(L.mf), "+v"(L.io0), "+v"(L.io1), "+v"(L.lo), "+v"(L.hi), "+v"(L.stp));                 \
+        _Pragma("unroll") for (int it = 0; it < NE; it++) {                                                           \
+            if constexpr (E8) asm volatile("" : "+v"(L.er[it].w), "+v"(L.er[it].rest));                               \
+            else asm volatile("" : "+v"(L.er[it].ij), "+v"(L.er[it].rest), "+v"(L.er[it].k), "+v"(L.er[it].c));     \
+        }                                                                                                             \
+    }
 template <bool IN3D, int NE, bool E8, bool AR = false>
 // (register budget: 5 waves per SIMD since the scalar wave index, 16 B of scratch at NE 3-4: 35.49 against 36.07 us per
 // step at 4, profiles/r04l_ab_resident.json)
@@ -2830,9 +2875,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tile = blockIdx.x * lg.wpb + wv;
     if (tile * lg.wpw >= b.N) return;
-#ifdef WG_STAMPS
-    const int stamp_wave = tile;
-#endif
+    STAMP_WAVE(tile);
     const LeanTile t = lean_tile_of(b, action, action_cols, lg, tile, lane);
     LeanIn<NE, E8> L;
     if (kp.prio) __builtin_amdgcn_s_setprio(2);
@@ -2840,9 +2883,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
     if (kp.prio) __builtin_amdgcn_s_setprio(0);
     {   // the incidence lists are static: into LDS once
         uint32_t *s_inc = reinterpret_cast<uint32_t *>(smem + wv * lg.slice + lg.off_inc);
-#pragma unroll
-        for (int it = 0; it < NE; it++)
-            if (lane + 64 * it < t.nE) s_inc[lane + 64 * it] = L.gi[it];
+        WG_INC_TO_LDS(s_inc, L.gi, lane, t.nE, NE, false);
     }
     if constexpr (AR) {   // the walkers' episode counts, each in its lane q == 0's LDS word
         if (t.is_mass && t.q == 0)
@@ -2860,20 +2901,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
         if (ts.acts && s + 1 < n_steps)
             a_next = action[(size_t)(s + 1) * (size_t)action_step +
                             (size_t)(uint32_t)(ts.w0 + ts.mu_wl) * (uint32_t)action_stride + (uint32_t)ts.mu_ua];
-        KOut os = o;
-        if (os.obs) os.obs += (size_t)s * os.obs_step;
-        if (os.reward) os.reward += (size_t)s * os.out_step;
-        if (os.done) os.done += (size_t)s * os.out_step;
-        if (os.energy) os.energy += (size_t)s * os.out_step;
-        if (os.centroid) os.centroid += 3 * (size_t)s * os.out_step;
-        if (os.steps) os.steps += (size_t)s * os.out_step;
-        // the same for the static inputs (the mass's 1/m, the springs' endpoint indices are re-derived per step)
-        asm volatile("" : "+v"(L.mf), "+v"(L.io0), "+v"(L.io1), "+v"(L.lo), "+v"(L.hi), "+v"(L.stp));
-#pragma unroll
-        for (int it = 0; it < NE; it++) {
-            if constexpr (E8) asm volatile("" : "+v"(L.er[it].w), "+v"(L.er[it].rest));
-            else asm volatile("" : "+v"(L.er[it].ij), "+v"(L.er[it].rest), "+v"(L.er[it].k), "+v"(L.er[it].c));
-        }
+        WG_KOUT_AT(os, o, s);
+        WG_PIN_STATIC(L, NE, E8)   // (the same for the static inputs)
         if constexpr (AR)
             lean_compute<IN3D, NE, true, E8, true>(b, kp, os, lg, smem + wv * lg.slice, ts, ln, L, s == n_steps - 1,
                                                    kreset_at(ar.r, o, s), nullptr,
@@ -3068,9 +3097,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
     if (!t.is_mass) { ps.ax = 0.f; ps.ay = 0.f; ps.az = 0.f; }
     {   // the incidence lists are static: into LDS once
         uint32_t *s_inc = reinterpret_cast<uint32_t *>(sl + lg.off_inc);
-#pragma unroll
-        for (int it = 0; it < NE; it++)
-            if (lane + 64 * it < t.nE) s_inc[lane + 64 * it] = L.gi[it];
+        WG_INC_TO_LDS(s_inc, L.gi, lane, t.nE, NE, false);
     }
     {   // the entry state's position sums, as the step leaves them for every later row
         const WalkerSums fs = walker_sums(L.p3[0], L.p3[1], L.p3[2], 0.f, 0.f, 0.f, lane & ~(b.M - 1), b.M, lane);
@@ -3097,19 +3124,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
         ts.acts = ts.is_mus && ts.mu_ua < pol.C;
         L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x,
                                     pol.action_out ? pol.action_out + (size_t)s * (size_t)pol.action_out_step : nullptr);
-        KOut os = o;
-        if (os.obs) os.obs += (size_t)s * os.obs_step;
-        if (os.reward) os.reward += (size_t)s * os.out_step;
-        if (os.done) os.done += (size_t)s * os.out_step;
-        if (os.energy) os.energy += (size_t)s * os.out_step;
-        if (os.centroid) os.centroid += 3 * (size_t)s * os.out_step;
-        if (os.steps) os.steps += (size_t)s * os.out_step;
-        asm volatile("" : "+v"(L.mf), "+v"(L.io0), "+v"(L.io1), "+v"(L.lo), "+v"(L.hi), "+v"(L.stp));
-#pragma unroll
-        for (int it = 0; it < NE; it++) {
-            if constexpr (E8) asm volatile("" : "+v"(L.er[it].w), "+v"(L.er[it].rest));
-            else asm volatile("" : "+v"(L.er[it].ij), "+v"(L.er[it].rest), "+v"(L.er[it].k), "+v"(L.er[it].c));
-        }
+        WG_KOUT_AT(os, o, s);
+        WG_PIN_STATIC(L, NE, E8)
         if constexpr (AR)
             lean_compute<IN3D, NE, true, E8, true, true>(b, kp, os, lg, sl, ts, ln, L, s == n_steps - 1,
                                                          kreset_at(ar, o, s), &ps,
@@ -3190,9 +3206,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
     const int blk = (kp.xcd & 1) ? xcd_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int tile = blk * rg.wpb + wv;
     if (tile >= ntiles) return;
-#ifdef WG_STAMPS
-    const int stamp_wave = tile;
-#endif
+    STAMP_WAVE(tile);
     STAMP(0);
     char *sl = smem + wv * rg.slice;
     const TermsAoS ts{reinterpret_cast<double *>(sl), reinterpret_cast<float *>(sl + rg.off_df)};
@@ -3316,15 +3330,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
     STAMP(1);
 
     // ================= incidence lists into LDS; act (gym/optimized_walker.py:27-43,164-172)
-#pragma unroll
-    for (int it = 0; it < NE; it++)
-        if (lane + 64 * it < nE) s_inc[lane + 64 * it] = gi[it];
+    WG_INC_TO_LDS(s_inc, gi, lane, nE, NE, false);
     if (lane == 0) s_inc[nE] = 0u;   // the read-ahead pad after the last list (mass_accumulate_v2)
     float x = mx;
     if (acts) {
-        x = (kp.action_mode == 1) ? ((act != 0.f) ? x + mst : x - mst) : x + act;
-        if (mlo > x) x = mlo;     // Python max(x, originx*minl)
-        if (mhi < x) x = mhi;     // Python min(x, originx*maxl)
+        x = muscle_act(kp.action_mode, x, act, mst, mlo, mhi);
         *WG_ST(b.muscle_x, U0 + lane, 1) = x;
     }
     if (is_mus) s_x[lane] = x;
@@ -3374,18 +3384,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
         mass_accumulate_v2(ts, reinterpret_cast<const uint16_t *>(s_inc) + 2 * mlb, mlb, io0,
                            (WG_ABLATE & 2) ? min(io1, io0 + 1) : io1, mf, ym, ax, ay, az, wave_tiny);
         mass_tail(kp, mf, (float)ym, p3, v3, px, py, pz, vx, vy, vz, ax, ay, az, hit, pin != 0, &et);
-        if (dead) {
-            px = __builtin_nanf(""); py = px; pz = px; vx = px; vy = px; vz = px; ax = px; ay = px; az = px;
-            hit = false;
-        }
+        if (dead) nan_state(px, py, pz, vx, vy, vz, ax, ay, az, hit);
         const uint32_t pl = (uint32_t)(P0 + lane);
-        float *gpo = WG_ST(b.pos, pl, 3), *gvo = WG_ST(b.vel, pl, 3), *gao = WG_ST(b.acc, pl, 3);
-        gpo[0] = px; gpo[1] = py; gpo[2] = pz;
-        gvo[0] = vx; gvo[1] = vy; gvo[2] = vz;
-        if (kp.keep_aux) {   // (as the lean kernel)
-            gao[0] = ax; gao[1] = ay; gao[2] = az;
-            if (b.contact) at_u32w(b.contact, pl) = (uint8_t)hit;
-        }
+        WG_STORE_STATE(b, pl, px, py, pz, vx, vy, vz, ax, ay, az, kp.keep_aux, hit)   // (as the lean kernel)
         if (b.radius) b.radius[pl] = hit ? 3.0 : 1.0;   // gym/optimized_env.py:156,175
     }
     STAMP(4);
@@ -3436,9 +3437,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
         if (o.steps) *WG_ST(o.steps, wrow, 1) = steps;
         if (o.reward) *WG_ST(o.reward, wrow, 1) = (cy + (-fdiv_count(rd[4], fM, yM)) * 0.1f) + neg_half_count(hits);
         if (o.done) {
-            int done = steps >= kp.max_steps;
-            if (!done && cy < kp.done_y) done = 1;
-            if (!done && steps > 100) done = all;
+            int done;
+            WG_EPISODE_DONE(done, steps, cy, all, kp);
             at_u32w(o.done, (uint32_t)wrow) = (uint8_t)done;
         }
         // the walker's mean position (np.mean: info's centroid, getstat's mid), once per walker: every mass lane of the
@@ -3498,13 +3498,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
         }
     }
     STAMP(6);
-#ifdef WG_STAMPS
-    if (lane == 0 && stamp_wave < (1 << 16)) {   // slot 7: HW_ID (gfx9 hwreg 4) | XCC_ID (gfx940+ hwreg 20) << 32
-        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-        const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        g_stamps[stamp_wave * 8 + 7] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-    }
-#endif
+    STAMP_HW(lane);
 }
 
 // reset: v += noise, steps = 0 (PhysicsEnv.reset, gym/optimized_env.py:53-68).  zmode 0: x, y (2D);
@@ -3564,660 +3558,6 @@ __global__ __launch_bounds__(256) void walker_info_kernel(wg_batch b, uint8_t *_
     if (momentum) { momentum[3 * r] = mx; momentum[3 * r + 1] = my; momentum[3 * r + 2] = mz; }
 }
 
-// ------------------------------------------------------------------ host side
-int env_int(const char *name, int dflt);
-int wave_passes(int M, int K);
-
-KParams make_kparams(const wg_params &p) {
-    KParams k;
-    k.neg_g = (float)(-p.g);
-    k.neg_dampk = (float)(-p.dampk);
-    k.ground = (float)p.ground;
-    k.neg_groundk = (float)(-p.groundk);
-    k.neg_grounddamp = (float)(-p.grounddamp);
-    k.friction = (float)p.friction;
-    k.dt = (float)p.dt;
-    k.pk = (float)p.pk; k.vk = (float)p.vk; k.ak = (float)p.ak; k.mk = (float)p.mk;
-    k.done_y = (float)(p.ground - 50.0);
-    k.g = p.g;
-    k.max_steps = p.max_steps; k.midform = p.midform; k.conmid = p.conmid;
-    k.spring_mode = p.spring_mode; k.action_mode = p.action_mode;
-    k.integrator = p.integrator;
-    k.pair_mode = p.pair_mode;
-    k.pair_g = p.pair_g;
-    k.pair_k = p.pair_k;
-    k.pair_e = p.pair_e;
-    k.bounce_kh = (float)(p.bounce_k / 2);
-    for (int i = 0; i < 3; i++) k.g3g[i] = (float)p.g3_gravity[i];
-    k.g3_damp = (float)p.g3_damping;
-    k.g3_dragc = (float)(-0.5 * p.g3_air);
-    k.g3_level = (float)p.g3_ground_level;
-    k.g3_rest = (float)p.g3_restitution;
-    k.g3_fric = (float)p.g3_friction;
-    k.g3_ground = p.g3_ground;
-    k.friction_mode = p.friction_mode;
-    k.prio = env_int("WG_LEAN_PRIO", 1);
-    k.xcd = env_int("WG_XCD", 3);   // both kernels (profiles/r03e_ab_canon.json, r03d_ab_ragged_window_xcd.json)
-    k.keep_aux = 1;
-
-    k.dt2 = (float)(p.dt * p.dt);
-    return k;
-}
-
-constexpr int RAG_P = 256, RAG_E = 512, RAG_U = 256, RAG_W = 64;
-constexpr int LDS_LIMIT = 160 * 1024;
-
-int validate(const wg_batch *b) {
-    if (!b) return wg_fail(WG_EINVAL, "null batch");
-    if (b->N < 0 || b->M < 1 || b->K < 0 || b->A < 0 || b->A > b->K)
-        return wg_fail(WG_EINVAL, "bad sizes N=%d M=%d K=%d A=%d", b->N, b->M, b->K, b->A);
-    if (2 * b->K > 65535) return wg_fail(WG_ERANGE, "K=%d exceeds the u16 incidence encoding", b->K);
-    if (b->M > WG_MAX_M) return wg_fail(WG_ERANGE, "M=%d > %d masses per walker", b->M, WG_MAX_M);
-    if (!b->pos || !b->vel || !b->acc || !b->mass || !b->steps || !b->muscle_x)
-        return wg_fail(WG_EINVAL, "missing state pointer");
-    if (b->K > 0 && (!b->edges || !b->inc || !b->inc_off)) return wg_fail(WG_EINVAL, "missing edge pointer");
-    if (b->M > 32767) return wg_fail(WG_ERANGE, "M=%d exceeds the 15-bit edge endpoint encoding", b->M);
-    if (!b->inc_off) return wg_fail(WG_EINVAL, "missing inc_off");
-    if (b->ragged < 0 || b->ragged > 2) return wg_fail(WG_EINVAL, "ragged must be 0, 1 or 2");
-    if (b->ragged && (!b->mass_off || !b->edge_off || !b->muscle_off))
-        return wg_fail(WG_EINVAL, "ragged batch without offsets");
-    if (!b->ragged && b->row) return wg_fail(WG_EINVAL, "row (a walker permutation) is for ragged batches only");
-    if (b->ragged == 2 && !wave_passes(b->M, b->K))
-        return wg_fail(WG_EINVAL, "ragged = 2 (wave tiles) needs M <= 64 and at most 8 spring passes (M=%d K=%d)", b->M, b->K);
-    return 0;
-}
-
-Geo uniform_geo(const wg_batch *b, int obs_stride, bool no_lite = false) {
-    Geo g{};
-    // walkers per workgroup: fill the 256 mass lanes, keep edges within EPL registers per lane,
-    // and make sure the grid has >= 512 workgroups when the batch allows it.
-    int W = std::max(1, NTHREADS / b->M);
-    if (b->M > 64 && env_int("WG_WIDE", 1)) {
-        // M > 64: the workgroup size (256..512 threads) that leaves the fewest idle lanes; 100-mass chains run
-        // 5 walkers on 512 threads (98 % of the lanes busy) instead of 2 on 256 (78 %)
-        int best = 0, bestT = NTHREADS;
-        for (int T = NTHREADS; T <= MAXT; T += 64) {
-            const int w = T / b->M;
-            if (w >= 1 && (int64_t)w * b->M * bestT > (int64_t)best * T) { best = w * b->M; bestT = T; W = w; }
-        }
-    }
-    if (b->K > 0) W = std::max(1, std::min(W, EPL * MAXT / std::max(1, b->K)));
-    while (W > 1 && (b->N + W - 1) / W < 512) W = std::max(1, W / 2);
-    g.W = W;
-    const bool shfl_shape = b->M <= 64 && (64 % b->M) == 0 && !(WG_ABLATE & 64);
-    for (;;) {
-        g.Pcap = g.W * b->M; g.Ecap = g.W * b->K; g.Ucap = g.W * b->A;
-        g.tbytes = std::max(g.Ecap * 3 * 8, g.W * std::max(0, obs_stride) * 4);
-        g.lite = (shfl_shape && g.W * b->M <= MAXT && !no_lite) ? 1 : 0;   // pair passes need the LDS copies
-        g.threads = std::min(MAXT, std::max(64, ((g.W * b->M + 63) / 64) * 64));
-        if (b->K > 0 && g.W * b->K > EPL * g.threads) g.threads = MAXT;
-        g.lds = carve_bytes(g);
-        if (g.lds <= 64 * 1024 || g.W == 1) break;
-        g.W = std::max(1, g.W / 2);
-    }
-    g.invM = 1.f / (float)b->M;
-    g.invK = 1.f / (float)std::max(1, b->K);
-    g.invA = 1.f / (float)std::max(1, b->A);
-    return g;
-}
-
-Geo ragged_geo(const wg_batch *b) {
-    Geo g{};
-    g.threads = NTHREADS;
-    g.W = RAG_W;
-    g.Pcap = std::max(RAG_P, b->M);
-    g.Ecap = std::max(RAG_E, b->K);
-    g.Ucap = std::max(RAG_U, b->A);
-    g.tbytes = g.Ecap * 3 * 8;
-    g.lite = 0;
-    g.lds = carve_bytes(g);
-    g.invM = g.invK = g.invA = 0.f;
-    return g;
-}
-
-template <bool STEP, bool RAGGED, bool IN3D, int PWD, bool SHFL>
-int launch(const wg_batch *b, const KParams &kp, const float *action, int cols, int astride,
-           const wg_outputs &o, const int32_t *plan, int blocks, const Geo &g, hipStream_t stream) {
-    // (+ the static 512 B of the powf tables in LDS)
-    const int lds_static = (int)(sizeof(s_pw_log2) + sizeof(s_pw_exp2));
-    if (g.lds + lds_static > LDS_LIMIT)
-        return wg_fail(WG_ERANGE, "workgroup needs %d B of LDS (> 160 KiB)", g.lds + lds_static);
-    WG_KLAUNCH((walker_step_kernel<STEP, RAGGED, IN3D, PWD, SHFL>), dim3(blocks), dim3(g.threads), (uint32_t)g.lds, stream,
-               *b, kp, action, cols, astride, kout(o), plan, g);
-    return wg_launched("launch");
-}
-
-// register (shuffle) reductions: every walker's masses are adjacent lanes of one wave
-bool shfl_ok(const wg_batch *b, const Geo &g) { return !b->ragged && g.lite; }
-
-template <bool STEP, int PWD>
-int dispatch2(const wg_batch *b, const KParams &kp, bool in3d, const float *a, int cols, int astride,
-              const wg_outputs &o, const int32_t *plan, int blocks, const Geo &g, hipStream_t st) {
-    if (b->ragged) {
-        return in3d ? launch<STEP, true, true, PWD, false>(b, kp, a, cols, astride, o, plan, blocks, g, st)
-                    : launch<STEP, true, false, PWD, false>(b, kp, a, cols, astride, o, plan, blocks, g, st);
-    }
-    if (PWD == 0 && shfl_ok(b, g)) {
-        return in3d ? launch<STEP, false, true, 0, true>(b, kp, a, cols, astride, o, plan, blocks, g, st)
-                    : launch<STEP, false, false, 0, true>(b, kp, a, cols, astride, o, plan, blocks, g, st);
-    }
-    return in3d ? launch<STEP, false, true, PWD, false>(b, kp, a, cols, astride, o, plan, blocks, g, st)
-                : launch<STEP, false, false, PWD, false>(b, kp, a, cols, astride, o, plan, blocks, g, st);
-}
-// ---- lean kernel selection: uniform batch, M | 64 with M >= 4, the wave's edges in <= 8 register
-// passes, its muscles in one pass, and a workgroup LDS footprint that keeps >= 2 workgroups per CU.
-// Knobs (read on every call, so one process can A/B them): WG_LEAN=0 selects the barrier kernels;
-// WG_LEAN_WAVES 1/2/4 waves per workgroup; WG_LEAN_PRIO 0/1 load-phase priority.
-int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return (e && *e) ? atoi(e) : dflt;
-}
-
-bool lean_enabled() { return env_int("WG_LEAN", 1) != 0; }
-
-// The compact spring records (wg_batch.edges8, ABI 15) are addressed by tile-relative lane roles: a lean launch reads
-// them only with the standard tile of 64 / M walkers per wave (small batches whose tiles lean_geo halves, and WG_LEAN_WPW,
-// keep the 16-B records).  WG_EDGE8=0 (read on every launch, like WG_LEAN) forces the 16-B records.
-bool use_edge8(const wg_batch *b, const LeanGeo &g) {
-    return b->edges8 != nullptr && g.wpw * b->M == 64 && env_int("WG_EDGE8", 1) != 0;
-}
-
-// The barrier-free kernels address their loads as SGPR base + 32-bit byte offset (at_u32): every array of the batch
-// must then span less than 4 GiB (positions 12 B and spring records 16 B per element dominate; M, K are maxima).
-bool u32_bytes(const wg_batch *b) {
-    const int64_t lim = 1ll << 32;
-    return (int64_t)b->N * b->M * 12 < lim && (int64_t)b->N * b->K * 16 < lim && (int64_t)b->N * b->A * 8 < lim &&
-           (int64_t)b->N * (b->M + 1) * 2 < lim;
-}
-// and their observation rows as 32-bit byte offsets (WG_ST)
-bool obs_u32(const wg_batch *b, int obs_stride) { return (int64_t)b->N * std::max(obs_stride, 1) * 4 < (1ll << 32); }
-
-// spring passes of a lean wave tile: ceil(wpw * K / 64), at most 8 (lean_geo)
-int lean_passes(const LeanGeo &g, const wg_batch *b) { return (g.wpw * b->K + 63) / 64; }
-
-bool lean_geo(const wg_batch *b, int obs_stride, LeanGeo *out, int spring_mode = 0) {
-    const int M = b->M;
-    if (b->ragged || M < 4 || M > 64 || (64 % M) != 0 || b->K < 1 || !lean_enabled() || (WG_ABLATE & 128)) return false;
-    if (spring_mode != 0) return false;          // the G2-compat element runs on the workgroup kernel
-    // 32-bit element offsets inside the kernel, 32-bit byte offsets for its loads (at_u32)
-    if ((int64_t)b->N * b->M * 3 >= (1ll << 31) || (int64_t)b->N * b->K * 4 >= (1ll << 31) ||
-        !obs_u32(b, obs_stride) || !u32_bytes(b))
-        return false;
-    LeanGeo g{};
-    g.wpw = 64 / M;
-    // small batches: fewer walkers per wave until there are 512 wave tiles (two per CU), so a latency-bound step
-    // spreads over more waves (4,096 Balance-v0 walkers: 16 -> 8 walkers per wave, 6.40 -> 5.97 us per step,
-    // profiles/r02_ab_balance4096_wpw.json); WG_LEAN_WPW (experiment) caps the count
-    while (g.wpw > 1 && (b->N + g.wpw - 1) / g.wpw < 512) g.wpw >>= 1;
-    const int wcap = env_int("WG_LEAN_WPW", 0);
-    if (wcap > 0 && wcap < g.wpw) g.wpw = wcap;
-    g.lgM = 0;
-    while ((1 << g.lgM) < M) g.lgM++;
-    if (lean_passes(g, b) > 8 || g.wpw * b->A > 64) return false;
-    // waves per workgroup: 4 (one workgroup per four tiles) unless the batch has no more tiles than the chip has SIMDs,
-    // where one wave per workgroup spreads the latency-bound step over twice the CUs (4,096 Balance-v0 walkers: 5.45
-    // against 5.60 us, 65,536 canonical: 44.31 against 44.01; profiles/r04m_ab_*_wpb.json); WG_LEAN_WAVES overrides
-    const int wpb = env_int("WG_LEAN_WAVES", 0);
-    g.wpb = (wpb == 1 || wpb == 2 || wpb == 4) ? wpb : ((b->N + g.wpw - 1) / g.wpw <= 1024 ? 1 : 4);
-    const int ew = g.wpw * b->K;                          // springs of a full wave tile
-    g.pl = (ew + 3) & ~3;                                 // spring-term slots: 16-B aligned regions
-    // t (f64 x3) | df (f32 x3) | incidence words | x (observation rows go from registers to HBM, no LDS tile)
-    g.off_df = align16(g.pl * 24);
-    g.off_inc = g.off_df + align16(g.pl * 12);
-    g.off_x = g.off_inc + align16(ew * 4 + 4);              // + the zero word after the last list (mass_accumulate_v2)
-    g.slice = g.off_x + align16(std::max(1, g.wpw * b->A) * 4);
-    if (4 * g.slice > 80 * 1024) return false;
-    g.invK = 1.f / (float)b->K;
-    g.invA = 1.f / (float)std::max(1, b->A);
-    g.invM = 1.f / (float)M;
-    g.nblk = (b->N + g.wpb * g.wpw - 1) / (g.wpb * g.wpw);   // the grid of a lean launch: one tile per wave
-    *out = g;
-    return true;
-}
-
-// walker_step_lean1's preloaded word: bits 0..29 the workgroup count, bit 30 the XCD-order flag (WG_XCD bit 1), bit 31
-// the load-phase priority flag (WG_LEAN_PRIO)
-int lean1_nblkx(const LeanGeo &g, const KParams &kp) {
-    return (int)((unsigned)g.nblk | ((unsigned)(kp.xcd & 2) << 29) | ((unsigned)(kp.prio != 0) << 31));
-}
-
-// ---- instance selection: the runtime (in3d, passes, compact records) of a launch as compile-time tags, in one place.
-// A launch site is one call whose generic lambda names its kernel with the tags' values; `if constexpr` in the lambda
-// keeps the instances nobody launches (NE 1 of walker_step_lean, FIX outside E8 and NE 1-4) uninstantiated.
-template <class F>
-void with_flag(bool v, F &&f) {
-    if (v) f(std::true_type{});
-    else f(std::false_type{});
-}
-// the pass count rounded up to an instantiated NE: 1, 2, 3, 4, 8
-template <class F>
-void with_passes(int ne, F &&f) {
-    if (ne <= 1) f(std::integral_constant<int, 1>{});
-    else if (ne == 2) f(std::integral_constant<int, 2>{});
-    else if (ne == 3) f(std::integral_constant<int, 3>{});
-    else if (ne == 4) f(std::integral_constant<int, 4>{});
-    else f(std::integral_constant<int, 8>{});
-}
-template <class F>
-void with_instance(bool in3d, int ne, F &&f) {   // f(IN3D, NE)
-    with_flag(in3d, [&](auto d3) { with_passes(ne, [&](auto n) { f(d3, n); }); });
-}
-template <class F>
-void with_instance(bool in3d, int ne, bool e8, F &&f) {   // f(IN3D, NE, E8)
-    with_instance(in3d, ne, [&](auto d3, auto n) { with_flag(e8, [&](auto c8) { f(d3, n, c8); }); });
-}
-
-// The caller's actions: cols values in row w of step s at ptr[s * step + w * stride]; ptr NULL = none
-struct Actions {
-    const float *ptr;
-    int32_t cols, stride;
-    int64_t step;
-    Actions at(int s) const { return Actions{ptr ? ptr + s * step : nullptr, cols, stride, step}; }
-};
-
-// The fixed-parameter instance (FIX) runs a launch whose every tile is full and whose batch, parameters, actions and
-// outputs are the default path's: compact records in 1..4 passes, no auto-reset, continuous actions for every muscle,
-// no pair passes, pins or radii, run1, midform 1 without conmid, unit observation scales (by bit pattern), every
-// per-step output but the optional steps asked for.  Anything else takes the generic instance, as a whole launch (a
-// partial last tile too).  WG_FIX=0 (read on every launch, like WG_EDGE8) forces the generic instance: the control arm
-// and the tests' cross-check.
-bool lean_fix_ok(const wg_batch *b, const KParams &kp, const Actions &a, const wg_outputs &o, const LeanGeo &g, bool e8,
-                 int ne, int ar_mode) {
-#ifdef WG_STAMPS
-    return false;
-#endif
-    if (WG_ABLATE != 0 || env_int("WG_FIX", 1) == 0) return false;
-    auto one = [](float f) {
-        uint32_t u;
-        memcpy(&u, &f, sizeof u);
-        return u == 0x3f800000u;
-    };
-    return e8 && ne >= 1 && ne <= 4 && ar_mode == 0 && b->N % g.wpw == 0 && g.wpw * b->M == 64 &&
-           b->A >= 1 && a.ptr != nullptr && a.cols >= b->A && a.stride >= b->A && kp.action_mode == 0 &&
-           kp.pair_mode == 0 && !b->pinned && !b->radius && kp.integrator != 2 && kp.midform == 1 && kp.conmid == 0 &&
-           one(kp.pk) && one(kp.vk) && one(kp.ak) && one(kp.mk) &&
-           o.obs && o.reward && o.done && o.centroid && o.energy;
-}
-// launches that took the fixed-parameter instance, this process (wg_fix_launches: the tests read which instance ran)
-std::atomic<long long> g_fix_launches{0};
-
-// One step of a uniform batch on the lean kernels.  ar_mode (wg_params.auto_reset) != 0: the AR instances (the auto-reset
-// tail, ABI 16); a launch that lean_fix_ok admits: the FIX instances.  One spring pass is walker_step_lean1's, with its
-// leading arguments preloaded (the compact records take the spring records' slot).
-int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const Actions &a, const wg_outputs &o, const LeanGeo &g,
-                hipStream_t st, int ar_mode = 0) {
-    const int ne = lean_passes(g, b);
-    // WG_LDS_PAD (diagnostic): extra LDS bytes per workgroup, to measure the kernel at lower occupancy
-    const uint32_t lds = (uint32_t)(g.wpb * g.slice + std::max(0, env_int("WG_LDS_PAD", 0)));
-    const bool e8 = use_edge8(b, g);
-    const bool fix = lean_fix_ok(b, kp, a, o, g, e8, ne, ar_mode);   // (E8, 1..4 passes, no auto-reset)
-    const dim3 grid(g.nblk), block(64 * g.wpb);
-    with_instance(in3d, ne, e8, [&](auto d3, auto n, auto c8) {
-        constexpr bool D3 = decltype(d3)::value, E8 = decltype(c8)::value;
-        constexpr int NE = decltype(n)::value;
-        if constexpr (NE == 1) {
-            const void *recs = E8 ? static_cast<const void *>(b->edges8) : static_cast<const void *>(b->edges);
-            auto go = [&](auto kernel, auto reset) {
-                WG_KLAUNCH(kernel, grid, block, lds, st, b->pos, b->vel, recs, b->inc, b->N, b->M, b->K, g.wpw, g.wpb,
-                           lean1_nblkx(g, kp), *b, kp, a.ptr, a.cols, a.stride, kout(o), g, reset);
-            };
-            if constexpr (E8) {
-                if (fix) return go(walker_step_lean1<D3, true, false, true>, KNoReset{});
-            }
-            if (ar_mode) go(walker_step_lean1<D3, E8, true>, kreset(o, ar_mode));
-            else go(walker_step_lean1<D3, E8>, KNoReset{});
-        } else {
-            auto go = [&](auto kernel, const auto &batch, auto reset) {
-                WG_KLAUNCH(kernel, grid, block, lds, st, batch, kp, a.ptr, a.cols, a.stride, kout(o), g, reset);
-            };
-            if constexpr (E8 && NE <= 4) {
-                if (fix) return go(walker_step_lean<D3, NE, true, false, true>, kbatch15(b), KNoReset{});
-            }
-            if (ar_mode) go(walker_step_lean<D3, NE, E8, true>, *b, kreset(o, ar_mode));
-            else go(walker_step_lean<D3, NE, E8>, kbatch15(b), KNoReset{});
-        }
-    });
-    if (const int rc = wg_launched("launch")) return rc;
-    if (fix) g_fix_launches.fetch_add(1, std::memory_order_relaxed);
-    return 0;
-}
-
-// n_steps steps of a uniform batch in one launch, the state in registers between them.  ar_mode != 0: the AR twin, one
-// LDS word per walker (its episode count) behind each wave's slice.  (A plain launch: wg_time_step never comes here.)
-int launch_lean_rollout(const wg_batch *b, const KParams &kp, bool in3d, const Actions &a, const wg_outputs &o,
-                        int n_steps, const LeanGeo &g0, hipStream_t st, int ar_mode = 0) {
-    LeanGeo g = g0;
-    const KResetRes ar{kreset(o, ar_mode), g.slice};
-    if (ar_mode) g.slice += align16(g.wpw * 4);
-    const dim3 grid(g.nblk), block(64 * g.wpb);
-    const int lds = g.wpb * g.slice;
-    with_instance(in3d, lean_passes(g, b), use_edge8(b, g), [&](auto d3, auto n, auto c8) {
-        constexpr bool D3 = decltype(d3)::value, E8 = decltype(c8)::value;
-        constexpr int NE = decltype(n)::value;
-        if (ar_mode)
-            hipLaunchKernelGGL((walker_rollout_lean<D3, NE, E8, true>), grid, block, lds, st, *b, kp, a.ptr, a.cols,
-                               a.stride, a.step, kout(o), n_steps, g, ar);
-        else
-            hipLaunchKernelGGL((walker_rollout_lean<D3, NE, E8>), grid, block, lds, st, *b, kp, a.ptr, a.cols, a.stride,
-                               a.step, kout(o), n_steps, g, KNoReset{});
-    });
-    return wg_launched("launch");
-}
-
-// ---- argument checks that run() and rollout_policy() share: 0, or the refusal.  Each entry calls them in the order its
-// callers have always seen (the first of several refusals is part of the contract: tests/test_refusal_order_cpu.py).
-// auto-reset (ABI 16): everything the reset tail reads
-int check_auto_reset(const wg_batch *b, int ar_mode) {
-    if (ar_mode & ~3) return wg_fail(WG_EINVAL, "auto_reset %d: bits 1 (done) and 2 (non-finite) only", ar_mode);
-    if (!b->init_pos || !b->init_vel || !b->init_acc || !b->init_muscle_x)
-        return wg_fail(WG_EINVAL, "auto_reset needs the snapshot (init_pos, init_vel, init_acc, init_muscle_x)");
-    if (!b->episodes) return wg_fail(WG_EINVAL, "auto_reset needs the episodes array");
-    if (b->reset_noise && b->reset_noise_rows < 1)
-        return wg_fail(WG_EINVAL, "auto_reset: reset_noise with reset_noise_rows %d < 1", b->reset_noise_rows);
-    if (b->reset_noise && b->reset_noise_stride < 3ll * b->N * b->M)
-        return wg_fail(WG_EINVAL, "auto_reset: reset_noise_stride %lld < 3 * P = %lld",
-                       (long long)b->reset_noise_stride, 3ll * b->N * b->M);
-    return 0;
-}
-int check_integrator(const wg_params *p) {
-    return p->integrator < 0 || p->integrator > 2 ? wg_fail(WG_EINVAL, "integrator must be 0/1 (run1) or 2 (run2)") : 0;
-}
-int check_muscle_bounds(const wg_batch *b) {
-    return b->muscle_bounds ? 0 : wg_fail(WG_EINVAL, "actions need muscle_bounds");
-}
-int check_discrete(const wg_batch *b, const wg_params *p) {
-    return p->action_mode == 1 && !b->muscle_stride ? wg_fail(WG_EINVAL, "discrete actions need muscle_stride") : 0;
-}
-
-// a batch's observation row length under p: Creature.getstat's list (gym/optimized_walker.py:129-162)
-int obs_row_len(const wg_batch *b, const wg_params *p) {
-    return 3 * (p->in3d ? 3 : 2) * b->M + (p->conmid ? 3 : 0) + b->A;
-}
-
-// wg_rollout_policy: every argument checked, then one walker_rollout_policy launch.  The wave's LDS slice is the lean
-// kernel's plus the walkers' observation rows, hidden vectors and actions.
-// episodes (wg_rollout_episodes): the AR instances, with auto-reset's own checks in place of the auto_reset refusal, the
-// accounting of `st`, and eight words per walker in the slice instead of four.
-int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o, int32_t n_steps,
-                   hipStream_t stream, bool episodes = false, const wg_episode_stats *st = nullptr) {
-    const char *fn = episodes ? "wg_rollout_episodes" : "wg_rollout_policy";
-    int rc = validate(b);
-    if (rc) return rc;
-    if (!p) return wg_fail(WG_EINVAL, "null params");
-    if (!pol) return wg_fail(WG_EINVAL, "%s: null policy", fn);
-    if (!pol->w2) return wg_fail(WG_EINVAL, "%s: null w2", fn);
-    if (n_steps < 1) return wg_fail(WG_EINVAL, "%s: n_steps %d < 1", fn, n_steps);
-    if (pol->hidden < 0 || pol->hidden > 256)
-        return wg_fail(WG_EINVAL, "%s: hidden %d outside 0..256", fn, pol->hidden);
-    if (pol->hidden > 0 && !pol->w1) return wg_fail(WG_EINVAL, "%s: hidden %d with a null w1", fn, pol->hidden);
-    if (pol->act_dim < 1 || pol->act_dim > b->A)
-        return wg_fail(WG_EINVAL, "%s: act_dim %d outside 1..A = %d", fn, pol->act_dim, b->A);
-    if (pol->obs_dim != obs_row_len(b, p))
-        return wg_fail(WG_EINVAL, "%s: obs_dim %d, the batch's rows have %d values", fn, pol->obs_dim,
-                    obs_row_len(b, p));
-    if (pol->n_sets < 1 || b->N % pol->n_sets != 0)
-        return wg_fail(WG_EINVAL, "%s: n_sets %d does not divide N = %d", fn, pol->n_sets, b->N);
-    if (!(pol->act_limit > 0.f)) return wg_fail(WG_EINVAL, "%s: act_limit must be > 0 (+inf allowed)", fn);
-    if (!episodes && p->auto_reset != 0)
-        return wg_fail(WG_EINVAL, "%s: auto_reset %d (the resident loop has no reset tail)", fn, p->auto_reset);
-    if (episodes) {
-        if (p->auto_reset == 0)
-            return wg_fail(WG_EINVAL, "%s: auto_reset is 0 (without episode roll-over use wg_rollout_policy)", fn);
-        if ((rc = check_auto_reset(b, p->auto_reset))) return rc;   // (auto-reset's own checks, as wg_step makes them)
-        if (!st) return wg_fail(WG_EINVAL, "%s: null episode stats", fn);
-        if (st->ep_slots < 0) return wg_fail(WG_EINVAL, "%s: ep_slots %d < 0", fn, st->ep_slots);
-        if ((st->ep_return || st->ep_length) && st->ep_slots == 0)
-            return wg_fail(WG_EINVAL, "%s: ep_return / ep_length with ep_slots 0", fn);
-        if (pol->return_out || pol->length_out)
-            return wg_fail(WG_EINVAL, "%s: return_out / length_out are defined by the first done (wg_rollout_policy); "
-                                   "the episode stats replace them", fn);
-    }
-    if ((rc = check_integrator(p)) || (rc = check_muscle_bounds(b)) || (rc = check_discrete(b, p))) return rc;
-    wg_outputs out = o ? *o : wg_outputs{};
-    if ((out.obs || (episodes && out.final_obs)) && out.obs_stride < pol->obs_dim)
-        return wg_fail(WG_EINVAL, "%s: obs_stride %d < obs_dim %d", fn, out.obs_stride, pol->obs_dim);
-    if (episodes && (out.nonfinite || out.momentum))
-        return wg_fail(WG_EINVAL, "%s: nonfinite / momentum are not produced here", fn);
-    if (!episodes && (out.nonfinite || out.momentum || out.reset || out.final_obs))
-        return wg_fail(WG_EINVAL, "%s: nonfinite / momentum / reset / final_obs are not produced here", fn);
-    LeanGeo lg{};
-    if (b->ragged || p->spring_mode != 0 || p->pair_mode != 0 ||
-        !lean_geo(b, (out.obs || (episodes && out.final_obs)) ? out.obs_stride : 0, &lg, p->spring_mode))
-        return wg_fail(WG_EINVAL, "%s needs a batch the resident lean kernel takes (uniform, M dividing 64, "
-                               "spring_mode 0, pair_mode 0, WG_LEAN not 0)", fn);
-    if (b->N == 0) return 0;
-    const KParams kp = make_kparams(*p);
-    KPolicy kpol{};
-    kpol.w1 = pol->hidden > 0 ? pol->w1 : nullptr; kpol.b1 = pol->hidden > 0 ? pol->b1 : nullptr;
-    kpol.w2 = pol->w2; kpol.b2 = pol->b2;
-    kpol.action_out = pol->action_out; kpol.return_out = pol->return_out; kpol.length_out = pol->length_out;
-    kpol.action_out_step = pol->action_out_step;
-    kpol.act_limit = pol->act_limit;
-    kpol.D = pol->obs_dim; kpol.H = pol->hidden; kpol.C = pol->act_dim;
-    kpol.wps = b->N / pol->n_sets;
-    kpol.off_row = lg.slice;
-    kpol.off_h = kpol.off_row + align16(lg.wpw * kpol.D * 4);
-    kpol.off_a = kpol.off_h + align16(std::max(1, lg.wpw * kpol.H) * 4);
-    kpol.off_w = kpol.off_a + align16(lg.wpw * kpol.C * 4);
-    lg.slice = kpol.off_w + lg.wpw * (episodes ? 32 : 16);
-    int lds = lg.wpb * lg.slice;
-    if (lds > 80 * 1024) return wg_fail(WG_ERANGE, "%s: workgroup needs %d B of LDS (> 80 KiB)", fn, lds);
-    // a shared policy's weights staged in LDS where that costs no resident wave: as many workgroups per CU (160 KiB of
-    // LDS, the kernel's register budget of 4 waves per SIMD, 3 at NE 8) with the weights as without.  (Staged at the
-    // price of occupancy the canonical batch ran 90.6 us per step with H = 32 against 73.8 through L2; the one-wave
-    // workgroups of a small batch keep their occupancy and run 7.96 against 9.03: profiles/r08_policy_rollout_ab.json.)
-    // WG_POLICY_STAGE (read on every call, like WG_LEAN): 0 never, 2 whenever the workgroup stays within 80 KiB
-    const int wbytes = 4 * (kpol.D * kpol.H + (kpol.H > 0 ? kpol.H : kpol.D) * kpol.C);
-    const int ne = lean_passes(lg, b);
-    const int cap = std::max(1, (ne > 4 ? 12 : 16) / lg.wpb);
-    const int stage = env_int("WG_POLICY_STAGE", 1);
-    const bool free_stage = std::min(cap, LDS_LIMIT / lds) == std::min(cap, LDS_LIMIT / (lds + wbytes));
-    kpol.off_wts = -1;
-    if (pol->n_sets == 1 && lds + wbytes <= 80 * 1024 && (stage == 2 || (stage == 1 && free_stage))) {
-        kpol.off_wts = lds;
-        lds += wbytes;
-    }
-    const dim3 grid(lg.nblk), block(64 * lg.wpb);
-    const KReset ar = kreset(out, p->auto_reset);
-    with_instance(p->in3d != 0, ne, use_edge8(b, lg), [&](auto d3, auto n, auto c8) {
-        constexpr bool D3 = decltype(d3)::value, E8 = decltype(c8)::value;
-        constexpr int NE = decltype(n)::value;
-        if (episodes)
-            hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8, true>), grid, block, lds, stream, *b, kp, kpol,
-                               kout(out), n_steps, lg, ar, *st);
-        else
-            hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8>), grid, block, lds, stream, *b, kp, kpol, kout(out),
-                               n_steps, lg, KNoReset{}, KNoReset{});
-    });
-    return wg_launched("launch");
-}
-
-// ---- ragged wave kernel (wg_batch.ragged = 2): spring passes, planner, geometry, launch
-// Spring passes of a wave tile from the batch maxima: enough for the longest walker, and for 64 masses of the
-// densest one (K / M springs per mass), rounded up to an instantiated NE (1, 2, 3, 4, 8); 0 = not eligible.
-int wave_passes(int M, int K) {
-    if (M < 1 || M > 64 || K < 0) return 0;
-    int ne = std::max((K + 63) / 64, (K + M - 1) / M);
-    ne = std::max(ne, 1);
-    if (ne > 8) return 0;
-    return ne <= 4 ? ne : 8;
-}
-
-bool rag_geo(const wg_batch *b, int obs_stride, RagGeo *out) {
-    const int ne = wave_passes(b->M, b->K);
-    if (b->ragged != 2 || ne == 0 || b->A > 64 || !u32_bytes(b) || !obs_u32(b, obs_stride)) return false;
-    RagGeo g{};
-    const int wpb = env_int("WG_LEAN_WAVES", 4);
-    g.wpb = (wpb == 1 || wpb == 2) ? wpb : 4;
-    const int ec = 64 * ne;                                      // spring slots of a tile
-    // spring terms t (f64 x3), later the per-mass reduction terms | damping forces df, later the walker partials |
-    // incidence words | muscle x | walker offsets and rows
-    g.off_df = align16(std::max(ec * 24, 4 * 64 * 6));
-    g.off_inc = g.off_df + align16(std::max(ec * 12, 4 * RW_MAXW * 8));
-    g.off_x = g.off_inc + align16(ec * 4 + 4);                   // + the read-ahead pad word (mass_accumulate_v2)
-    g.off_wo = g.off_x + align16(64 * 4);
-    g.slice = g.off_wo + align16(4 * (RW_MAXW + 1) * 3 + 4 * RW_MAXW + 12 * RW_MAXW);   // + the walkers' means
-    *out = g;
-    return true;
-}
-
-int launch_waves(const wg_batch *b, const KParams &kp, bool in3d, const Actions &a, const wg_outputs &o,
-                 const int32_t *plan, int ntiles, const RagGeo &g, hipStream_t st) {
-    const dim3 grid((ntiles + g.wpb - 1) / g.wpb), block(64 * g.wpb);
-    const uint32_t lds = (uint32_t)(g.wpb * g.slice);
-    with_instance(in3d, wave_passes(b->M, b->K), [&](auto d3, auto n) {
-        WG_KLAUNCH((walker_step_waves<decltype(d3)::value, decltype(n)::value>), grid, block, lds, st, *b, kp, a.ptr,
-                   a.cols, a.stride, kout(o), plan, ntiles, g);
-    });
-    return wg_launched("launch");
-}
-
-int reset_impl(const wg_batch *b, const float *noise, const uint8_t *mask, int zmode, hipStream_t stream) {
-    int rc = validate(b);
-    if (rc) return rc;
-    if (b->N == 0) return 0;
-    const long P = b->ragged ? -1 : (long)b->N * b->M;
-    const int blocks = P > 0 ? (int)std::min<long>((P + 255) / 256, 4096) : 1024;
-    hipLaunchKernelGGL(walker_reset_kernel, dim3(blocks), dim3(256), 0, stream, *b, noise, mask, zmode);
-    return wg_launched("reset launch");
-}
-
-template <bool STEP>
-int dispatch(const wg_batch *b, const KParams &kp, bool in3d, const float *a, int cols, int astride,
-             const wg_outputs &o, const int32_t *plan, int blocks, const Geo &g, hipStream_t st) {
-    return b->M <= 128 ? dispatch2<STEP, 0>(b, kp, in3d, a, cols, astride, o, plan, blocks, g, st)
-                       : dispatch2<STEP, 3>(b, kp, in3d, a, cols, astride, o, plan, blocks, g, st);
-}
-
-// the outputs of step s of a call (rows out_step / obs_step apart; the three-component ones 3 * out_step)
-wg_outputs outputs_at(const wg_outputs &o, int s) {
-    wg_outputs os = o;
-    if (os.obs) os.obs += s * os.obs_step;
-    if (os.reward) os.reward += s * os.out_step;
-    if (os.done) os.done += s * os.out_step;
-    if (os.energy) os.energy += s * os.out_step;
-    if (os.centroid) os.centroid += 3 * s * os.out_step;
-    if (os.steps) os.steps += s * os.out_step;
-    if (os.nonfinite) os.nonfinite += s * os.out_step;
-    if (os.momentum) os.momentum += 3 * s * os.out_step;
-    if (os.reset) os.reset += s * os.out_step;
-    if (os.final_obs) os.final_obs += s * os.obs_step;
-    return os;
-}
-
-// What a run() call is, beside the batch, parameters, outputs and plan.  Every entry fills it by field name.
-struct RunCall {
-    bool step;         // env steps; false: the outputs of the state as it is (wg_observe), one launch
-    bool resident;     // every step in one launch where the batch allows it (wg_rollout); false: a launch per step
-    bool check_only;   // check every argument, launch nothing (wg_run_ranges, wg_time_step: before their first launch)
-    int s_first;       // the index of this call's first step in the caller's whole call (its outputs and actions)
-    int s_total;       // the steps of that whole call when this is one slice of it: 0 = s_first + n_steps, < 0 = every
-                       // step keeps its acc / contact stores (wg_time_step)
-    Actions act;
-};
-
-int run(const wg_batch *b, const wg_params *p, const wg_outputs *o, int32_t n_steps, const int32_t *plan,
-        int32_t plan_blocks, hipStream_t stream, const RunCall &c) {
-    const bool step = c.step;
-    Actions act = c.act;
-    if (!act.ptr) act.step = 0;
-    int rc = validate(b);
-    if (rc) return rc;
-    if (!p) return wg_fail(WG_EINVAL, "null params");
-    if (b->N == 0 || n_steps <= 0) return 0;
-    if (act.ptr && (act.cols < 0 || act.stride < act.cols)) return wg_fail(WG_EINVAL, "bad action stride");
-    if (act.ptr && (rc = check_discrete(b, p))) return rc;
-    if ((rc = check_integrator(p))) return rc;
-    if (act.ptr && (rc = check_muscle_bounds(b))) return rc;
-    if (b->ragged && (!plan || plan_blocks <= 0)) return wg_fail(WG_EINVAL, "ragged batch needs a plan");
-    wg_outputs out = o ? *o : wg_outputs{};
-    if (out.obs && out.obs_stride <= 0) return wg_fail(WG_EINVAL, "obs_stride must be > 0");
-    KParams kp = make_kparams(*p);
-    const Geo g = b->ragged ? ragged_geo(b) : uniform_geo(b, out.obs ? out.obs_stride : 0, step && p->pair_mode != 0);
-    if (g.W > g.threads) return wg_fail(WG_ERANGE, "more than %d walkers per workgroup", g.threads);
-    const int blocks = b->ragged ? plan_blocks : (b->N + g.W - 1) / g.W;
-    LeanGeo lg{};
-    const bool act_u32 = !act.ptr || (int64_t)b->N * act.stride * 4 < (1ll << 32);   // at_u32 action offsets
-    const bool use_lean = step && act_u32 && lean_geo(b, out.obs ? out.obs_stride : 0, &lg, p->spring_mode);
-    RagGeo rgeo{};
-    const bool use_waves = step && act_u32 && p->spring_mode == 0 && p->pair_mode == 0 && lean_enabled() &&
-                           rag_geo(b, out.obs ? out.obs_stride : 0, &rgeo);
-    if (p->spring_mode < 0 || p->spring_mode > 2)
-        return wg_fail(WG_EINVAL, "spring_mode %d: 0 (engine.py), 1 (G2 element), 2 (G3 engine) only", p->spring_mode);
-    if (step && (p->pair_mode & ~31))
-        return wg_fail(WG_EINVAL, "pair_mode %d: bits 1 (gravity), 2 (coulomb), 4 (bounce), 8 (G2 gravity_vec), "
-                                  "16 (electrostatic) only", p->pair_mode);
-    if (step && p->pair_mode != 0 && p->spring_mode != 0)
-        return wg_fail(WG_EINVAL, "pair_mode %d needs spring_mode 0", p->pair_mode);
-    if (step && (p->pair_mode & 4) && !b->radius)
-        return wg_fail(WG_EINVAL, "pair_mode 4 (bounce) needs the radius array");
-    // auto-reset (ABI 16): fused into the lean step kernels only; everything it reads checked here
-    const int ar_mode = step ? p->auto_reset : 0;
-    if (ar_mode) {
-        if ((rc = check_auto_reset(b, ar_mode))) return rc;
-        if (p->pair_mode != 0) return wg_fail(WG_EINVAL, "auto_reset needs pair_mode 0 (pair_mode %d)", p->pair_mode);
-        if (!use_lean)
-            return wg_fail(WG_EINVAL, "auto_reset needs a batch the lean kernel takes (uniform, M dividing 64, "
-                                      "spring_mode 0, pair_mode 0, WG_LEAN not 0): the ragged wave kernel and the "
-                                      "workgroup kernel have no auto-reset");
-    }
-    if (c.check_only) return 0;
-    const bool in3d = p->in3d != 0;
-    const bool extras = out.nonfinite || out.momentum;   // opt-in per-walker info after each step (ABI 10)
-    auto info_pass = [&](const wg_outputs &os) -> int {
-        if (!(os.nonfinite || os.momentum)) return 0;
-        hipLaunchKernelGGL(walker_info_kernel, dim3((b->N + 255) / 256), dim3(256), 0, stream, *b, os.nonfinite,
-                           os.momentum, b->ragged ? plan : nullptr, plan_blocks);
-        return wg_launched("info launch");
-    };
-    // (the resident rollout keeps the state in registers between steps: with the per-step info extras requested the
-    // steps run as per-step launches instead, bit-identical)
-    // (with auto-reset: the resident kernel's AR twin, the reset tail in its loop, where its episode counts fit beside
-    // the slices in the lean kernel's 80 KiB)
-    const bool ar_fits = !ar_mode || lg.wpb * (lg.slice + align16(lg.wpw * 4)) <= 80 * 1024;
-    if (c.resident && use_lean && p->pair_mode == 0 && !extras && ar_fits)   // one launch for every step
-        return launch_lean_rollout(b, kp, in3d, act, out, n_steps, lg, stream, ar_mode);
-    // acc and contact are read by nothing on the step path and overwritten by the next step: only the call's last step
-    // stores them (the info kernel reads acc: with its outputs requested every step does)
-    const int s_last = (c.s_total > 0 ? c.s_total : c.s_first + n_steps) - 1;
-    for (int s = c.s_first; s < c.s_first + n_steps; s++) {
-        kp.keep_aux = (c.s_total < 0 || s >= s_last || extras) ? 1 : 0;
-        const wg_outputs os = outputs_at(out, s);
-        const Actions a = act.at(s);
-        if (use_lean) rc = launch_lean(b, kp, in3d, a, os, lg, stream, ar_mode);
-        else if (use_waves) rc = launch_waves(b, kp, in3d, a, os, plan, plan_blocks, rgeo, stream);
-        else rc = step ? dispatch<true>(b, kp, in3d, a.ptr, a.cols, a.stride, os, plan, blocks, g, stream)
-                       : dispatch<false>(b, kp, in3d, nullptr, 0, 0, os, plan, blocks, g, stream);
-        if (rc) return rc;
-        if (extras && (rc = info_pass(os))) return rc;
-    }
-    return 0;
-}
-
-// The greedy packer of wg_plan_waves and wg_plan_ragged: consecutive walkers join a group (a wave tile, a workgroup)
-// while its masses, springs, muscles and walkers stay within the caps; plan[i] .. plan[i + 1] are group i's walkers.
-// A walker over a cap by itself: refused where the group cannot hold it (strict: a wave tile), a group of its own
-// otherwise (the ragged workgroup kernel sizes its LDS from the batch maxima).
-struct PackCaps { int P, E, U, W; };
-int pack_plan(const int32_t *mass_off, const int32_t *edge_off, const int32_t *muscle_off, int N, int32_t *plan,
-              int max_groups, const PackCaps &c, bool strict, const char *unit) {
-    int groups = 0, w = 0;
-    plan[0] = 0;
-    while (w < N) {
-        int P = 0, E = 0, U = 0, n = 0;
-        while (w < N) {
-            const int m = mass_off[w + 1] - mass_off[w], k = edge_off[w + 1] - edge_off[w],
-                      a = muscle_off[w + 1] - muscle_off[w];
-            if (strict && (m > c.P || a > c.U || k > c.E)) return wg_fail(WG_EINVAL, "walker %d does not fit one wave", w);
-            if (n > 0 && (P + m > c.P || E + k > c.E || U + a > c.U || n + 1 > c.W)) break;
-            P += m; E += k; U += a; n++; w++;
-        }
-        if (groups + 1 > max_groups) return wg_fail(WG_ERANGE, "plan needs more than %d %s", max_groups, unit);
-        plan[++groups] = w;
-    }
-    return groups;
-}
-
 // the launch floor beside a small step (bench.py): an empty launch, and one coalesced load + store per thread
 __global__ __launch_bounds__(1024) void floor_empty_kernel(float *) {}
 __global__ __launch_bounds__(1024) void floor_load_store_kernel(const float *__restrict__ in, float *__restrict__ out) {
@@ -4234,6 +3574,9 @@ __global__ __launch_bounds__(1024) void floor_busy_kernel(const float *__restric
     for (int k = 0; k < 4096; k++) y = __builtin_fmaf(y, 0.99993896484375f, x);
     out[i] = y;
 }
+
+// the host side (the first section moved out of this unit)
+#include "wg_host.h"
 
 }  // namespace
 

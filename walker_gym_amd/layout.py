@@ -431,7 +431,7 @@ WAVE_MAX_WALKERS = 32    # walkers per wave tile (walker_hip.hip RW_MAXW)
 
 
 def wave_edge_passes(M: int, K: int) -> int:
-    """walker_hip.hip wave_passes (exported as wg_wave_edge_passes): spring passes of a wave tile for batch maxima
+    """csrc/wg_host.h wave_passes (exported as wg_wave_edge_passes): spring passes of a wave tile for batch maxima
     M, K; 0 = the batch cannot use the wave kernel."""
     if M < 1 or M > 64 or K < 0:
         return 0
