@@ -8,7 +8,9 @@ include/walker_hip.h, HIP kernels for gfx950).  Drop-in facades of the reference
   walker_gym_amd.env           Environment (G1 step(t) API)                  (gym/env.py)
   walker_gym_amd.snapshot      state.pkl read/write without unpickling       (gym/engine.py:199-212)
 Training on the device: walker_gym_amd.policy.MLPPolicy (evaluated inside the rollout kernels) and
-walker_gym_amd.es.EvolutionStrategy (seeded perturb / update kernels, wg_es_* in the header).
+walker_gym_amd.es.EvolutionStrategy (seeded perturb / update kernels, wg_es_* in the header);
+BatchedPhysicsEnv.rollout_stochastic and walker_gym_amd.pg (seeded action noise in the rollout kernel, the GAE kernel,
+collect() for PPO: wg_rollout_stochastic / wg_gae).
 Importing the package needs no GPU; stepping does (no CPU fallback).
 """
 from .engine import Config, DingPoint, Point, to_data  # noqa: F401
@@ -29,6 +31,12 @@ def __getattr__(name):
     if name == "EvolutionStrategy":
         from . import es
         return es.EvolutionStrategy
+    if name == "pg":   # policy-gradient support: the noise and GAE restatements, gae(), collect()
+        import importlib
+        return importlib.import_module(".pg", __name__)
+    if name == "rollout_stochastic":   # BatchedPhysicsEnv.rollout_stochastic(env, policy, n_steps, sigma, seed, ...)
+        from . import batched_env
+        return batched_env.BatchedPhysicsEnv.rollout_stochastic
     if name in ("PhysicsEnv", "make_env"):
         from . import optimized_env
         return getattr(optimized_env, name)

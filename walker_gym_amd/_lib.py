@@ -86,10 +86,17 @@ class WgEs(C.Structure):
                 ("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp)]
 
 
+class WgActionNoise(C.Structure):
+    """wg_action_noise: the seeded exploration noise of wg_rollout_stochastic and its optional per-step outputs."""
+    _fields_ = [("seed", C.c_uint64), ("step_base", C.c_uint32), ("walker_base", C.c_uint32), ("sigma", _vp),
+                ("raw_out", _vp), ("raw_out_step", C.c_int64), ("eps_out", _vp), ("eps_out_step", C.c_int64)]
+
+
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
            "wg_step_simple", "wg_observe_simple", "wg_reset", "wg_reset_noise", "wg_plan_ragged", "wg_plan_waves",
            "wg_wave_edge_passes", "wg_plan_errors", "wg_launch_geometry", "wg_launch_floor", "wg_time_step",
-           "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches", "wg_es_perturb", "wg_es_update")
+           "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches", "wg_es_perturb", "wg_es_update",
+           "wg_rollout_stochastic", "wg_gae")
 
 _lib = None
 _lock = threading.Lock()
@@ -120,6 +127,11 @@ def load(path: str | None = None):
                                         C.POINTER(WgOutputs), C.c_int32, _vp]
         L.wg_rollout_episodes.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), C.POINTER(WgPolicy),
                                           C.POINTER(WgOutputs), C.POINTER(WgEpisodeStats), C.c_int32, _vp]
+        L.wg_rollout_stochastic.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), C.POINTER(WgPolicy),
+                                            C.POINTER(WgActionNoise), C.POINTER(WgOutputs), C.POINTER(WgEpisodeStats),
+                                            C.c_int32, _vp]
+        L.wg_gae.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_float, _vp, _vp,
+                             _vp]
         L.wg_es_perturb.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp]
         L.wg_es_update.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp, C.c_double, C.c_float, _vp, _vp, _vp, _vp]
         L.wg_step_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,

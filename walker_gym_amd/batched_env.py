@@ -660,6 +660,81 @@ class BatchedPhysicsEnv:
         self._stale = _ROLLOUT_STALE
         return res
 
+    def rollout_stochastic(self, policy, n_steps: int, sigma, seed: int, step_base: int = 0, walker_base: int = 0,
+                           obs_out=None, reward_out=None, done_out=None, steps_out=None, action_out=None,
+                           raw_action_out=None, eps_out=None, reset_out=None, final_obs_out=None,
+                           episode_slots: int = 0) -> dict:
+        """rollout_policy (auto-reset off) or rollout_episodes (auto-reset on) with seeded exploration noise in the
+        policy's output layer, in ONE launch (wg_rollout_stochastic).  Output unit c of walker w at the call's step s:
+            u = y + sigma[set][c] * aeps(seed, step_base + s, walker_base + w, c);   a = clip(u, -L, L)
+        with y the deterministic pre-clip output and aeps a unit-variance Irwin-Hall(8) variate, one Philox call, a pure
+        function of its four arguments (walker_gym_amd.pg.action_noise_numpy restates it bit for bit).  sigma: float32
+        device tensor [G, C] ([C] for a shared policy), or a number for every unit.  Beside the other entries' per-step
+        buffers: steps_out [T, N] i32 (info['steps'] after each step), action_out [T, N, C] the clipped a,
+        raw_action_out [T, N, C] u, eps_out [T, N, C] aeps.  The density put on aeps or u is the caller's business.
+        A rank that holds walkers [w0, w0 + N) of a larger population passes walker_base = w0; a rollout split into
+        several calls passes the steps already taken as step_base.
+
+        Returns rollout_policy's dict with auto-reset off and rollout_episodes' dict with it on; the same ValueErrors as
+        those two (nothing launched; batches the resident kernel does not take are refused, there is no stochastic
+        policy_loop), and for a sigma that does not fit, a seed outside uint64, episode_slots / reset_out /
+        final_obs_out with auto-reset off, step_base + n_steps or walker_base + N past 2^32."""
+        N, dv = self.N, self.device
+        entry = "rollout_stochastic"
+        ar = bool(self._ar_mode)
+        slots = int(episode_slots)
+        if not ar and (slots != 0 or reset_out is not None or final_obs_out is not None):
+            raise ValueError(f"{entry}: episode_slots / reset_out / final_obs_out need auto-reset (enable_auto_reset)")
+        pol, o, T = self._resident_policy(entry, ar, policy, n_steps, slots if ar else None, obs_out, reward_out,
+                                          done_out, action_out, reset_out, final_obs_out)
+        G, Cc = policy.G, policy.C
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"{entry}: seed is a uint64")
+        if not (0 <= int(step_base) and int(step_base) + T <= 1 << 32):
+            raise ValueError(f"{entry}: step_base {step_base} + n_steps {T} outside 0 .. 2^32")
+        if not (0 <= int(walker_base) and int(walker_base) + N <= 1 << 32):
+            raise ValueError(f"{entry}: walker_base {walker_base} + N {N} outside 0 .. 2^32")
+        if sigma is None:
+            raise ValueError(f"{entry}: sigma is required (a [G, C] float32 device tensor, or a number)")
+        if not isinstance(sigma, torch.Tensor):
+            sigma = torch.full((G, Cc), float(sigma), dtype=torch.float32, device=dv)
+        elif sigma.dim() == 1 and G == 1:
+            sigma = sigma[None]
+        require_tensor(sigma, "sigma", dv, torch.float32, (G, Cc))
+        for name, t, dt, shape in (("steps_out", steps_out, torch.int32, (T, N)),
+                                   ("raw_action_out", raw_action_out, torch.float32, (T, N, Cc)),
+                                   ("eps_out", eps_out, torch.float32, (T, N, Cc))):
+            if t is not None:
+                require_tensor(t, name, dv, dt, shape)
+        p = _lib.ptr
+        o.steps = p(steps_out)
+        nz = _lib.WgActionNoise(seed=int(seed), step_base=int(step_base), walker_base=int(walker_base), sigma=p(sigma),
+                                raw_out=p(raw_action_out), raw_out_step=N * Cc, eps_out=p(eps_out), eps_out_step=N * Cc)
+        if ar:
+            res = {"return_sum": torch.empty(N, dtype=torch.float32, device=dv),
+                   "length_sum": torch.empty(N, dtype=torch.int32, device=dv),
+                   "episodes": torch.empty(N, dtype=torch.int32, device=dv),
+                   "tail_return": torch.empty(N, dtype=torch.float32, device=dv),
+                   "tail_length": torch.empty(N, dtype=torch.int32, device=dv)}
+            if slots > 0:
+                res["ep_returns"] = torch.full((N, slots), float("nan"), dtype=torch.float32, device=dv)
+                res["ep_lengths"] = torch.full((N, slots), -1, dtype=torch.int32, device=dv)
+            st = C.byref(_lib.WgEpisodeStats(return_sum=p(res["return_sum"]), length_sum=p(res["length_sum"]),
+                                             episodes_done=p(res["episodes"]), tail_return=p(res["tail_return"]),
+                                             tail_length=p(res["tail_length"]), ep_return=p(res.get("ep_returns")),
+                                             ep_length=p(res.get("ep_lengths")), ep_slots=slots))
+        else:
+            res = {"returns": torch.empty(N, dtype=torch.float32, device=dv),
+                   "lengths": torch.empty(N, dtype=torch.int32, device=dv)}
+            pol.return_out, pol.length_out = p(res["returns"]), p(res["lengths"])
+            st = None
+        _lib.check(_lib.load().wg_rollout_stochastic(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
+                                                     C.byref(nz), C.byref(o), st, T, self._stream()),
+                   "wg_rollout_stochastic")
+        self._steps_at = -1   # (as rollout_policy(): only after the call was accepted)
+        self._stale = _ROLLOUT_STALE
+        return res
+
     def run(self, actions, n_steps: int, info: bool = True, lanes: Optional[int] = None, resident: bool = False,
             record: Optional[dict] = None, _only: Optional[int] = None):
         """Throughput path: n_steps env steps in one C call; step s acts with actions[s % T]

@@ -20,33 +20,13 @@
 
 #include "walker_hip.h"
 #include "walker_internal.h"   // wg_fail, wg_launched: the refusals here go to the library's one error message
+#include "wg_philox.h"         // wg_eps: the one definition of the noise, shared with the action noise of walker_hip.hip
 
 namespace {
 
 constexpr int ES_THREADS = 256;
 constexpr int ES_CHUNK = 256;             // pairs per float64 partial sum (the contract's chunk)
-constexpr uint32_t ES_TAG = 0x45530001u;  // counter word 3
 constexpr int64_t ES_MAX_K = (int64_t)1 << 23;   // parameters: blockIdx.y counts blocks of 256 of them (at most 65,535)
-
-// eps(seed, generation, j, k): Philox4x32-10 on the counter (k, j, generation, ES_TAG) under the key (seed lo, seed hi);
-// the eight 16-bit halves of the four output words added, centred and scaled to unit variance (Irwin-Hall(8)).
-__device__ __forceinline__ float es_eps(uint32_t k0, uint32_t k1, uint32_t generation, uint32_t j, uint32_t k) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-    uint32_t c0 = k, c1 = j, c2 = generation, c3 = ES_TAG;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(M0, c0), l0 = M0 * c0, h1 = __umulhi(M1, c2), l1 = M1 * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += W0;
-        k1 += W1;
-    }
-    const int32_t s = (int32_t)((c0 & 0xffffu) + (c0 >> 16) + (c1 & 0xffffu) + (c1 >> 16) + (c2 & 0xffffu) + (c2 >> 16) +
-                                (c3 & 0xffffu) + (c3 >> 16));
-    return __fmul_rn((float)(s - 262140), __uint_as_float(0x379CC471u));   // |s - 262140| < 2^24: the cast is exact
-}
 
 // The four segments of theta: element counts (0 for an absent one) and the candidate tensors.
 struct EsLayout {
@@ -88,7 +68,7 @@ __global__ __launch_bounds__(ES_THREADS) void es_perturb(EsLayout lay, const flo
     dst += off;
     const int32_t j = first_pair + jl;
     const float th = theta[k];
-    const float d = __fmul_rn(sigma, es_eps(k0, k1, generation, (uint32_t)j, (uint32_t)k));
+    const float d = __fmul_rn(sigma, wg_eps<WG_ES_TAG>(k0, k1, generation, (uint32_t)j, (uint32_t)k));
     float *p = dst + 2 * (int64_t)j * stride;
     p[0] = __fadd_rn(th, d);
     p[stride] = __fsub_rn(th, d);
@@ -108,7 +88,7 @@ __global__ __launch_bounds__(ES_THREADS) void es_update_partial(const float *__r
     for (int32_t jl = a; jl < b; ++jl) {
         const int64_t j = (int64_t)first_pair + jl;
         const float d = __fsub_rn(util[2 * j], util[2 * j + 1]);
-        const float e = es_eps(k0, k1, generation, (uint32_t)j, (uint32_t)k);
+        const float e = wg_eps<WG_ES_TAG>(k0, k1, generation, (uint32_t)j, (uint32_t)k);
         acc = __dadd_rn(acc, __dmul_rn((double)d, (double)e));
     }
     partial[(int64_t)c * K + k] = acc;

@@ -37,6 +37,7 @@
 #include "walker_hip.h"
 #include "powf2.h"
 #include "walker_internal.h"
+#include "wg_philox.h"
 
 static thread_local char g_err[512] = "";
 
@@ -2931,6 +2932,16 @@ struct KPolicy {
                                    // offset, behind the waves' slices; < 0: every lane reads its set's weights through L2
 };
 
+// The action noise of wg_rollout_stochastic (wg_action_noise): the NZ instances of walker_rollout_policy take it as a
+// trailing kernel argument of their own (the other instances take the empty KNoReset, as with KReset).
+struct KNoise {
+    const float *sigma;            // [n_sets][C]
+    float *raw_out, *eps_out;      // optional [n_steps][N][C]: u before the clip, aeps
+    int64_t raw_out_step, eps_out_step;
+    uint32_t k0, k1;               // the Philox key: seed lo, seed hi
+    uint32_t step_base, walker_base;
+};
+
 // One unit of a layer, the contract's chain: acc = bias; acc = RN32(acc + RN32(x[i] * w[i][j])) for i ascending, the
 // multiply and the add separate roundings (no FMA).  x: the walker's input vector in LDS (the same address in every lane
 // of the walker: a broadcast); w: column j of the set's [n][stride] matrix.
@@ -2988,10 +2999,14 @@ __device__ __forceinline__ void policy_unit2(const float *x, const float *__rest
 // policy reads are the rows the step stores, by construction), then the walker's M lanes share the units of each layer,
 // lane q taking units q, q + M, ...; the hidden vector and the actions go through LDS.  Returns the muscle lane's action
 // (0 where the lane does not act).  act_dst: this step's action_out rows, or NULL.  WS: the LDS words of a walker's record.
-template <bool IN3D, int WS = 4>
+// NZ = KNoise (wg_rollout_stochastic): the lane that owns output unit j adds RN32(sigma[set][j] * aeps(seed, step_base + s,
+// walker_base + w, j)) to the unit's chain value before the clip, its own Philox call, and stores the raw action and the
+// variate beside act_dst; s is the call's step.  NZ = KNoReset: none of that is compiled.
+template <bool IN3D, int WS = 4, class NZ = KNoReset>
 __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &kp, const KPolicy &pol, const LeanGeo &lg,
                                              char *smem, char *sl, const LeanTile &t, const float *p3, const float *v3,
-                                             const LeanPolOut &ps, float x, float *act_dst) {
+                                             const LeanPolOut &ps, float x, float *act_dst, const NZ &nz = NZ{},
+                                             int s = 0) {
     const int M = b.M, D = pol.D, H = pol.H, C = pol.C;
     float *row = reinterpret_cast<float *>(sl + pol.off_row);
     float *hid = reinterpret_cast<float *>(sl + pol.off_h);
@@ -3035,7 +3050,16 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
                                 ? policy_unit(xin, reinterpret_cast<const float *>(smem + pol.off_wts) + D * H + j, n, C,
                                               bias)
                                 : policy_unit(xin, pol.w2 + (size_t)gset * (size_t)n * (size_t)C + j, n, C, bias);
-            const float a = (y < -lim) ? -lim : ((y > lim) ? lim : y);   // (a NaN passes through)
+            float u = y;
+            if constexpr (std::is_same<NZ, KNoise>::value) {
+                const uint32_t wg = (uint32_t)(t.w0 + t.wl);
+                const float e = wg_eps<WG_ACT_TAG>(nz.k0, nz.k1, nz.step_base + (uint32_t)s, nz.walker_base + wg, (uint32_t)j);
+                u = __fadd_rn(y, __fmul_rn(nz.sigma[(size_t)gset * (size_t)C + j], e));
+                const size_t at = (size_t)wg * (size_t)C + j;   // (64-bit offsets; plain vector stores)
+                if (nz.raw_out) nz.raw_out[(size_t)s * (size_t)nz.raw_out_step + at] = u;
+                if (nz.eps_out) nz.eps_out[(size_t)s * (size_t)nz.eps_out_step + at] = e;
+            }
+            const float a = (u < -lim) ? -lim : ((u > lim) ? lim : u);   // (a NaN passes through)
             act[t.wl * C + j] = a;
             if (act_dst) act_dst[(size_t)(uint32_t)(t.w0 + t.wl) * (size_t)C + j] = a;
         }
@@ -3054,13 +3078,16 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
 // the running episode's return and length, the episodes finished in this call, the parameter set, the finished
 // episodes' return and length sums, the walker's episode count (wg_batch.episodes), one spare.  Lane q == 0 keeps the
 // accounting of wg_episode_stats, stores an ep_return / ep_length slot when an episode ends, the sums after the last step.
-template <bool IN3D, int NE, bool E8, bool AR = false>
+// NZ (wg_rollout_stochastic): seeded action noise in the policy's output layer (lean_policy), in either mode; dead code in
+// the NZ = false instances, whose trailing argument is the empty KNoReset.
+template <bool IN3D, int NE, bool E8, bool AR = false, bool NZ = false>
 // (register budget: one wave per SIMD fewer than walker_rollout_lean.  The LDS slice with the rows already holds the
 // canonical walker to 4 waves per SIMD, the NE 8 shapes to 2, and the latency-bound NE 1 batches run one)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3 : 4))) void walker_rollout_policy(
     wg_batch b, KParams kp, KPolicy pol, KOut o, int n_steps, LeanGeo lg,
     typename std::conditional<AR, KReset, KNoReset>::type ar,
-    typename std::conditional<AR, wg_episode_stats, KNoReset>::type st) {
+    typename std::conditional<AR, wg_episode_stats, KNoReset>::type st,
+    typename std::conditional<NZ, KNoise, KNoReset>::type nz) {
     constexpr int WS = AR ? 8 : 4;   // LDS words per walker
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -3122,8 +3149,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
         asm volatile("" : "+v"(ln));
         LeanTile ts = lean_tile_of(b, nullptr, pol.C, lg, tile, ln);
         ts.acts = ts.is_mus && ts.mu_ua < pol.C;
-        L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x,
-                                    pol.action_out ? pol.action_out + (size_t)s * (size_t)pol.action_out_step : nullptr);
+        float *const act_dst = pol.action_out ? pol.action_out + (size_t)s * (size_t)pol.action_out_step : nullptr;
+        if constexpr (NZ) L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst, nz, s);
+        else L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst);
         WG_KOUT_AT(os, o, s);
         WG_PIN_STATIC(L, NE, E8)
         if constexpr (AR)
@@ -3607,6 +3635,11 @@ int wg_rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *po
 int wg_rollout_episodes(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o,
                         const wg_episode_stats *st, int32_t n_steps, hipStream_t stream) {
     return rollout_policy(b, p, pol, o, n_steps, stream, true, st);
+}
+
+int wg_rollout_stochastic(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_action_noise *nz,
+                          const wg_outputs *o, const wg_episode_stats *st, int32_t n_steps, hipStream_t stream) {
+    return rollout_policy(b, p, pol, o, n_steps, stream, p && p->auto_reset != 0, st, true, nz);
 }
 
 int wg_run_ranges(const wg_range *ranges, int32_t n, const wg_params *p, const float *action, int32_t action_cols,

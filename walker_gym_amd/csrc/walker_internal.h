@@ -1,4 +1,4 @@
-// walker_internal.h — what libwalker_hip.so's translation units (walker_hip.hip, es_hip.hip) share and do not export.
+// walker_internal.h — what libwalker_hip.so's translation units (walker_hip.hip, es_hip.hip, pg_hip.hip) share and do not export.
 #pragma once
 
 #include <hip/hip_runtime.h>

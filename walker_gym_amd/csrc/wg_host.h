@@ -386,12 +386,16 @@ int obs_row_len(const wg_batch *b, const wg_params *p) {
 // kernel's plus the walkers' observation rows, hidden vectors and actions.
 // episodes (wg_rollout_episodes): the AR instances, with auto-reset's own checks in place of the auto_reset refusal, the
 // accounting of `st`, and eight words per walker in the slice instead of four.
+// stochastic (wg_rollout_stochastic): either mode, chosen by p->auto_reset, with the NZ instances and the checks of `nz`.
 int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o, int32_t n_steps,
-                   hipStream_t stream, bool episodes = false, const wg_episode_stats *st = nullptr) {
-    const char *fn = episodes ? "wg_rollout_episodes" : "wg_rollout_policy";
+                   hipStream_t stream, bool episodes = false, const wg_episode_stats *st = nullptr,
+                   bool stochastic = false, const wg_action_noise *nz = nullptr) {
+    const char *fn = stochastic ? "wg_rollout_stochastic" : episodes ? "wg_rollout_episodes" : "wg_rollout_policy";
     int rc = validate(b);
     if (rc) return rc;
     if (!p) return wg_fail(WG_EINVAL, "null params");
+    if (stochastic && !episodes && st)
+        return wg_fail(WG_EINVAL, "%s: episode stats with auto_reset 0 (st must be NULL without episode roll-over)", fn);
     if (!pol) return wg_fail(WG_EINVAL, "%s: null policy", fn);
     if (!pol->w2) return wg_fail(WG_EINVAL, "%s: null w2", fn);
     if (n_steps < 1) return wg_fail(WG_EINVAL, "%s: n_steps %d < 1", fn, n_steps);
@@ -419,6 +423,22 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
         if (pol->return_out || pol->length_out)
             return wg_fail(WG_EINVAL, "%s: return_out / length_out are defined by the first done (wg_rollout_policy); "
                                    "the episode stats replace them", fn);
+    }
+    if (stochastic) {
+        if (!nz) return wg_fail(WG_EINVAL, "%s: null action noise", fn);
+        if (!nz->sigma) return wg_fail(WG_EINVAL, "%s: null sigma", fn);
+        const int64_t row = (int64_t)b->N * pol->act_dim;
+        if (nz->raw_out && nz->raw_out_step < row)
+            return wg_fail(WG_EINVAL, "%s: raw_out_step %lld < N * act_dim = %lld", fn, (long long)nz->raw_out_step,
+                           (long long)row);
+        if (nz->eps_out && nz->eps_out_step < row)
+            return wg_fail(WG_EINVAL, "%s: eps_out_step %lld < N * act_dim = %lld", fn, (long long)nz->eps_out_step,
+                           (long long)row);
+        // the counters are 32-bit words: no step or walker of the call may wrap
+        if ((uint64_t)nz->step_base + (uint64_t)n_steps > (1ull << 32))
+            return wg_fail(WG_EINVAL, "%s: step_base %u + n_steps %d passes 2^32", fn, nz->step_base, n_steps);
+        if ((uint64_t)nz->walker_base + (uint64_t)b->N > (1ull << 32))
+            return wg_fail(WG_EINVAL, "%s: walker_base %u + N %d passes 2^32", fn, nz->walker_base, b->N);
     }
     if ((rc = check_integrator(p)) || (rc = check_muscle_bounds(b)) || (rc = check_discrete(b, p))) return rc;
     wg_outputs out = o ? *o : wg_outputs{};
@@ -467,15 +487,23 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
     }
     const dim3 grid(lg.nblk), block(64 * lg.wpb);
     const KReset ar = kreset(out, p->auto_reset);
+    KNoise kn{};
+    if (stochastic)
+        kn = KNoise{nz->sigma, nz->raw_out, nz->eps_out, nz->raw_out_step, nz->eps_out_step,
+                    (uint32_t)(nz->seed & 0xffffffffu), (uint32_t)(nz->seed >> 32), nz->step_base, nz->walker_base};
     with_instance(p->in3d != 0, ne, use_edge8(b, lg), [&](auto d3, auto n, auto c8) {
         constexpr bool D3 = decltype(d3)::value, E8 = decltype(c8)::value;
         constexpr int NE = decltype(n)::value;
-        if (episodes)
-            hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8, true>), grid, block, lds, stream, *b, kp, kpol,
-                               kout(out), n_steps, lg, ar, *st);
-        else
-            hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8>), grid, block, lds, stream, *b, kp, kpol, kout(out),
-                               n_steps, lg, KNoReset{}, KNoReset{});
+        auto go = [&](auto kernel, const auto &reset, const auto &stats, const auto &noise) {
+            hipLaunchKernelGGL(kernel, grid, block, lds, stream, *b, kp, kpol, kout(out), n_steps, lg, reset, stats, noise);
+        };
+        if (stochastic) {
+            if (episodes) go(walker_rollout_policy<D3, NE, E8, true, true>, ar, *st, kn);
+            else go(walker_rollout_policy<D3, NE, E8, false, true>, KNoReset{}, KNoReset{}, kn);
+        } else {
+            if (episodes) go(walker_rollout_policy<D3, NE, E8, true>, ar, *st, KNoReset{});
+            else go(walker_rollout_policy<D3, NE, E8>, KNoReset{}, KNoReset{}, KNoReset{});
+        }
     });
     return wg_launched("launch");
 }
