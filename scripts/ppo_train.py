@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""A short clipped-surrogate (PPO) loop on Balance-v0 over pg.collect: a torch autograd actor of the MLPPolicy shape whose
-weights are copied into the MLPPolicy that the rollout kernel evaluates, a torch critic, and a Gaussian log-density on
-the recorded variates aeps (the library reports aeps and the raw action u = y + sigma * aeps; the density on them is
-this script's choice: the variate is Irwin-Hall(8), unit variance, bounded).  Per iteration one stochastic rollout of
-`--steps` steps of every walker (one launch), the GAE kernel, `--epochs` passes of minibatch updates.  Nothing is tuned
-and nothing is asserted: the curve is recorded as it comes.
+"""A short clipped-surrogate (PPO) loop on Balance-v0 over pg.collect and pg.policy_rows: the actor is the MLPPolicy the
+rollout kernel evaluates, its tensors nn.Parameters that Adam updates in place (no second actor, no weight copy); its
+mean on the recorded rows is pg.policy_rows, the kernel's own arithmetic, so on the first pass over fresh data the
+mean is the y inside the recorded u = RN32(y + RN32(sigma * aeps)) bit for bit.  A torch critic, and a Gaussian
+log-density on u around that mean (the density is this script's choice: the variate is Irwin-Hall(8), unit variance,
+bounded).  Per iteration one stochastic rollout of `--steps` steps of every walker (one launch), the GAE kernel,
+`--epochs` passes of minibatch updates, a minibatch being a row mask over the [T, N] batch.  Nothing is tuned and
+nothing is asserted: the curve is recorded as it comes.
 
     python scripts/ppo_train.py [--walkers 1024] [--hidden 32] [--iterations 20] [--steps 64] [--epochs 4]
-                                [--sigma 0.3] [--lr 3e-4] [--seed 0] [--out profiles/r11_ppo_balance_curve.json]
+                                [--sigma 0.3] [--lr 3e-4] [--seed 0] [--out profiles/r12_ppo_balance_curve.json]
 """
 import argparse
 import json
@@ -47,44 +49,51 @@ def main():
     env = BatchedPhysicsEnv(balance_spec(a.walkers), in3d=0, max_steps=a.max_steps, rand_sigma=0.01, seed=a.seed)
     env.enable_auto_reset(on=("done", "nonfinite"), noise_rows=8, final_obs=True)   # a diverged walker starts over
     dev, N, D, A, H = env.device, env.N, env.obs_dim, env.batch.A, a.hidden
-    # the actor: MLPPolicy's shape (y = relu(x @ w1 + b1) @ w2 + b2), its parameters the autograd leaves
+    # the actor: the MLPPolicy itself, its tensors the autograd leaves (kept by identity: Adam's in-place steps are what
+    # the next rollout reads)
     p = lambda *s, k=1.0: torch.nn.Parameter(torch.randn(s, device=dev) * k)
-    w1, b1 = p(D, H, k=0.002), torch.nn.Parameter(torch.zeros(H, device=dev))
-    w2, b2 = p(H, A, k=0.01), torch.nn.Parameter(torch.zeros(A, device=dev))
+    w1, b1 = p(1, D, H, k=0.002), torch.nn.Parameter(torch.zeros(1, H, device=dev))
+    w2, b2 = p(1, H, A, k=0.01), torch.nn.Parameter(torch.zeros(1, A, device=dev))
+    pol = MLPPolicy(w2, b2, w1, b1)
+    assert pol.w1 is w1 and pol.w2 is w2
     log_sigma = torch.nn.Parameter(torch.full((A,), math.log(a.sigma), device=dev))
     critic = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to(dev)
     opt = torch.optim.Adam([w1, b1, w2, b2, log_sigma, *critic.parameters()], lr=a.lr)
     obs_scale = 1e-2   # the rows hold accelerations in the thousands: the critic sees them scaled
     value_fn = lambda rows: critic((rows * obs_scale).clamp(-10.0, 10.0)).squeeze(-1)
-    mean_of = lambda rows: torch.relu(rows @ w1 + b1) @ w2 + b2
 
-    def log_prob(rows, u):   # Gaussian density of u around the actor's mean: eps = (u - y) / sigma
-        sg = log_sigma.exp()
-        z = (u - mean_of(rows)) / sg
+    def log_prob(mean, u):   # Gaussian density of u around the policy's mean
+        z = (u - mean) / log_sigma.exp()
         return (-0.5 * z * z - log_sigma - 0.5 * math.log(2 * math.pi)).sum(-1)
 
     curve, t0 = [], time.perf_counter()
     for it in range(a.iterations):
-        with torch.no_grad():   # this iteration's weights into the policy the kernel evaluates
-            pol = MLPPolicy(w2.detach().clone(), b2.detach().clone(), w1.detach().clone(), b1.detach().clone())
-            sigma = log_sigma.exp().detach().reshape(1, A).contiguous()
+        sigma = log_sigma.exp().detach().reshape(1, A).contiguous()
         batch = pg.collect(env, pol, sigma, a.steps, a.seed, it * a.steps, value_fn, a.gamma, a.lam)
-        rows = batch["obs_before"].reshape(-1, D)
-        u = batch["raw_action"].reshape(-1, A)
-        adv, ret = batch["adv"].reshape(-1), batch["ret"].reshape(-1)
-        ok = torch.isfinite(adv) & torch.isfinite(ret) & torch.isfinite(rows).all(1) & torch.isfinite(u).all(1)
-        adv_n = (adv - adv[ok].mean()) / (adv[ok].std() + 1e-8)
-        with torch.no_grad():
-            eps = batch["eps"].reshape(-1, A)   # the recorded variate is the old policy's z, exactly
-            old_lp = (-0.5 * eps * eps - log_sigma - 0.5 * math.log(2 * math.pi)).sum(-1)
-        idx_all = torch.nonzero(ok).squeeze(1)
+        obs, u = batch["obs_before"], batch["raw_action"]          # [T, N, D], [T, N, A]
+        adv, ret = batch["adv"], batch["ret"]
+        ok = torch.isfinite(adv) & torch.isfinite(ret) & torch.isfinite(obs).all(-1) & torch.isfinite(u).all(-1)
+        adv_n = torch.where(ok, (adv - adv[ok].mean()) / (adv[ok].std() + 1e-8), torch.zeros_like(adv))
+        ret_0 = torch.where(ok, ret, torch.zeros_like(ret))
+        with torch.no_grad():   # the old policy's density: the same function on the same rows, before any update
+            old_lp = log_prob(pg.policy_rows(pol, obs, ok), u)
+            first_ratio_dev = None
+        T = obs.shape[0]
         for _ in range(a.epochs):
-            perm = idx_all[torch.randperm(idx_all.numel(), device=dev)]
-            for mb in perm.chunk(a.minibatches):
-                ratio = (log_prob(rows[mb], u[mb]) - old_lp[mb]).exp()
-                surr = torch.minimum(ratio * adv_n[mb], ratio.clamp(1 - a.clip, 1 + a.clip) * adv_n[mb])
-                v_loss = (value_fn(rows[mb]) - ret[mb]).pow(2).mean()
-                loss = -surr.mean() + 0.5 * v_loss
+            part = torch.randint(a.minibatches, (T, N), device=dev)
+            for m in range(a.minibatches):
+                mask = ok & (part == m)           # the minibatch: a row mask (skipped rows are neither read nor summed)
+                cnt = mask.sum().clamp(min=1)
+                mean = pg.policy_rows(pol, obs, mask)
+                lp = torch.where(mask, log_prob(mean, torch.where(mask[..., None], u, torch.zeros_like(u))), old_lp)
+                ratio = (lp - old_lp).exp()
+                if first_ratio_dev is None:       # exactly 0: the trained function is the function the kernel ran
+                    first_ratio_dev = float((ratio.detach()[mask] - 1).abs().max())
+                surr = torch.minimum(ratio * adv_n, ratio.clamp(1 - a.clip, 1 + a.clip) * adv_n)
+                v_err = torch.where(mask, value_fn(torch.where(mask[..., None], obs, torch.zeros_like(obs))) - ret_0,
+                                    torch.zeros_like(ret))
+                v_loss = v_err.pow(2).sum() / cnt
+                loss = -(surr * mask).sum() / cnt + 0.5 * v_loss
                 opt.zero_grad(set_to_none=True)
                 loss.backward()
                 torch.nn.utils.clip_grad_norm_([w1, b1, w2, b2, log_sigma, *critic.parameters()], 0.5)
@@ -96,6 +105,7 @@ def main():
                       "mean_episode_length": float(batch["length_sum"].double().sum() / n_ep),
                       "value_loss": float(v_loss.detach()), "sigma": [float(s) for s in log_sigma.exp()],
                       "clipped_action_fraction": float((batch["raw_action"].abs() > 1).float().mean()),
+                      "first_pass_max_ratio_minus_1": first_ratio_dev,
                       "samples_dropped_nonfinite": int((~ok).sum())})
         print(json.dumps(curve[-1]), flush=True)
     torch.cuda.synchronize()

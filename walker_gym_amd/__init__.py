@@ -10,7 +10,8 @@ include/walker_hip.h, HIP kernels for gfx950).  Drop-in facades of the reference
 Training on the device: walker_gym_amd.policy.MLPPolicy (evaluated inside the rollout kernels) and
 walker_gym_amd.es.EvolutionStrategy (seeded perturb / update kernels, wg_es_* in the header);
 BatchedPhysicsEnv.rollout_stochastic and walker_gym_amd.pg (seeded action noise in the rollout kernel, the GAE kernel,
-collect() for PPO: wg_rollout_stochastic / wg_gae).
+collect() for PPO: wg_rollout_stochastic / wg_gae; policy_rows(), the MLPPolicy over recorded rows as a
+torch.autograd.Function: wg_policy_forward / wg_policy_backward).
 Importing the package needs no GPU; stepping does (no CPU fallback).
 """
 from .engine import Config, DingPoint, Point, to_data  # noqa: F401
@@ -34,6 +35,9 @@ def __getattr__(name):
     if name == "pg":   # policy-gradient support: the noise and GAE restatements, gae(), collect()
         import importlib
         return importlib.import_module(".pg", __name__)
+    if name == "policy_rows":   # pg.policy_rows(policy, obs, mask=None, chunk_rows=None): differentiable in-kernel policy
+        import importlib
+        return importlib.import_module(".pg", __name__).policy_rows
     if name == "rollout_stochastic":   # BatchedPhysicsEnv.rollout_stochastic(env, policy, n_steps, sigma, seed, ...)
         from . import batched_env
         return batched_env.BatchedPhysicsEnv.rollout_stochastic

@@ -92,11 +92,19 @@ class WgActionNoise(C.Structure):
                 ("raw_out", _vp), ("raw_out_step", C.c_int64), ("eps_out", _vp), ("eps_out_step", C.c_int64)]
 
 
+class WgPolicyRows(C.Structure):
+    """wg_policy_rows: the recorded observation rows of wg_policy_forward / wg_policy_backward."""
+    _fields_ = [("x", _vp), ("x_step", C.c_int64), ("mask", _vp), ("mask_step", C.c_int64), ("n_steps", C.c_int32),
+                ("N", C.c_int32)]
+
+
+POLICY_GRAD_MAX_K = 16384   # WG_POLICY_GRAD_MAX_K
+
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
            "wg_step_simple", "wg_observe_simple", "wg_reset", "wg_reset_noise", "wg_plan_ragged", "wg_plan_waves",
            "wg_wave_edge_passes", "wg_plan_errors", "wg_launch_geometry", "wg_launch_floor", "wg_time_step",
            "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches", "wg_es_perturb", "wg_es_update",
-           "wg_rollout_stochastic", "wg_gae")
+           "wg_rollout_stochastic", "wg_gae", "wg_policy_forward", "wg_policy_backward_workspace", "wg_policy_backward")
 
 _lib = None
 _lock = threading.Lock()
@@ -132,6 +140,10 @@ def load(path: str | None = None):
                                             C.c_int32, _vp]
         L.wg_gae.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_float, _vp, _vp,
                              _vp]
+        L.wg_policy_forward.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgPolicyRows), _vp, C.c_int64, _vp]
+        L.wg_policy_backward_workspace.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgPolicyRows), C.c_int32]
+        L.wg_policy_backward.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgPolicyRows), _vp, C.c_int64, C.c_int32, _vp,
+                                         _vp, _vp, _vp, _vp, _vp]
         L.wg_es_perturb.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp]
         L.wg_es_update.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp, C.c_double, C.c_float, _vp, _vp, _vp, _vp]
         L.wg_step_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,
@@ -154,6 +166,7 @@ def load(path: str | None = None):
         for f in EXPORTS[2:]:
             getattr(L, f).restype = C.c_int
         L.wg_fix_launches.restype = C.c_longlong
+        L.wg_policy_backward_workspace.restype = C.c_int64
         v = L.wg_abi_version()
         if v != ABI_VERSION:
             raise WalkerHipError(f"{p}: ABI version {v}, expected {ABI_VERSION}")

@@ -9,9 +9,24 @@
 //              already in registers: with vmcnt counting in order the chain waits for its own block only, and 5 * GAE_U
 //              loads per lane stay in flight behind it.  Six dependent float32 operations per step, no FMA
 //              (-ffp-contract=off, and the intrinsics round once each).  Every element offset is 64-bit.
+//
+// and wg_policy_forward / wg_policy_backward: wg_policy's layers over recorded observation rows, and their gradient.
+//
+//   pr_forward       a workgroup takes tiles of up to 64 rows: the rows are copied to LDS once (coalesced; skipped rows
+//                    are neither loaded nor stored), then one thread per (row, unit) runs the unit's chain, pr_chain,
+//                    the one definition of the arithmetic here (x rows padded to an odd length: no bank conflicts).  A shared policy's weights (n_sets == 1) are staged in
+//                    LDS when they fit PR_W_LDS bytes; otherwise they are read through L2.
+//   pr_grad_partial  a workgroup owns one (set, chunk) and walks its rows in order, PR_BWD_ROWS at a time: x, dy in LDS,
+//                    h recomputed by pr_chain, dh beside it.  The two outer products (x|1) (x) dh and (in|1) (x) dy (the
+//                    appended 1 makes each bias one more row) are cut into 4 x 4 register blocks of float64
+//                    accumulators, NT blocks per thread: a row costs a thread two 16-byte LDS reads per 16 fma.
+//                    RN64(P + a * b) with an exact product is one float64 fma.  Blocks past the shapes compute on
+//                    zero padding and are dropped.
+//   pr_grad_tail     S = the chunks' partials added in order, g = RN32(S), one thread per element.
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdint>
 
@@ -77,15 +92,364 @@ __global__ __launch_bounds__(GAE_THREADS) void gae_scan(const float *__restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------------ policy rows
+constexpr int PR_THREADS = 256;
+constexpr int PR_LDS = 64 * 1024;    // dynamic LDS of a workgroup, at most
+constexpr int PR_W_LDS = 32 * 1024;  // forward: a shared policy's weights are staged in LDS up to this size
+constexpr int PR_FWD_ROWS = 64;      // rows per tile, at most
+constexpr int PR_BWD_ROWS = 16;
+constexpr int PR_MAX_NT = 4;         // 4 x 4 blocks per thread: WG_POLICY_GRAD_MAX_K / (16 * PR_THREADS)
+static_assert(PR_MAX_NT * 16 * PR_THREADS == WG_POLICY_GRAD_MAX_K, "the header's limit is what the registers hold");
+
+inline int up4(int v) { return (v + 3) & ~3; }
+
+struct PrArgs {
+    const float *x;
+    const uint8_t *mask;
+    const float *w1, *b1, *w2, *b2;
+    int64_t x_step, mask_step;
+    int32_t n_steps, N, n;          // n = N / n_sets walkers per set
+    int32_t D, H, C, n2;            // n2 = H ? H : D inputs of the output layer
+    int32_t Dp, Hq, Hp, Cp;         // LDS row lengths: up4(D + 1), up4(H + 1), up4(H), up4(C) (the forward: D | 1, H | 1)
+    int32_t TR;                     // rows per tile
+};
+
+// The unit's chain, acc = RN32(acc + RN32(in[i] * w[i * stride + off])) for i ascending, of NU units side by side:
+// every unit's own operations are the contract's, in its order; NU independent chains share the loads of in[i].
+// PR_NU = 4 was measured: the forward gained under 10 %, the backward's recompute lost a wave per SIMD to the extra
+// registers and doubled its time at H = 32; one unit per thread it is.
+constexpr int PR_NU = 1;
+template <int NU>
+__device__ __forceinline__ void pr_chain(float (&acc)[NU], const float *in, const float *w, int n, int stride,
+                                         const int (&off)[NU]) {
+#pragma unroll 4
+    for (int i = 0; i < n; i++) {
+        const float v = in[i];
+        const float *wi = w + (int64_t)i * stride;
+#pragma unroll
+        for (int k = 0; k < NU; k++) acc[k] = __fadd_rn(acc[k], __fmul_rn(v, wi[off[k]]));
+    }
+}
+
+// Rows rho0 .. rho0 + TR of a sequence numbered rho = t * n_seq + (w - w_base), those below rho_end: row r's (t, w) to
+// rt / rw, whether it is evaluated to ok, its x (then 1.0f, then zeros up to Dp) to xs, and, with dy, its dy row (zeros
+// up to Cp) to dys.  A wave per row, lanes along the row.
+__device__ __forceinline__ void pr_stage(const PrArgs &a, int64_t rho0, int64_t rho_end, int n_seq, int w_base,
+                                         const float *__restrict__ dy, int64_t dy_step, float *xs, float *dys, int *ok,
+                                         int *rt, int *rw) {
+    const int lane = threadIdx.x & 63;
+    for (int r = threadIdx.x >> 6; r < a.TR; r += PR_THREADS / 64) {
+        const int64_t rho = rho0 + r;
+        const bool in = rho < rho_end;
+        const int t = in ? (int)(rho / n_seq) : 0, w = in ? w_base + (int)(rho % n_seq) : 0;
+        const bool on = in && (!a.mask || a.mask[(int64_t)t * a.mask_step + w] != 0);
+        if (lane == 0) {
+            ok[r] = on;
+            rt[r] = t;
+            rw[r] = w;
+        }
+        if (!on) continue;
+        const float *xr = a.x + (int64_t)t * a.x_step + (int64_t)w * a.D;
+        for (int i = lane; i < a.Dp; i += 64) xs[r * a.Dp + i] = i < a.D ? xr[i] : (i == a.D ? 1.0f : 0.0f);
+        if (dy) {
+            const float *dr = dy + (int64_t)t * dy_step + (int64_t)w * a.C;
+            for (int c = lane; c < a.Cp; c += 64) dys[r * a.Cp + c] = c < a.C ? dr[c] : 0.0f;
+        }
+    }
+}
+
+// The hidden layer of the tile's rows: a thread takes a row and the PR_NU units j, j + JS, ... (JS = ceil(H / PR_NU):
+// the lanes of a wave read consecutive weights; a unit past H repeats unit H - 1 and is dropped).  h to hs and, with DH,
+// dh to dhs:
+//   d = +0.0f; for c ascending: d = RN32(d + RN32(dy[c] * w2[j][c]));  dh[j] = (z[j] > 0) ? d : +0.0f   (h > 0 iff z > 0)
+// lw1 / lb1: the set's weights in LDS (WLDS) -- otherwise each row's set is read through L2.
+template <bool WLDS, bool DH>
+__device__ __forceinline__ void pr_hidden(const PrArgs &a, const float *xs, const float *dys, const int *ok, const int *rw,
+                                          const float *lw1, const float *lb1, float *hs, float *dhs) {
+    const int JS = (a.H + PR_NU - 1) / PR_NU;
+    for (int item = threadIdx.x; item < a.TR * JS; item += PR_THREADS) {
+        const int r = item / JS, j = item - r * JS;
+        if (!ok[r]) continue;
+        const int64_t g = rw[r] / a.n;
+        const float *w1 = WLDS ? lw1 : a.w1 + g * a.D * a.H;
+        const float *b1 = WLDS ? lb1 : (a.b1 ? a.b1 + g * a.H : nullptr);
+        int u[PR_NU];
+        float z[PR_NU];
+#pragma unroll
+        for (int k = 0; k < PR_NU; k++) {
+            u[k] = j + k * JS < a.H ? j + k * JS : a.H - 1;
+            z[k] = b1 ? b1[u[k]] : 0.0f;
+        }
+        pr_chain<PR_NU>(z, xs + r * a.Dp, w1, a.D, a.H, u);
+#pragma unroll
+        for (int k = 0; k < PR_NU; k++) {
+            if (j + k * JS >= a.H) continue;
+            const float h = z[k] > 0.0f ? z[k] : 0.0f;
+            hs[r * a.Hq + u[k]] = h;
+            if (DH) {
+                float d[1] = {0.0f};
+                const int at[1] = {0};
+                pr_chain<1>(d, dys + r * a.Cp, a.w2 + (g * a.H + u[k]) * a.C, a.C, 1, at);
+                dhs[r * a.Hp + u[k]] = h > 0.0f ? d[0] : 0.0f;
+            }
+        }
+    }
+}
+
+// LDS, in floats: [the weights (WLDS)] xs[TR][Dp] hs[TR][Hq] ok[TR] rt[TR] rw[TR]
+template <bool WLDS>
+__global__ __launch_bounds__(PR_THREADS) void pr_forward(PrArgs a, int64_t n_tiles, int w_floats, float *__restrict__ y,
+                                                         int64_t y_step) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *lw1 = lds, *lb1 = lw1 + a.D * a.H, *lw2 = lb1 + (a.b1 ? a.H : 0), *lb2 = lw2 + a.n2 * a.C;
+    float *xs = lds + w_floats, *hs = xs + a.TR * a.Dp;
+    int *ok = reinterpret_cast<int *>(hs + (a.H ? a.TR * a.Hq : 0)), *rt = ok + a.TR, *rw = rt + a.TR;
+    if (WLDS) {
+        for (int i = threadIdx.x; i < a.D * a.H; i += PR_THREADS) lw1[i] = a.w1[i];
+        for (int i = threadIdx.x; i < a.H && a.b1; i += PR_THREADS) lb1[i] = a.b1[i];
+        for (int i = threadIdx.x; i < a.n2 * a.C; i += PR_THREADS) lw2[i] = a.w2[i];
+        for (int i = threadIdx.x; i < a.C && a.b2; i += PR_THREADS) lb2[i] = a.b2[i];
+    }
+    const int64_t rows = (int64_t)a.n_steps * a.N;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        pr_stage(a, tile * a.TR, rows, a.N, 0, nullptr, 0, xs, nullptr, ok, rt, rw);
+        __syncthreads();
+        if (a.H) {
+            pr_hidden<WLDS, false>(a, xs, nullptr, ok, rw, lw1, a.b1 ? lb1 : nullptr, hs, nullptr);
+            __syncthreads();
+        }
+        const int JS = (a.C + PR_NU - 1) / PR_NU;      // the output units likewise: c, c + JS, ...
+        for (int item = threadIdx.x; item < a.TR * JS; item += PR_THREADS) {
+            const int r = item / JS, c = item - r * JS;
+            if (!ok[r]) continue;
+            const int64_t g = rw[r] / a.n;
+            const float *w2 = WLDS ? lw2 : a.w2 + g * a.n2 * a.C;
+            const float *b2 = WLDS ? (a.b2 ? lb2 : nullptr) : (a.b2 ? a.b2 + g * a.C : nullptr);
+            int u[PR_NU];
+            float acc[PR_NU];
+#pragma unroll
+            for (int k = 0; k < PR_NU; k++) {
+                u[k] = c + k * JS < a.C ? c + k * JS : a.C - 1;
+                acc[k] = b2 ? b2[u[k]] : 0.0f;
+            }
+            pr_chain<PR_NU>(acc, a.H ? hs + r * a.Hq : xs + r * a.Dp, w2, a.n2, a.C, u);
+            float *yr = y + (int64_t)rt[r] * y_step + (int64_t)rw[r] * a.C;
+#pragma unroll
+            for (int k = 0; k < PR_NU; k++)
+                if (c + k * JS < a.C) yr[u[k]] = acc[k];
+        }
+        __syncthreads();
+    }
+}
+
+// LDS, in floats: xs[TR][Dp] hs[TR][Hq] dhs[TR][Hp] dys[TR][Cp] ok[TR] rt[TR] rw[TR]
+// Block q of the workgroup's list: q < T1 the layer-1 product (x|1) (x) dh, rows 4 * (q / JT1) .., columns 4 * (q % JT1)
+// ..; then the T2 blocks of (in|1) (x) dy; thread tid owns blocks tid, tid + 256, ...
+template <int NT>
+__global__ __launch_bounds__(PR_THREADS) void pr_grad_partial(PrArgs a, const float *__restrict__ dy, int64_t dy_step,
+                                                              int32_t chunk_rows, int64_t n_chunks, int32_t T1,
+                                                              double *__restrict__ ws, int32_t K) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *xs = lds, *hs = xs + a.TR * a.Dp, *dhs = hs + (a.H ? a.TR * a.Hq : 0), *dys = dhs + (a.H ? a.TR * a.Hp : 0);
+    int *ok = reinterpret_cast<int *>(dys + a.TR * a.Cp), *rt = ok + a.TR, *rw = rt + a.TR;
+    const int g = (int)(blockIdx.x / n_chunks);
+    const int64_t k = blockIdx.x - (int64_t)g * n_chunks;
+    const int64_t lo = k * chunk_rows, set_rows = (int64_t)a.n_steps * a.n;
+    const int64_t hi = set_rows - lo < chunk_rows ? set_rows : lo + chunk_rows;
+
+    // the padding that no tile rewrites: hs[r][H] = 1 (the bias row), zeros behind it and behind dh
+    if (a.H)
+        for (int r = threadIdx.x; r < a.TR; r += PR_THREADS) {
+            for (int j = a.H; j < a.Hq; j++) hs[r * a.Hq + j] = j == a.H ? 1.0f : 0.0f;
+            for (int j = a.H; j < a.Hp; j++) dhs[r * a.Hp + j] = 0.0f;
+        }
+
+    const float *in2 = a.H ? hs : xs;
+    const int s_in2 = a.H ? a.Hq : a.Dp, JT1 = a.Hp >> 2, JT2 = a.Cp >> 2, T2 = (s_in2 >> 2) * JT2;
+    const float *pa[NT], *pb[NT];
+    int sa[NT], sb[NT];
+#pragma unroll
+    for (int u = 0; u < NT; u++) {
+        const int q = (int)threadIdx.x + u * PR_THREADS;
+        if (q < T1) {
+            pa[u] = xs + 4 * (q / JT1); sa[u] = a.Dp;
+            pb[u] = dhs + 4 * (q % JT1); sb[u] = a.Hp;
+        } else {
+            const int q2 = q - T1 < T2 ? q - T1 : 0;      // a thread past the list repeats block 0 and drops it
+            pa[u] = in2 + 4 * (q2 / JT2); sa[u] = s_in2;
+            pb[u] = dys + 4 * (q2 % JT2); sb[u] = a.Cp;
+        }
+    }
+    double acc[NT][4][4];
+#pragma unroll
+    for (int u = 0; u < NT; u++)
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[u][i][j] = 0.0;
+
+    for (int64_t base = lo; base < hi; base += a.TR) {
+        pr_stage(a, base, hi, a.n, g * a.n, dy, dy_step, xs, dys, ok, rt, rw);
+        __syncthreads();
+        if (a.H) {
+            if (T1) pr_hidden<false, true>(a, xs, dys, ok, rw, nullptr, nullptr, hs, dhs);
+            else pr_hidden<false, false>(a, xs, dys, ok, rw, nullptr, nullptr, hs, dhs);
+            __syncthreads();
+        }
+        for (int r = 0; r < a.TR; r++) {
+            if (!ok[r]) continue;
+#pragma unroll
+            for (int u = 0; u < NT; u++) {
+                const float4 va = *reinterpret_cast<const float4 *>(pa[u] + r * sa[u]);
+                const float4 vb = *reinterpret_cast<const float4 *>(pb[u] + r * sb[u]);
+                const double da[4] = {va.x, va.y, va.z, va.w}, db[4] = {vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) acc[u][i][j] = fma(da[i], db[j], acc[u][i][j]);
+            }
+        }
+        __syncthreads();
+    }
+
+    // wg_es's segment order: w1 [D][H], b1 [H] (if set), w2 [n2][C], b2 [C] (if set)
+    double *out = ws + ((int64_t)g * n_chunks + k) * K;
+    const int base2 = a.D * a.H + (a.H && a.b1 ? a.H : 0);
+#pragma unroll
+    for (int u = 0; u < NT; u++) {
+        const int q = (int)threadIdx.x + u * PR_THREADS;
+        const bool l1 = q < T1;
+        if (!l1 && q - T1 >= T2) continue;
+        const int i0 = l1 ? 4 * (q / JT1) : 4 * ((q - T1) / JT2), j0 = l1 ? 4 * (q % JT1) : 4 * ((q - T1) % JT2);
+        const int I = l1 ? a.D : a.n2, J = l1 ? a.H : a.C, off = l1 ? 0 : base2;
+        const bool bias = l1 ? a.b1 != nullptr : a.b2 != nullptr;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int ii = i0 + i, jj = j0 + j;
+                if (jj < J && (ii < I || (ii == I && bias))) out[off + ii * J + jj] = acc[u][i][j];
+            }
+    }
+}
+
+struct PrGrads {
+    float *g[4];        // w1, b1, w2, b2 (NULL: not wanted)
+    int32_t end[4];     // the segments' ends in [0, K]
+};
+
+__global__ __launch_bounds__(PR_THREADS) void pr_grad_tail(const double *__restrict__ ws, PrGrads o, int32_t K,
+                                                           int64_t n_chunks, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * PR_THREADS + threadIdx.x;
+    if (idx >= total) return;
+    const int64_t g = idx / K;
+    const int e = (int)(idx - g * K);
+    float *dst;
+    int lo, hi;
+    if (e < o.end[0]) dst = o.g[0], lo = 0, hi = o.end[0];
+    else if (e < o.end[1]) dst = o.g[1], lo = o.end[0], hi = o.end[1];
+    else if (e < o.end[2]) dst = o.g[2], lo = o.end[1], hi = o.end[2];
+    else dst = o.g[3], lo = o.end[2], hi = o.end[3];
+    if (!dst) return;
+    const double *p = ws + g * n_chunks * K + e;
+    double S = 0.0;
+    for (int64_t c = 0; c < n_chunks; c++) S = __dadd_rn(S, p[c * K]);
+    dst[g * (hi - lo) + (e - lo)] = (float)S;
+}
+
 // [p, p + bytes) of an array of `elem`-byte elements, [n_steps][N] with `stride` elements between steps
 struct Span {
     uintptr_t lo, hi;
 };
-Span span_of(const void *p, int n_steps, int N, int64_t stride, int elem) {
+Span span_of(const void *p, int n_steps, int64_t N, int64_t stride, int elem) {
     const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
     return Span{lo, lo + (uintptr_t)(((int64_t)(n_steps - 1) * stride + N) * elem)};
 }
 bool overlap(const Span &a, const Span &b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// ------------------------------------------------------------------------------------------------ policy rows: host
+struct PrPlan {
+    PrArgs a;
+    int64_t K;            // parameters per set, wg_es's count
+    int32_t end[4];       // the ends of w1, b1, w2, b2 in [0, K]
+    int32_t T1, T2;       // 4 x 4 blocks of the two outer products
+    int32_t n_sets;
+};
+struct PrBuf {
+    const char *name;
+    const void *p;
+    Span s;
+};
+
+// What the three calls check alike; fills the plan (TR stays 0).
+int pr_check(const wg_policy *pol, const wg_policy_rows *rows, const char *who, PrPlan *pl) {
+    if (!pol) return wg_fail(WG_EINVAL, "%s: null policy", who);
+    if (!rows) return wg_fail(WG_EINVAL, "%s: null rows", who);
+    if (!pol->w2) return wg_fail(WG_EINVAL, "%s: null w2", who);
+    if (pol->hidden < 0 || pol->hidden > 256) return wg_fail(WG_EINVAL, "%s: hidden %d outside 0..256", who, pol->hidden);
+    if (pol->hidden > 0 && !pol->w1) return wg_fail(WG_EINVAL, "%s: hidden %d with a null w1", who, pol->hidden);
+    if (pol->obs_dim < 1) return wg_fail(WG_EINVAL, "%s: obs_dim %d < 1", who, pol->obs_dim);
+    if (pol->act_dim < 1) return wg_fail(WG_EINVAL, "%s: act_dim %d < 1", who, pol->act_dim);
+    if (pol->action_out || pol->return_out || pol->length_out)
+        return wg_fail(WG_EINVAL, "%s: action_out / return_out / length_out must be NULL", who);
+    if (rows->n_steps < 1) return wg_fail(WG_EINVAL, "%s: n_steps %d < 1", who, rows->n_steps);
+    if (rows->N < 1) return wg_fail(WG_EINVAL, "%s: N %d < 1", who, rows->N);
+    if (pol->n_sets < 1 || rows->N % pol->n_sets != 0)
+        return wg_fail(WG_EINVAL, "%s: n_sets %d does not divide N = %d", who, pol->n_sets, rows->N);
+    const int64_t D = pol->obs_dim, H = pol->hidden, C = pol->act_dim, n2 = H ? H : D;
+    if ((int64_t)rows->N * D > INT32_MAX || (int64_t)rows->N * C > INT32_MAX || D * (H ? H : C) > INT32_MAX)
+        return wg_fail(WG_ERANGE, "%s: a step's rows or a layer pass 2^31 elements", who);
+    if (!rows->x) return wg_fail(WG_EINVAL, "%s: null x", who);
+    if (rows->x_step < rows->N * D)
+        return wg_fail(WG_EINVAL, "%s: x_step %lld < N * obs_dim = %lld", who, (long long)rows->x_step,
+                       (long long)(rows->N * D));
+    if (rows->mask && rows->mask_step < rows->N)
+        return wg_fail(WG_EINVAL, "%s: mask_step %lld < N = %d", who, (long long)rows->mask_step, rows->N);
+    PrArgs &a = pl->a;
+    a = PrArgs{};
+    a.x = rows->x; a.mask = rows->mask; a.x_step = rows->x_step; a.mask_step = rows->mask_step;
+    a.w1 = H ? pol->w1 : nullptr; a.b1 = H ? pol->b1 : nullptr; a.w2 = pol->w2; a.b2 = pol->b2;
+    a.n_steps = rows->n_steps; a.N = rows->N; a.n = rows->N / pol->n_sets;
+    a.D = (int32_t)D; a.H = (int32_t)H; a.C = (int32_t)C; a.n2 = (int32_t)n2;
+    a.Dp = up4(a.D + 1); a.Hq = up4(a.H + 1); a.Hp = up4(a.H); a.Cp = up4(a.C);
+    pl->n_sets = pol->n_sets;
+    pl->K = D * H + (a.b1 ? H : 0) + n2 * C + (a.b2 ? C : 0);
+    pl->end[0] = (int32_t)(D * H); pl->end[1] = pl->end[0] + (a.b1 ? a.H : 0);
+    pl->end[2] = pl->end[1] + (int32_t)(n2 * C); pl->end[3] = (int32_t)pl->K;
+    return 0;
+}
+
+// The inputs every call reads, for the aliasing checks.
+int pr_inputs(const PrPlan &pl, PrBuf *in) {
+    const PrArgs &a = pl.a;
+    const int64_t G = pl.n_sets;
+    int n = 0;
+    in[n++] = {"x", a.x, span_of(a.x, a.n_steps, (int64_t)a.N * a.D, a.x_step, 4)};
+    if (a.mask) in[n++] = {"mask", a.mask, span_of(a.mask, a.n_steps, a.N, a.mask_step, 1)};
+    if (a.w1) in[n++] = {"w1", a.w1, span_of(a.w1, 1, G * a.D * a.H, 0, 4)};
+    if (a.b1) in[n++] = {"b1", a.b1, span_of(a.b1, 1, G * a.H, 0, 4)};
+    in[n++] = {"w2", a.w2, span_of(a.w2, 1, G * a.n2 * a.C, 0, 4)};
+    if (a.b2) in[n++] = {"b2", a.b2, span_of(a.b2, 1, G * a.C, 0, 4)};
+    return n;
+}
+
+// The backward's own limits: the 4 x 4 blocks in the registers of one workgroup, the rows of a tile in its LDS.
+int pr_backward_plan(PrPlan *pl, int32_t chunk_rows, const char *who, int64_t *n_chunks) {
+    if (chunk_rows < 1) return wg_fail(WG_EINVAL, "%s: chunk_rows %d < 1", who, chunk_rows);
+    PrArgs &a = pl->a;
+    const int64_t t1 = a.H ? (int64_t)(a.Dp / 4) * (a.Hp / 4) : 0, t2 = (int64_t)((a.H ? a.Hq : a.Dp) / 4) * (a.Cp / 4);
+    if (pl->K > WG_POLICY_GRAD_MAX_K || 16 * (t1 + t2) > WG_POLICY_GRAD_MAX_K)
+        return wg_fail(WG_ERANGE, "%s: %lld parameters per set, %lld in 4 x 4 blocks (at most WG_POLICY_GRAD_MAX_K = %d)",
+                       who, (long long)pl->K, (long long)(16 * (t1 + t2)), WG_POLICY_GRAD_MAX_K);
+    pl->T1 = (int32_t)t1; pl->T2 = (int32_t)t2;
+    const int row = 4 * (a.Dp + (a.H ? a.Hq + a.Hp : 0) + a.Cp) + 12;
+    a.TR = PR_LDS / row < PR_BWD_ROWS ? PR_LDS / row : PR_BWD_ROWS;
+    if (a.TR < 1) return wg_fail(WG_ERANGE, "%s: one row needs %d B of LDS (> 64 KiB)", who, row);
+    *n_chunks = ((int64_t)a.n_steps * a.n + chunk_rows - 1) / chunk_rows;
+    if (*n_chunks * pl->n_sets > INT32_MAX)
+        return wg_fail(WG_ERANGE, "%s: %lld chunks in %d sets pass 2^31 workgroups", who, (long long)*n_chunks, pl->n_sets);
+    return 0;
+}
 
 }  // namespace
 
@@ -126,6 +490,94 @@ int wg_gae(const float *reward, const float *value, const float *next_value, con
     else if (cut) go(gae_scan<false, true>);
     else go(gae_scan<false, false>);
     return wg_launched("wg_gae: launch");
+}
+
+int wg_policy_forward(const wg_policy *pol, const wg_policy_rows *rows, float *y, int64_t y_step, hipStream_t stream) {
+    const char *who = "wg_policy_forward";
+    PrPlan pl;
+    if (const int rc = pr_check(pol, rows, who, &pl)) return rc;
+    PrArgs &a = pl.a;
+    if (!y) return wg_fail(WG_EINVAL, "%s: null y", who);
+    if (y_step < (int64_t)a.N * a.C)
+        return wg_fail(WG_EINVAL, "%s: y_step %lld < N * act_dim = %lld", who, (long long)y_step, (long long)a.N * a.C);
+    PrBuf in[6];
+    const int n_in = pr_inputs(pl, in);
+    const Span sy = span_of(y, a.n_steps, (int64_t)a.N * a.C, y_step, 4);
+    for (int i = 0; i < n_in; i++)
+        if (overlap(sy, in[i].s)) return wg_fail(WG_EINVAL, "%s: y aliases %s", who, in[i].name);
+    a.Dp = a.D | 1; a.Hq = a.H | 1;                  // odd row lengths: the rows of a wave fall on distinct LDS banks
+    const bool stage = pl.n_sets == 1 && pl.K * 4 <= PR_W_LDS;
+    const int w_floats = stage ? up4((int)pl.K) : 0;
+    const int row = 4 * (a.Dp + (a.H ? a.Hq : 0)) + 12, room = PR_LDS - 4 * w_floats;
+    a.TR = room / row < PR_FWD_ROWS ? room / row : PR_FWD_ROWS;
+    if (a.TR < 1) return wg_fail(WG_ERANGE, "%s: one row needs %d B of LDS (> %d)", who, row, room);
+    const int64_t n_tiles = ((int64_t)a.n_steps * a.N + a.TR - 1) / a.TR;
+    const int64_t cap = stage ? 2048 : 1 << 20;     // staged weights are loaded once per workgroup: few, long-lived
+    const dim3 grid((unsigned)(n_tiles < cap ? n_tiles : cap));
+    const size_t lds = (size_t)4 * w_floats + (size_t)a.TR * row;
+    if (stage) pr_forward<true><<<grid, PR_THREADS, lds, stream>>>(a, n_tiles, w_floats, y, y_step);
+    else pr_forward<false><<<grid, PR_THREADS, lds, stream>>>(a, n_tiles, w_floats, y, y_step);
+    return wg_launched("wg_policy_forward: launch");
+}
+
+int64_t wg_policy_backward_workspace(const wg_policy *pol, const wg_policy_rows *rows, int32_t chunk_rows) {
+    PrPlan pl;
+    int64_t n_chunks;
+    if (const int rc = pr_check(pol, rows, "wg_policy_backward_workspace", &pl)) return rc;
+    if (const int rc = pr_backward_plan(&pl, chunk_rows, "wg_policy_backward_workspace", &n_chunks)) return rc;
+    return (int64_t)pl.n_sets * n_chunks * pl.K;
+}
+
+int wg_policy_backward(const wg_policy *pol, const wg_policy_rows *rows, const float *dy, int64_t dy_step,
+                       int32_t chunk_rows, double *workspace, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
+                       hipStream_t stream) {
+    const char *who = "wg_policy_backward";
+    PrPlan pl;
+    int64_t n_chunks;
+    if (const int rc = pr_check(pol, rows, who, &pl)) return rc;
+    PrArgs &a = pl.a;
+    if (!dy) return wg_fail(WG_EINVAL, "%s: null dy", who);
+    if (!workspace) return wg_fail(WG_EINVAL, "%s: null workspace", who);
+    if (dy_step < (int64_t)a.N * a.C)
+        return wg_fail(WG_EINVAL, "%s: dy_step %lld < N * act_dim = %lld", who, (long long)dy_step, (long long)a.N * a.C);
+    if (!g_w1 && !g_b1 && !g_w2 && !g_b2) return wg_fail(WG_EINVAL, "%s: every gradient pointer is null", who);
+    if (!a.H && (g_w1 || g_b1)) return wg_fail(WG_EINVAL, "%s: g_w1 / g_b1 without a hidden layer", who);
+    if (g_b1 && !a.b1) return wg_fail(WG_EINVAL, "%s: g_b1 of a policy without b1", who);
+    if (g_b2 && !a.b2) return wg_fail(WG_EINVAL, "%s: g_b2 of a policy without b2", who);
+    if (const int rc = pr_backward_plan(&pl, chunk_rows, who, &n_chunks)) return rc;
+    PrBuf in[7], out[5];
+    int n_in = pr_inputs(pl, in), n_out = 0;
+    in[n_in++] = {"dy", dy, span_of(dy, a.n_steps, (int64_t)a.N * a.C, dy_step, 4)};
+    const int64_t G = pl.n_sets;
+    out[n_out++] = {"workspace", workspace, span_of(workspace, 1, G * n_chunks * pl.K, 0, 8)};
+    if (g_w1) out[n_out++] = {"g_w1", g_w1, span_of(g_w1, 1, G * a.D * a.H, 0, 4)};
+    if (g_b1) out[n_out++] = {"g_b1", g_b1, span_of(g_b1, 1, G * a.H, 0, 4)};
+    if (g_w2) out[n_out++] = {"g_w2", g_w2, span_of(g_w2, 1, G * a.n2 * a.C, 0, 4)};
+    if (g_b2) out[n_out++] = {"g_b2", g_b2, span_of(g_b2, 1, G * a.C, 0, 4)};
+    for (int o = 0; o < n_out; o++) {
+        for (int i = 0; i < n_in; i++)
+            if (overlap(out[o].s, in[i].s)) return wg_fail(WG_EINVAL, "%s: %s aliases %s", who, out[o].name, in[i].name);
+        for (int p = 0; p < o; p++)
+            if (overlap(out[o].s, out[p].s)) return wg_fail(WG_EINVAL, "%s: %s aliases %s", who, out[o].name, out[p].name);
+    }
+    const int32_t T1 = (g_w1 || g_b1) ? pl.T1 : 0;     // without them neither dh nor the layer-1 product is computed
+    const int nt = (T1 + pl.T2 + PR_THREADS - 1) / PR_THREADS;
+    const size_t lds = (size_t)a.TR * (4 * (a.Dp + (a.H ? a.Hq + a.Hp : 0) + a.Cp) + 12);
+    const dim3 grid((unsigned)(n_chunks * G));
+    const int32_t K = (int32_t)pl.K;
+    auto go = [&](auto kernel) {
+        kernel<<<grid, PR_THREADS, lds, stream>>>(a, dy, dy_step, chunk_rows, n_chunks, T1, workspace, K);
+    };
+    if (nt <= 1) go(pr_grad_partial<1>);
+    else if (nt == 2) go(pr_grad_partial<2>);
+    else if (nt == 3) go(pr_grad_partial<3>);
+    else go(pr_grad_partial<4>);
+    if (const int rc = wg_launched("wg_policy_backward (partial sums): launch")) return rc;
+    PrGrads o{{g_w1, g_b1, g_w2, g_b2}, {pl.end[0], pl.end[1], pl.end[2], pl.end[3]}};
+    const int64_t total = G * K;
+    pr_grad_tail<<<(unsigned)((total + PR_THREADS - 1) / PR_THREADS), PR_THREADS, 0, stream>>>(workspace, o, K, n_chunks,
+                                                                                             total);
+    return wg_launched("wg_policy_backward (tail): launch");
 }
 
 }  // extern "C"

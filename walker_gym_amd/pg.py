@@ -14,6 +14,18 @@ GAE.  With gl = RN32(gamma * lam), carry = +0.0, t descending, float32, every op
   c = cut[t] ? +0.0 : carry;            adv[t] = carry = RN32(delta + RN32(gl * c));  ret[t] = RN32(adv[t] + value[t])
 Non-finite inputs flow through; the sign and payload of a NaN the arithmetic produces are not part of the contract (the
 host keeps the NaN operand of a subtraction, the GPU computes a + (-b)).
+
+Differentiable rows.  policy_rows(policy, obs) is the MLPPolicy over recorded rows [T, N, D] as the rollout kernel
+evaluated it (wg_policy_forward: the chain value before the clip), a torch.autograd.Function whose backward is
+wg_policy_backward: per row, float32, every operation rounded by itself,
+  d = +0.0; for c ascending: d = RN32(d + RN32(dy[c] * w2[j][c]));   dh[j] = (z[j] > 0) ? d : +0.0
+and per parameter set, its rows numbered rho = t * n + (w - g * n) and cut into chunks of chunk_rows, float64 sums of
+exact products in a fixed order:
+  P_k[e] = +0.0; rho ascending over the chunk's unskipped rows: P_k[e] = RN64(P_k[e] + a * b)
+  S[e] = +0.0; k ascending: S[e] = RN64(S[e] + P_k[e]);   grad[e] = RN32(S[e])
+with (a, b) = (in[i], dy[c]) for w2[i][c], (1, dy[c]) for b2[c], (x[i], dh[j]) for w1[i][j], (1, dh[j]) for b1[j].
+policy_rows_numpy and policy_grad_numpy restate both on the host, bit for bit.  There is no gradient with respect to
+obs.
 """
 from __future__ import annotations
 
@@ -91,7 +103,212 @@ def gae_numpy(reward, value, next_value, term=None, cut=None, gamma: float = 0.9
     return adv, ret
 
 
-# ---------------------------------------------------------------------------------------------------- the kernel
+def _sets_of(policy, N: int):
+    if policy.G > 1 and N % policy.G != 0:
+        raise ValueError(f"{N} walkers do not divide into {policy.G} parameter sets")
+    return np.arange(N, dtype=np.int64) // (N // policy.G)
+
+
+def _rows_arrays(policy, x, mask):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 3 or x.shape[2] != policy.D:
+        raise ValueError(f"x must be [T, N, {policy.D}], got {x.shape}")
+    T, N, _ = x.shape
+    on = np.ones((T, N), bool) if mask is None else np.asarray(mask).reshape(T, N) != 0
+    return x, on, _sets_of(policy, N)
+
+
+def policy_rows_numpy(policy, x, mask=None):
+    """wg_policy_forward on the host: MLPPolicy.forward_numpy at act_limit = inf, step by step over x [T, N, D].
+    Returns float32 [T, N, C]; the rows mask skips (mask [T, N], 0 = skipped) are zero."""
+    x, on, _ = _rows_arrays(policy, x, mask)
+    T, N, _ = x.shape
+    inf = policy.__class__(policy.w2, policy.b2, policy.w1, policy.b1, act_limit=float("inf"))
+    y = np.zeros((T, N, policy.C), np.float32)
+    for t in range(T):
+        y[t] = np.where(on[t][:, None], inf.forward_numpy(x[t], 0, N), np.float32(0.0))
+    return y
+
+
+def policy_grad_numpy(policy, x, dy, mask=None, chunk_rows: int = 256):
+    """wg_policy_backward on the host: float32 chains, float64 sums, in the contract's order (see the module's
+    docstring).  x [T, N, D], dy [T, N, C], mask [T, N] or None.  Returns (g_w1, g_b1, g_w2, g_b2), float32 arrays
+    shaped like the policy's tensors ([G, D, H], [G, H], [G, n2, C], [G, C]), None for what the policy does not have."""
+    x, on, sets = _rows_arrays(policy, x, mask)
+    T, N, D = x.shape
+    G, H, Cc = policy.G, policy.H, policy.C
+    dy = np.ascontiguousarray(dy, dtype=np.float32)
+    if dy.shape != (T, N, Cc):
+        raise ValueError(f"dy must be {(T, N, Cc)}, got {dy.shape}")
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 1:
+        raise ValueError("chunk_rows < 1")
+    host = lambda t: None if t is None else t.detach().cpu().numpy()
+    w1, b1, w2, b2 = host(policy.w1), host(policy.b1), host(policy.w2), host(policy.b2)
+    n, zero = N // G, np.float32(0.0)
+    with np.errstate(all="ignore"):
+        inp, dh = x, None
+        if H:
+            z = np.zeros((T, N, H), np.float32) if b1 is None else np.broadcast_to(b1[sets], (T, N, H)).copy()
+            for i in range(D):
+                z = z + x[:, :, i:i + 1] * w1[sets, i][None]         # RN32 of the product, then RN32 of the sum
+            inp = np.where(z > 0, z, zero).astype(np.float32)
+            d = np.zeros((T, N, H), np.float32)
+            for c in range(Cc):
+                d = d + dy[:, :, c:c + 1] * w2[sets, :, c][None]
+            dh = np.where(z > 0, d, zero).astype(np.float32)
+
+        def ordered(a, b, bias):
+            """S[g] over the set's rows of (a|1) (x) b: a [T, N, I], b [T, N, J] -> float32 [G, I (+ 1), J]."""
+            if bias:
+                a = np.concatenate([a, np.ones(a.shape[:2] + (1,), np.float32)], axis=2)
+            a = a.astype(np.float64).reshape(T, G, n, -1)
+            b = b.astype(np.float64).reshape(T, G, n, -1)
+            v = on.reshape(T, G, n)
+            S = np.zeros((G, a.shape[3], b.shape[3]), np.float64)
+            P = np.zeros_like(S)
+            for rho in range(T * n):
+                if rho and rho % chunk_rows == 0:
+                    S, P = S + P, np.zeros_like(S)
+                t, r = divmod(rho, n)
+                P = np.where(v[t, :, r, None, None], P + a[t, :, r, :, None] * b[t, :, r, None, :], P)
+            return (S + P).astype(np.float32)
+
+        g2 = ordered(inp, dy, b2 is not None)
+        n2 = inp.shape[2]
+        g_w2, g_b2 = np.ascontiguousarray(g2[:, :n2]), (None if b2 is None else np.ascontiguousarray(g2[:, n2]))
+        g_w1 = g_b1 = None
+        if H:
+            g1 = ordered(x, dh, b1 is not None)
+            g_w1, g_b1 = np.ascontiguousarray(g1[:, :D]), (None if b1 is None else np.ascontiguousarray(g1[:, D]))
+    return g_w1, g_b1, g_w2, g_b2
+
+
+# ---------------------------------------------------------------------------------------------------- the kernels
+def _rows_struct(policy, obs, mask, who):
+    """(wg_policy, wg_policy_rows, T, N, the 3-D views kept alive) of obs [T, N, D] / [R, D] and mask [T, N] / [R]."""
+    import torch
+    if not isinstance(obs, torch.Tensor) or obs.dim() not in (2, 3) or obs.dtype != torch.float32:
+        raise ValueError(f"{who}: obs must be a float32 device tensor [T, N, D] or [R, D]")
+    flat = obs.dim() == 2
+    o3 = obs[None] if flat else obs
+    T, N, D = (int(v) for v in o3.shape)
+    if D != policy.D or obs.device != policy.device:
+        raise ValueError(f"{who}: obs is [.., {D}] on {obs.device}, the policy takes {policy.D} values on {policy.device}")
+    if T < 1 or N < 1:
+        raise ValueError(f"{who}: no rows")
+    if o3.stride(2) != 1 or o3.stride(1) != D or (T > 1 and o3.stride(0) < N * D):
+        raise ValueError(f"{who}: only the step dimension of obs may be strided (strides {tuple(o3.stride())})")
+    m3 = None
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.device != obs.device:
+            raise ValueError(f"{who}: mask must be a uint8 or bool tensor on {obs.device}")
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        m3 = mask[None] if flat else mask
+        if mask.dtype != torch.uint8 or tuple(m3.shape) != (T, N) or m3.stride(1) != 1 or (T > 1 and m3.stride(0) < N):
+            raise ValueError(f"{who}: mask must be uint8 / bool {(T, N)} with only its step dimension strided")
+    rows = _lib.WgPolicyRows(x=_lib.ptr(o3), x_step=o3.stride(0) if T > 1 else N * D, mask=_lib.ptr(m3),
+                             mask_step=(m3.stride(0) if T > 1 else N) if m3 is not None else 0, n_steps=T, N=N)
+    return policy.struct(N), rows, T, N, o3, m3, flat
+
+
+def default_chunk_rows(T: int, n: int) -> int:
+    """policy_rows' chunk_rows: 256 rows, more once a set has over 512 such chunks (the workspace stays near 512 K
+    doubles per set)."""
+    return max(256, -(-(T * n) // 512))
+
+
+def policy_rows_forward(policy, obs, mask=None, y_out=None):
+    """wg_policy_forward called directly (no autograd): y [T, N, C] (or [R, C]) of the rows of obs, written into y_out
+    where given (float32 [T, N, C], only its step dimension strided; skipped rows of a y_out are left as they are).
+    Without y_out the skipped rows are zero."""
+    import torch
+    pol, rows, T, N, o3, m3, flat = _rows_struct(policy, obs, mask, "policy_rows_forward")
+    Cc, dv = policy.C, obs.device
+    if y_out is None:
+        y = (torch.empty if m3 is None else torch.zeros)((T, N, Cc), dtype=torch.float32, device=dv)
+    else:
+        y = y_out[None] if (flat and isinstance(y_out, torch.Tensor) and y_out.dim() == 2) else y_out
+        if (not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.device != dv or tuple(y.shape) != (T, N, Cc)
+                or y.stride(2) != 1 or y.stride(1) != Cc):
+            raise ValueError(f"policy_rows_forward: y_out must be float32 {(T, N, Cc)} with only its step dimension strided")
+    stream = torch.cuda.current_stream(dv).cuda_stream
+    _lib.check(_lib.load().wg_policy_forward(pol, rows, _lib.ptr(y), y.stride(0) if T > 1 else N * Cc, stream),
+               "wg_policy_forward")
+    return y[0] if flat else y
+
+
+_ROWS_FN = None
+
+
+def _rows_function():
+    global _ROWS_FN
+    if _ROWS_FN is not None:
+        return _ROWS_FN
+    import torch
+
+    class PolicyRows(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, policy, obs, mask, chunk_rows, w1, b1, w2, b2):
+            ctx.policy, ctx.chunk_rows = policy, chunk_rows
+            ctx.save_for_backward(obs, mask)
+            return policy_rows_forward(policy, obs, mask)
+
+        @staticmethod
+        def backward(ctx, dy):
+            need = ctx.needs_input_grad[4:8]
+            if not any(need):
+                return (None,) * 8
+            obs, mask = ctx.saved_tensors
+            grads = policy_rows_backward(ctx.policy, obs, dy.to(torch.float32).contiguous(), mask, ctx.chunk_rows, need)
+            return (None, None, None, None, *grads)
+
+    _ROWS_FN = PolicyRows
+    return PolicyRows
+
+
+def policy_rows(policy, obs, mask=None, chunk_rows: Optional[int] = None):
+    """The chain values y of `policy` (an MLPPolicy: before the clip, act_limit ignored) on the recorded rows obs
+    [T, N, D], or [R, D] read as T = 1, N = R: float32 [T, N, C] (or [R, C]), bit for bit what the rollout kernels add
+    their noise to.  Row (t, w) uses parameter set w // (N // G).  obs is a float32 device tensor; only its step
+    dimension may be strided (a window of a longer buffer passes without a copy).  mask, uint8 or bool [T, N] (or
+    [R]): rows with 0 are skipped (they may hold anything, NaN included); their y is zero and they add nothing to any
+    gradient: a minibatch is a row mask.
+
+    Differentiable with respect to policy.w1 / b1 / w2 / b2, whichever require grad (MLPPolicy keeps the tensors it was
+    given by identity: make them nn.Parameters or leaves with requires_grad); what the autograd engine does not need is
+    not computed.  There is NO gradient with respect to obs: its grad stays None.  The backward's sums are ordered
+    (module docstring), chunk_rows rows per float64 partial sum, default max(256, ceil(T * n / 512)); two calls give
+    identical bits.  The float64 workspace is allocated per call.  ValueError for what the library refuses."""
+    return _rows_function().apply(policy, obs, mask, chunk_rows, policy.w1, policy.b1, policy.w2, policy.b2)
+
+
+def policy_rows_backward(policy, obs, dy, mask=None, chunk_rows: Optional[int] = None, want=(True, True, True, True)):
+    """wg_policy_backward called directly: (g_w1, g_b1, g_w2, g_b2) of dy [T, N, C] (or [R, C]) on the rows of obs, None
+    where `want` is False or the policy has no such tensor.  What policy_rows' autograd backward runs."""
+    import torch
+    pol, rows, T, N, o3, m3, flat = _rows_struct(policy, obs, mask, "policy_rows_backward")
+    dv = obs.device
+    if not isinstance(dy, torch.Tensor) or dy.dtype != torch.float32 or dy.device != dv:
+        raise ValueError("policy_rows_backward: dy must be a float32 tensor on the rows' device")
+    d3 = dy[None] if dy.dim() == 2 else dy
+    if tuple(d3.shape) != (T, N, policy.C) or d3.stride(2) != 1 or d3.stride(1) != policy.C:
+        raise ValueError(f"policy_rows_backward: dy must be {(T, N, policy.C)} with only its step dimension strided")
+    chunk = default_chunk_rows(T, N // policy.G) if chunk_rows is None else int(chunk_rows)
+    L = _lib.load()
+    count = L.wg_policy_backward_workspace(pol, rows, chunk)
+    _lib.check(count, "wg_policy_backward_workspace")
+    ws = torch.empty(int(count), dtype=torch.float64, device=dv)
+    grads = [torch.empty_like(t) if (k and t is not None) else None
+             for t, k in zip((policy.w1, policy.b1, policy.w2, policy.b2), want)]
+    p = _lib.ptr
+    _lib.check(L.wg_policy_backward(pol, rows, p(d3), d3.stride(0) if T > 1 else N * policy.C, chunk, p(ws),
+                                    *(p(g) for g in grads), torch.cuda.current_stream(dv).cuda_stream),
+               "wg_policy_backward")
+    return tuple(grads)
+
+
 def gae(reward, value, next_value, term=None, cut=None, gamma: float = 0.99, lam: float = 0.95, adv_out=None,
         ret_out=None, want_ret: bool = True):
     """wg_gae on device tensors: reward / value / next_value float32 [T, N], term / cut uint8 (or bool) [T, N] or None,

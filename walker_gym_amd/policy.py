@@ -72,6 +72,13 @@ class _BoundPolicy:
 
 
 class MLPPolicy:
+    """The policy of the module's docstring over w2 [G, H or D, C], b2 [G, C], w1 [G, D, H], b1 [G, H].
+
+    A tensor that is already contiguous and of full rank ([G, ..]) is kept by identity: an nn.Parameter (or any leaf
+    that requires grad) handed in stays that object in .w1 / .b1 / .w2 / .b2.  walker_gym_amd.pg.policy_rows
+    differentiates with respect to exactly those, so an optimizer over the same parameters updates the policy the
+    rollout kernel reads, with no copy in between."""
+
     def __init__(self, w2, b2=None, w1=None, b1=None, act_limit: float = 1.0):
         w2 = _as_tensor(w2, "w2")
         if w2.dim() == 2:
