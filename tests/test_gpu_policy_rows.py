@@ -6,6 +6,7 @@ import functools
 import numpy as np
 import pytest
 
+import rows_cases as rc
 from conftest import gpu_available
 
 pytestmark = pytest.mark.gpu
@@ -72,22 +73,40 @@ SHAPES = [
     ((3, 1000), 1, 1, 5, 1, True, True, 7),
     ((9, 65), 155, 5, 0, 5, False, True, 7),
     ((2, 63), 191, 8, 64, 1, True, True, 7),
-]
+] + [shape for shape, _ in rc.EDGES]   # the plan's edges (tests/rows_cases.py), each asserted from the restated plan
+EDGE_OF = dict(rc.EDGES)
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "T%dxN%d-D%d-C%d-H%d-G%d-%d%d-k%d" % (s[0] + s[1:]))
+def _blank_mask(T, N, tile, TR):
+    """A mask [T, N] without forward tile `tile` (rows tile * TR .. of rho = t * N + w) and without row 0."""
+    mask = np.ones(T * N, np.uint8)
+    mask[tile * TR:(tile + 1) * TR] = 0
+    mask[0] = 0
+    return mask.reshape(T, N)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "T%dxN%d-D%d-C%d-H%d-G%d-%d%d-k%d" % (s[0] + s[1:8]))
 def test_forward_and_backward_equal_numpy(shape):
     import torch
     from walker_gym_amd import pg
-    (T, N), D, Cc, H, G, b1, b2, chunk = shape
-    pol = _policy(sum(shape[1:]) + T, G, D, H, Cc, b1, b2)
+    (T, N), D, Cc, H, G, b1, b2, chunk = shape[:8]
+    plan = rc.plan_of(shape)
+    for k, v in EDGE_OF.get(shape, {}).items():
+        assert plan[k] == v, (k, plan[k], v)
+    pol = _policy(sum(shape[1:8]) + T, G, D, H, Cc, b1, b2)
     x, dy = _rows(N + D, T, N, D, Cc)
-    y = pg.policy_rows_forward(pol, _dev(x))
-    got = pg.policy_rows_backward(pol, _dev(x), _dev(dy), None, chunk)
+    mask = None
+    if len(shape) > 8:   # a mask that empties one whole forward tile
+        assert shape[8] < plan["n_tiles"] - 1
+        mask = _blank_mask(T, N, shape[8], plan["fwd_TR"])
+        x[mask == 0] = np.nan
+        dy[mask == 0] = np.nan
+    y = pg.policy_rows_forward(pol, _dev(x), _dev(mask))
+    got = pg.policy_rows_backward(pol, _dev(x), _dev(dy), _dev(mask), chunk)
     torch.cuda.synchronize()
     cpu = pol.to("cpu")
-    assert tuple(y.shape) == (T, N, Cc) and _same(y, pg.policy_rows_numpy(cpu, x))
-    want = pg.policy_grad_numpy(cpu, x, dy, None, chunk)
+    assert tuple(y.shape) == (T, N, Cc) and _same(y, pg.policy_rows_numpy(cpu, x, mask))
+    want = pg.policy_grad_numpy(cpu, x, dy, mask, chunk)
     for name, a, b in zip(("w1", "b1", "w2", "b2"), got, want):
         assert _same(a, b), name
         assert a is None or bool(torch.isfinite(a).all())
@@ -216,6 +235,61 @@ def test_gradient_subsets_and_determinism():
         pg.policy_rows_forward(pol, _dev(x).double())
     with pytest.raises(ValueError):
         pg.policy_rows_forward(pol, _dev(x), y_out=_dev(x))     # y_out of the wrong shape
+
+
+@pytest.mark.parametrize("shape,full_nt", [(rc.EDGES[2][0], 4), (SHAPES[4], 3)], ids=["1024-blocks", "155x64"])
+def test_layer_two_alone_drops_the_layer_one_blocks(shape, full_nt):
+    """want = (False, False, True, True) on shapes whose full call is pr_grad_partial<4> / <3>: with g_w1 and g_b1 NULL
+    T1 becomes 0 and the launch is <1> (64 and 34 blocks), h is recomputed without dh.  The full call's bits."""
+    import torch
+    from walker_gym_amd import pg
+    (T, N), D, Cc, H, G, b1, b2, chunk = shape
+    assert rc.plan_of(shape)["NT"] == full_nt and rc.plan_of(shape, layer1=False)["NT"] == 1
+    pol = _policy(90 + D, G, D, H, Cc, b1, b2)
+    x, dy = _rows(91 + D, T, N, D, Cc)
+    args = (pol, _dev(x), _dev(dy), None, chunk)
+    full = pg.policy_rows_backward(*args)
+    part = pg.policy_rows_backward(*args, want=(False, False, True, True))
+    torch.cuda.synchronize()
+    assert part[0] is None and part[1] is None
+    for k in (2, 3):
+        assert torch.equal(part[k].view(torch.int32), full[k].view(torch.int32)), k
+        assert bool(torch.isfinite(part[k]).all()) and bool((part[k] != 0).any())
+    want = pg.policy_grad_numpy(pol.to("cpu"), x, dy, None, chunk)
+    assert _same(part[2], want[2]) and _same(part[3], want[3])
+
+
+def test_forward_walks_more_tiles_than_workgroups():
+    """199,996 rows of a staged policy: 3,125 tiles of 64 rows on a grid capped at 2,048 workgroups, so 1,077 workgroups
+    take a second tile (staged weights reused, xs / hs / ok rewritten behind the closing barrier) and the last tile is
+    partial.  A random mask that also blanks one whole second-round tile; y_out holds a sentinel that skipped rows
+    keep.  The L2 path's cap of 2^20 workgroups needs over 67 million rows and is deliberately not covered."""
+    import torch
+    from walker_gym_amd import pg
+    (T, N), D, Cc, H, G, b1, b2 = rc.SECOND_TILE
+    plan = rc.plan_of(rc.SECOND_TILE)
+    assert plan["stage"] and plan["fwd_TR"] == 64 and plan["n_tiles"] == 3125 and plan["grid"] == 2048
+    assert (T * N) % 64 == 60, "a partial last tile"
+    pol = _policy(95, G, D, H, Cc, b1, b2)
+    rng = np.random.default_rng(96)
+    x = rng.standard_normal((T, N, D)).astype(f32)
+    mask = (rng.random(T * N) < 0.8).astype(np.uint8)
+    blank = 2048 + 700                                   # a tile of the second round
+    mask[blank * 64:(blank + 1) * 64] = 0
+    mask = mask.reshape(T, N)
+    x[mask == 0] = np.nan
+    y = torch.full((T, N, Cc), -123.0, device=DEV)
+    out = pg.policy_rows_forward(pol, _dev(x), _dev(mask), y_out=y)
+    torch.cuda.synchronize()
+    assert out.data_ptr() == y.data_ptr()
+    yh, on = y.cpu().numpy(), mask != 0
+    want = pg.policy_rows_numpy(pol.to("cpu"), x, mask)
+    assert not (yh[on] == -123.0).any(), "an unskipped row kept the sentinel: a tile was not walked"
+    assert _same(yh[on], want[on])
+    assert (yh[~on] == -123.0).all() and np.isfinite(yh).all()
+    second = np.zeros(T * N, bool)
+    second[2048 * 64:] = True                            # the rows only a second iteration reaches
+    assert (on.reshape(-1) & second).sum() > 50000
 
 
 @pytest.mark.parametrize("flat", [False, True])

@@ -82,14 +82,19 @@ def _state(env, auto_reset):
     return st
 
 
-def _run(name, auto_reset, Tn, step_base=gc.STEP_BASE, seed=gc.SEED, buffers=True, env=None, slots=gc.SLOTS):
+def _run(name, auto_reset, Tn, step_base=gc.STEP_BASE, seed=gc.SEED, buffers=True, env=None, slots=gc.SLOTS,
+         walker_base=gc.WALKER_BASE, zeros=False, only=None):
+    """One call on a fresh env (or `env`).  only: of the per-step buffers, the named ones alone."""
     import torch
     case = gc.case_of(name)
     env = _env(name, auto_reset) if env is None else env
     buf = _buffers(env, Tn, case.C, auto_reset) if buffers else {}
+    if only is not None:
+        buf = {k: v for k, v in buf.items() if k in only}
     kw = dict(episode_slots=slots) if auto_reset else {}
-    res = env.rollout_stochastic(gc.policy_of(case, DEV), Tn, _sigma(name), seed, step_base=step_base,
-                                 walker_base=gc.WALKER_BASE, **buf, **kw)
+    sigma = torch.from_numpy(gc.sigma_of(name, zeros).copy()).to(DEV)
+    res = env.rollout_stochastic(gc.policy_of(case, DEV), Tn, sigma, seed, step_base=step_base,
+                                 walker_base=walker_base, **buf, **kw)
     torch.cuda.synchronize()
     out = dict(_host(buf), **_state(env, auto_reset))
     out["stats"] = {k: v.cpu().numpy() for k, v in res.items()}
@@ -121,25 +126,16 @@ def _check_state(got, want, names):
     assert np.array_equal(got["contact"].astype(np.uint8).ravel(), np.asarray(want["contact"]).astype(np.uint8).ravel())
 
 
-# ------------------------------------------------------------------ against the CPU reference
-@CASES
-def test_auto_reset_off_equals_reference_engine(name):
-    """Every step's obs / reward / done / action / raw action / aeps, the final state, returns and lengths."""
-    fused, _ = _off(name)
-    ref = gc.reference_off(name)
+def _check_off(fused, ref):
     for k in OFF_STEP:
         a, b = fused[k], np.ascontiguousarray(ref[k]).reshape(fused[k].shape)
         assert a.dtype == b.dtype and _same(a, b), k
     _check_state(fused, ref, [(k, k) for k in STATE[:-1]])
     assert _same(fused["stats"]["returns"], ref["returns"]) and _same(fused["stats"]["lengths"], ref["lengths"])
-    assert set(fused["stats"]) == {"returns", "lengths"}
 
 
-@CASES
-def test_auto_reset_on_equals_composed_reference(name):
-    """Per-step outputs including steps, reset and final_obs, the final state, episodes, every stats array (4 slots)."""
-    fused, _ = _on(name)
-    ref = dict(gc.reference_on(name))
+def _check_on(fused, ref):
+    ref = dict(ref)
     ref["steps_t"] = ref["steps"]
     for k in ON_STEP:
         a, b = fused[k], np.ascontiguousarray(ref[k]).reshape(fused[k].shape)
@@ -148,6 +144,22 @@ def test_auto_reset_on_equals_composed_reference(name):
                                        ("steps", "steps"), ("episodes", "episodes")])
     for k in STATS:
         assert fused["stats"][k].dtype == ref["stats"][k].dtype and _same(fused["stats"][k], ref["stats"][k]), k
+
+
+# ------------------------------------------------------------------ against the CPU reference
+@CASES
+def test_auto_reset_off_equals_reference_engine(name):
+    """Every step's obs / reward / done / action / raw action / aeps, the final state, returns and lengths."""
+    fused, _ = _off(name)
+    _check_off(fused, gc.reference_off(name))
+    assert set(fused["stats"]) == {"returns", "lengths"}
+
+
+@CASES
+def test_auto_reset_on_equals_composed_reference(name):
+    """Per-step outputs including steps, reset and final_obs, the final state, episodes, every stats array (4 slots)."""
+    fused, _ = _on(name)
+    _check_on(fused, gc.reference_on(name))
     assert fused["reset"].sum(0).min() >= 2 and fused["reset"][-1].any()
 
 
@@ -167,12 +179,97 @@ def test_weights_staged_and_through_l2(monkeypatch):
     staged = {n: pc.lds_bytes(gc.case_of(n).pol)["staged"][1] for n in gc.NAMES}
     assert staged["canonical-h0-shared"] and staged["six-h5-c6-shared"], staged
     assert not staged["balance-h5-4sets"] and not staged["canonical4-h5-5sets"] and not staged["balance16-h0-perwalker"]
+    assert not staged["canonical4-perwalker-c5-inf"] and not staged["wide-h5-c20-shared"]
     monkeypatch.setenv("WG_POLICY_STAGE", "0")
     for name in ("canonical-h0-shared", "six-h5-c6-shared"):
         l2 = _run(name, False, gc.T_OFF)
         fused, _ = _off(name)
         for k in OFF_STEP + STATE:
             assert _same(l2[k], fused[k]), (name, k)
+
+
+# ------------------------------------------------------------------ every NZ instance
+@pytest.mark.parametrize("auto_reset", [False, True], ids=["off", "ar"])
+@pytest.mark.parametrize("edge8", [True, False], ids=["compact", "16-byte"])
+@pytest.mark.parametrize("name", gc.COVER_NAMES)
+def test_every_noise_instance_equals_reference(name, edge8, auto_reset, monkeypatch):
+    """The NZ instance of walker_rollout_policy at every (IN3D, NE, E8, AR): pg_cases.COVER's batches (512 full tiles of
+    16 walkers of M = 4, or of one of M = 64), the walkers per wave asserted from the launch geometry.  Without
+    auto-reset every per-step buffer, the final state, returns and lengths; with it those buffers plus steps, reset and
+    final_obs, the final state, episodes and every stats array.  Both record formats against one reference."""
+    if not edge8:
+        monkeypatch.setenv("WG_EDGE8", "0")
+    case = gc.case_of(name)
+    env = _env(name, auto_reset)
+    geo = env.launch_geometry()
+    assert geo["walkers_per_block"] * 64 // geo["threads"] == case.wpw, geo
+    if auto_reset:
+        _check_on(_run(name, True, gc.T_ON, env=env), gc.reference_on(name))
+    else:
+        _check_off(_run(name, False, case.t_off, env=env), gc.reference_off(name))
+
+
+# ------------------------------------------------------------------ the edges of the noise's inputs
+@pytest.mark.parametrize("auto_reset", [False, True], ids=["off", "ar"])
+def test_largest_accepted_counters(auto_reset):
+    """step_base + T = 2^32 and walker_base + N = 2^32, the largest counters wg_rollout_stochastic accepts, on the batch
+    whose last tile is half full (the lanes past N of that tile wrap their 32-bit walker counter; they store nothing):
+    every buffer equals the reference driven with the same counters, and the variates are not the usual run's."""
+    name = gc.ZEROS
+    case = gc.case_of(name)
+    Tn = gc.T_ON if auto_reset else case.t_off
+    env = _env(name, auto_reset)
+    assert env.N % case.wpw != 0, "a partial last tile"
+    sb, wb = gc.LAST - Tn, gc.LAST - env.N
+    got = _run(name, auto_reset, Tn, step_base=sb, walker_base=wb, env=env)
+    if auto_reset:
+        _check_on(got, gc.reference_on(name, sb, wb))
+    else:
+        _check_off(got, gc.reference_off(name, gc.SEED, sb, wb))
+    usual = (_on if auto_reset else _off)(name)[0]
+    assert not _same(got["eps"], usual["eps"]) and not _same(got["action"], usual["action"])
+
+
+def test_zero_sigma_entries():
+    """A sigma whose set 1 is all zero and which has one zero column in every other set: bits against the reference, and
+    where sigma is 0 and the chain value y is not zero, the raw action is y in bits (y from pg.policy_rows on the obs
+    rows the previous step recorded).  At y == -0.0 the contract differs: u = RN32(-0.0 + RN32(0 * aeps))
+    is +0.0 wherever the product is +0.0 (aeps >= 0) and -0.0 elsewhere, so those entries are left to the reference
+    comparison."""
+    import torch
+    from walker_gym_amd import pg
+    name = gc.ZEROS
+    case = gc.case_of(name)
+    got = _run(name, False, case.t_off, zeros=True)
+    _check_off(got, gc.reference_off(name, gc.SEED, gc.STEP_BASE, gc.WALKER_BASE, True))
+    assert not _same(got["raw"], _off(name)[0]["raw"])
+    sg = gc.sigma_of(name, True)
+    N = got["raw"].shape[1]
+    zero = (sg == 0)[np.arange(N) // (N // case.G)]                     # [N, C]
+    assert zero[N // case.G:2 * (N // case.G)].all() and zero.sum(1).min() == 1
+    y = pg.policy_rows(gc.policy_of(case, DEV), torch.from_numpy(got["obs"][:-1].copy()).to(DEV)).cpu().numpy()
+    raw = got["raw"][1:]                                                # step t acts on the rows step t - 1 recorded
+    sel = zero[None] & (y != 0)
+    assert sel.sum() > 0.9 * zero.sum() * len(y)
+    assert np.array_equal(raw.view(np.uint32)[sel], y.view(np.uint32)[sel])
+    rest = ~np.broadcast_to(zero[None], y.shape)                       # (and the other entries did get their noise)
+    assert (raw.view(np.uint32)[rest] != y.view(np.uint32)[rest]).mean() > 0.9
+
+
+@pytest.mark.parametrize("name,auto_reset,only", [("canonical4-h5-5sets", False, "raw_action_out"),
+                                                  ("six-h5-c6-shared", True, "eps_out")])
+def test_one_noise_buffer_at_a_time(name, auto_reset, only):
+    """Only raw_action_out, or only eps_out (and no other per-step buffer): the buffer given carries the full run's
+    bytes, and the final state and the call's statistics are the full run's."""
+    full = (_on if auto_reset else _off)(name)[0]
+    got = _run(name, auto_reset, gc.T_ON if auto_reset else gc.case_of(name).t_off, only=(only,))
+    key = _KEYS[only]
+    assert set(got) & set(_KEYS.values()) == {key}
+    assert got[key].dtype == np.float32 and _same(got[key], full[key])
+    for k in STATE + (("episodes",) if auto_reset else ()):
+        assert _same(got[k], full[k]), k
+    for k in full["stats"]:
+        assert _same(got["stats"][k], full["stats"][k]), k
 
 
 # ------------------------------------------------------------------ the counters

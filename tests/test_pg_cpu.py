@@ -384,8 +384,11 @@ def _conditions(ref, case, T):
     u, a, e = ref["raw"], ref["action"], ref["eps"]
     clipped = np.abs(u) > f32(case.L)
     print(case.name, "clipped", float(clipped.mean()))
-    assert clipped.any() and not clipped.all(), "some action is clipped and some is not"
-    assert np.array_equal(np.abs(a[clipped]), np.full(int(clipped.sum()), f32(case.L)))
+    if np.isinf(case.L):   # no clip: the action is the raw action, in bits, everywhere
+        assert not clipped.any() and np.array_equal(bits(a), bits(u))
+    else:
+        assert clipped.any() and not clipped.all(), "some action is clipped and some is not"
+        assert np.array_equal(np.abs(a[clipped]), np.full(int(clipped.sum()), f32(case.L)))
     # RN32(sigma * aeps) changes the bits of some unclipped action: u - d is not u there (y itself is not recorded)
     N = u.shape[1]
     srow = np.broadcast_to(sg[0], (N, case.C)) if case.G == 1 else sg[np.arange(N) // (N // case.G)]
@@ -404,6 +407,55 @@ def test_cases_without_auto_reset_mean_something(name):
     # another seed gives other actions
     other = gc.reference_off(name, gc.SEED + 1)
     assert not np.array_equal(other["action"], ref["action"])
+
+
+@pytest.mark.parametrize("name", gc.COVER_NAMES)
+def test_cover_cases_without_auto_reset_mean_something(name):
+    """The instance-coverage cases (pg_cases.COVER), T = 4: finite, clipped and unclipped actions, a noise that moves
+    some unclipped action's bits."""
+    case, ref = gc.case_of(name), gc.reference_off(name)
+    assert case.t_off == 4 and case.H == 0 and case.G == 1
+    _conditions(ref, case, case.t_off)
+    for k in ("pos", "vel", "acc"):
+        assert np.isfinite(ref[k]).all(), k
+
+
+@pytest.mark.parametrize("name", gc.COVER_NAMES)
+def test_cover_cases_with_auto_reset_mean_something(name):
+    """As above with auto-reset, T = 16: every walker resets at least once."""
+    case, ref = gc.case_of(name), gc.reference_on(name)
+    _conditions(ref, case, gc.T_ON)
+    for k in ("pos", "vel", "acc"):
+        assert np.isfinite(ref["state"][k]).all(), k
+    assert (ref["reset"].sum(0) >= 1).all(), "every walker resets at least once"
+
+
+def test_edge_inputs_mean_something():
+    """The inputs of test_gpu_stochastic_rollout.py's edge tests, on the reference alone.  The largest accepted counters
+    (step_base + T = walker_base + N = 2^32) give other variates than the usual ones and a finite run; the sigma with
+    zero entries has set 1 all zero and one zero column in every other set, and leaves the run finite."""
+    name = gc.ZEROS
+    case, base = gc.case_of(name), gc.reference_off(name)
+    N = gc.n_walkers(case)
+    assert case.wpw == 4 and N % case.wpw == 2, "a half-full last tile"
+    edge = gc.reference_off(name, gc.SEED, gc.LAST - case.t_off, gc.LAST - N)
+    assert not np.array_equal(bits(edge["eps"]), bits(base["eps"]))
+    assert np.array_equal(bits(edge["eps"]), bits(pg.action_noise_numpy(gc.SEED, gc.LAST - case.t_off, case.t_off,
+                                                                        gc.LAST - N, N, case.C)))
+    edge_on = gc.reference_on(name, gc.LAST - gc.T_ON, gc.LAST - N)
+    for ref in (edge, edge_on):
+        for k in ("obs", "reward", "action", "raw", "eps"):
+            assert np.isfinite(ref[k]).all(), k
+    assert not np.array_equal(bits(edge_on["eps"]), bits(gc.reference_on(name)["eps"]))
+    sg = gc.sigma_of(name, True)
+    assert not sg[1].any() and all((sg[g] == 0).sum() == 1 for g in range(case.G) if g != 1)
+    zr = gc.reference_off(name, gc.SEED, gc.STEP_BASE, gc.WALKER_BASE, True)
+    for k in ("obs", "reward", "action", "raw", "eps"):
+        assert np.isfinite(zr[k]).all(), k
+    # step 0 acts on the same rows: the raw action changes where sigma became zero, and nowhere else
+    zero = (sg == 0)[np.arange(N) // (N // case.G)]
+    moved = bits(zr["raw"][0]) != bits(base["raw"][0])
+    assert moved[zero].mean() > 0.9 and not moved[~zero].any()
 
 
 @pytest.mark.parametrize("name", gc.NAMES)

@@ -391,6 +391,33 @@ def test_the_k_limit_on_both_sides(lib):
     _expect(lib, _apply(_big(20000, 0, 1), [("a", "y", None)]).forward(lib), _lib.WG_EINVAL, b"null y", "forward")
 
 
+def test_the_restated_plan_agrees_with_the_host_at_its_limits(lib):
+    """tests/rows_cases.py::plan against wg_policy_backward_workspace, which plans without launching: the two at-limit
+    shapes (1,024 blocks behind a hidden layer; K = WG_POLICY_GRAD_MAX_K without one) are accepted, each with one more
+    block (one more 4-column group of C, or D + 4) is refused, and the restatement says the same; every edge shape's
+    K is the host's count."""
+    import rows_cases as rc
+    assert rc.MAX_K == _lib.POLICY_GRAD_MAX_K
+    for shape in rc.AT_LIMIT:
+        _, D, Cc, H, G, b1, b2 = shape[:7]
+        p = rc.plan(D, H, Cc, 1, b1, b2)
+        assert p["bwd_ok"] and p["blocks"] == 1024 and p["NT"] == 4
+        assert _big(D, H, Cc, b1=b1, b2=b2).workspace(lib) == p["K"]
+        for d, c in ((D, Cc + 4), (D + 4, Cc)):
+            q = rc.plan(d, H, c, 1, b1, b2)
+            assert not q["bwd_ok"] and q["blocks"] > 1024, (d, c)
+            for fn in ("workspace", "backward"):
+                _expect(lib, getattr(_big(d, H, c, b1=b1, b2=b2), fn)(lib), _lib.WG_ERANGE, b"WG_POLICY_GRAD_MAX_K", (fn, d, c))
+    for shape, _ in rc.EDGES:
+        (T, N), D, Cc, H, G, b1, b2, chunk = shape[:8]
+        p = rc.plan_of(shape)
+        assert p["bwd_ok"] and 1 <= p["bwd_TR"] <= 16 and 1 <= p["fwd_TR"] <= 64
+        assert _big(D, H, Cc, b1=b1, b2=b2).workspace(lib) == p["K"], shape
+    # the second-tile shape: staged, 64 rows to a tile, more tiles than the staged grid's cap
+    p = rc.plan_of(rc.SECOND_TILE)
+    assert p["stage"] and p["fwd_TR"] == 64 and p["n_tiles"] == 3125 > p["grid"] == rc.FWD_CAP
+
+
 def test_aliasing_is_refused_down_to_one_shared_element(lib):
     def share_last_first(c, out, inp, out_elems, elem=4):
         """`out` placed so that its last element is `inp`'s first."""
