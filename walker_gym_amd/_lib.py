@@ -103,7 +103,7 @@ POLICY_GRAD_MAX_K = 16384   # WG_POLICY_GRAD_MAX_K
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
            "wg_step_simple", "wg_observe_simple", "wg_reset", "wg_reset_noise", "wg_plan_ragged", "wg_plan_waves",
            "wg_wave_edge_passes", "wg_plan_errors", "wg_launch_geometry", "wg_launch_floor", "wg_time_step",
-           "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches", "wg_es_perturb", "wg_es_update",
+           "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches", "wg_wt_launches", "wg_es_perturb", "wg_es_update",
            "wg_rollout_stochastic", "wg_gae", "wg_policy_forward", "wg_policy_backward_workspace", "wg_policy_backward")
 
 _lib = None
@@ -166,6 +166,7 @@ def load(path: str | None = None):
         for f in EXPORTS[2:]:
             getattr(L, f).restype = C.c_int
         L.wg_fix_launches.restype = C.c_longlong
+        L.wg_wt_launches.restype = C.c_longlong
         L.wg_policy_backward_workspace.restype = C.c_int64
         v = L.wg_abi_version()
         if v != ABI_VERSION:

@@ -2411,6 +2411,51 @@ __device__ __forceinline__ void lean_obs_rows(float *obs, int stride, const KPar
         *WG_ST(obs, (uint32_t)(w0 + mu_wl) * (uint32_t)stride + per * M + nmid + mu_ua, 1) = FIX ? x : x * kp.mk;
 }
 
+// The FIX instances' tile epilogue through LDS (WT; launch_lean's lean_wt_ok, WG_WT=0 forces the FIX epilogue as it was): a full tile's pos, vel and
+// observation rows are three contiguous pieces of HBM (768 B, 768 B, wpw * stride * 4 B: the rows have no padding), so
+// the wave lays them out in the spring terms' area of its slice, dead after the mass loop, exactly as they lie in HBM
+// (the rows as lean_obs_rows<FIX> writes them), and then stores 16 B per lane, each store instruction whole lines, as
+// write-through (sc1) buffer stores: they leave the L2 as they are issued, not as dirty lines at the kernel's end.  (The
+// same image with plain 16-B stores did not pass the keep rule, profiles/r10_wt_ab_bench_canonical.json; narrow stores
+// stay plain: written through they cost a fabric write each.)  The host checked: the bases are 16-B aligned, the
+// pieces multiples of 16 B, the image fits (lean_wt_ok).
+template <bool IN3D>
+__device__ __forceinline__ void lean_tile_image(const wg_batch &b, const KOut &o, char *sl, int M, int A, int w0, int lane,
+                                                int wl, int q, int mu_wl, int mu_ua, bool is_mus, float px, float py,
+                                                float pz, float vx, float vy, float vz, float ax, float ay, float az,
+                                                float midx, float midy, float midz, float x) {
+    constexpr int d = IN3D ? 3 : 2, per = 3 * d;
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const int stride = per * M + A;                     // == o.obs_stride (lean_wt_ok)
+    float *img = reinterpret_cast<float *>(sl);         // pos | vel | rows
+    wave_sync();   // the mass loop's term reads (its IEEE redo branch's too) are complete
+    float *ip = img + 3 * lane, *iv = img + 192 + 3 * lane, *ir = img + 384 + wl * stride + per * q;
+    ip[0] = px; ip[1] = py; ip[2] = pz;
+    iv[0] = vx; iv[1] = vy; iv[2] = vz;
+    const float pm[3] = {px - midx, py - midy, pz - midz}, vm[3] = {vx, vy, vz}, am[3] = {ax, ay, az};
+#pragma unroll
+    for (int c = 0; c < d; c++) { ir[c] = pm[c]; ir[d + c] = vm[c]; ir[2 * d + c] = am[c]; }
+    if (is_mus) img[384 + mu_wl * stride + per * M + mu_ua] = x;
+    wave_sync();
+    const u4 *im4 = reinterpret_cast<const u4 *>(sl);
+    const uint32_t tile = (uint32_t)w0 >> (6 - (31 - __builtin_clz(M)));   // w0 / wpw, wpw * M == 64
+    const uint32_t nrow = (64u / (uint32_t)M) * (uint32_t)stride * 4u;        // the tile's row bytes
+    const uint32_t lb = 16u * (uint32_t)lane;
+    auto put = [&](float *base, uint32_t bytes, uint32_t off, const u4 &v) {   // (the descriptor: wave-uniform, in SGPRs)
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)off, 0, 16);   // aux 16: sc1
+    };
+    const uint32_t sbytes = (uint32_t)b.N * (uint32_t)M * 12u, obytes = (uint32_t)b.N * (uint32_t)stride * 4u;
+    if (lane < 48) {
+        const u4 vp = im4[lane], vv = im4[48 + lane];
+        put(b.pos, sbytes, tile * 768u + lb, vp);
+        put(b.vel, sbytes, tile * 768u + lb, vv);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++)   // (at most 160 16-B pieces: wpw * A <= 64)
+        if (lb + 1024u * k < nrow) put(o.obs, obytes, tile * nrow + lb + 1024u * k, im4[96 + lane + 64 * k]);
+}
+
 // One wave's tile after its loads: the edge lanes leave the spring term t and the damping force df of every
 // edge in LDS, then each mass lane walks its incidence list, dividing by m as the reference does (mass_step).
 // RES (walker_rollout_lean): the tile's state stays in L across steps; it is written to HBM only when `last`.
@@ -2433,12 +2478,14 @@ struct LeanPolOut { float ax, ay, az, sx, sy, sz, reward; int done; int reset; }
 // in the last spring pass only), continuous actions on every muscle, no pair passes, pins or radii, run1, midform 1
 // without conmid, unit observation scales, obs / reward / done / centroid / energy present (the steps output stays a
 // wave-uniform test).  The same arithmetic in the same order.
-template <bool IN3D, int NE, bool RES = false, bool E8 = false, bool AR = false, bool POL = false, bool FIX = false>
+template <bool IN3D, int NE, bool RES = false, bool E8 = false, bool AR = false, bool POL = false, bool FIX = false,
+          bool WT = false>
 __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &kp_in, const KOut &o,
                                              const LeanGeo &lg, char *sl, const LeanTile &t, int lane,
                                              LeanIn<NE, E8> &L, bool last = true, const KReset &ar = KReset{},
                                              LeanPolOut *po = nullptr, uint32_t *epw = nullptr, int epw_stride = 1) {
     static_assert(!FIX || (E8 && !RES && !AR && !POL && NE <= 4), "FIX: the plain E8 step instance");
+    static_assert(!WT || FIX, "WT: the FIX instances' tile epilogue");
     const KParams kp_fix = FIX ? lean_fix_params(kp_in) : KParams{};
     const KParams &kp = FIX ? kp_fix : kp_in;
     const bool store = !RES || last;
@@ -2633,7 +2680,13 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     if (is_mass) {
         // acc and contact (wave-uniform): not in the steps of a multi-step call before its last (run(); the resident
         // kernel stores after its last step only)
-        if (store) WG_STORE_STATE(b, pl, px, py, pz, vx, vy, vz, ax, ay, az, RES || kp.keep_aux, hit)
+        if constexpr (WT) {   // (pos and vel leave with the tile image below)
+            if (kp.keep_aux) {
+                float *gao = WG_ST(b.acc, pl, 3);
+                gao[0] = ax; gao[1] = ay; gao[2] = az;
+                if (b.contact) at_u32w(b.contact, pl) = (uint8_t)hit;
+            }
+        } else if (store) WG_STORE_STATE(b, pl, px, py, pz, vx, vy, vz, ax, ay, az, RES || kp.keep_aux, hit)
         if (q == 0) {
             const uint32_t wg = (uint32_t)(w0 + wl);
             const int steps = L.wsteps + 1;
@@ -2665,7 +2718,10 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
 
     STAMP(5);
     // ================= observation rows: Creature.getstat (gym/optimized_walker.py:129-162) =========
-    if ((FIX || o.obs) && !(WG_ABLATE & 16))
+    if constexpr (WT)
+        lean_tile_image<IN3D>(b, o, sl, M, A, w0, lane, wl, q, mu_wl, mu_ua, is_mus, px, py, pz, vx, vy, vz, ax, ay, az,
+                                  midx, midy, midz, x);
+    else if ((FIX || o.obs) && !(WG_ABLATE & 16))
         lean_obs_rows<IN3D, FIX>(o.obs, o.obs_stride, kp, M, A, w0, wl, q, mu_wl, mu_ua, is_mass, is_mus, px, py, pz,
                                  vx, vy, vz, ax, ay, az, sx, sy, sz, midx, midy, midz, x);
     // ================= auto-reset (ABI 16): the walkers whose episode this step ended start their next one here
@@ -2764,7 +2820,8 @@ constexpr int lean_waves(int NE) { return NE >= 8 ? 4 : 6; }
 // One tile (64 / M walkers) per wave; waves never wait for one another.  E8: the compact spring records (b.edges8).
 // AR: the auto-reset tail (ABI 16), its arguments in the trailing `ar` (empty otherwise).
 // FIX: the fixed-parameter instance for full tiles on the default path (lean_fix_ok; WG_FIX=0 forces the generic one).
-template <bool IN3D, int NE, bool E8, bool AR = false, bool FIX = false>
+// WT (FIX only): pos, vel and the observation rows leave as the tile's image through LDS (lean_tile_image).
+template <bool IN3D, int NE, bool E8, bool AR = false, bool FIX = false, bool WT = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(NE)))) void walker_step_lean(
     typename std::conditional<AR, wg_batch, KBatch15>::type bk, KParams kp, const float *__restrict__ action,
     int action_cols, int action_stride, KOut o, LeanGeo lg, typename std::conditional<AR, KReset, KNoReset>::type ar) {
@@ -2786,7 +2843,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lean_waves(
     if (kp.prio) __builtin_amdgcn_s_setprio(0);
     STAMP(1);
     if constexpr (AR) lean_compute<IN3D, NE, false, E8, true>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L, true, ar);
-    else lean_compute<IN3D, NE, false, E8, false, false, FIX>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
+    else lean_compute<IN3D, NE, false, E8, false, false, FIX, WT>(b, kp, o, lg, smem + wv * lg.slice, t, lane, L);
 }
 
 // NE = 1, the latency-bound small batches (Balance-4096: 512 waves, one per SIMD, the launch as long as its slowest
@@ -3820,6 +3877,7 @@ int wg_debug_stamps(unsigned long long *host, int n) {
 }
 
 long long wg_fix_launches(void) { return g_fix_launches.load(std::memory_order_relaxed); }
+long long wg_wt_launches(void) { return g_wt_launches.load(std::memory_order_relaxed); }
 
 int wg_launch_geometry(const wg_batch *b, wg_launch_info *info) {
     int rc = validate(b);

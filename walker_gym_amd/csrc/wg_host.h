@@ -289,6 +289,25 @@ bool lean_fix_ok(const wg_batch *b, const KParams &kp, const Actions &a, const w
 // launches that took the fixed-parameter instance, this process (wg_fix_launches: the tests read which instance ran)
 std::atomic<long long> g_fix_launches{0};
 
+// The FIX instances' tile epilogue through LDS (lean_tile_image: pos, vel and the observation rows as the tile's HBM
+// image, stored 16 B per lane, write-through).  A FIX launch takes it, as a whole launch, when the observation rows are
+// contiguous (no padding; FIX has no conmid column), pos / vel / obs start on 16-B boundaries, a tile's row block is a
+// multiple of 16 B (pos and vel are 768 B each: wpw * M == 64) and the image fits the spring terms' area of the wave's
+// slice.  A one-pass tile (walker_step_lean1) never qualifies: its terms' area is at most 64 x 36 = 2,304 B, and pos and
+// vel alone are 1,536 B of the image.  WG_WT=0 (read on every launch, like WG_FIX) forces today's epilogue: the control
+// arm and the tests' cross-check.
+bool lean_wt_ok(const wg_batch *b, bool in3d, const wg_outputs &o, const LeanGeo &g, bool fix) {
+    if (!fix || env_int("WG_WT", 1) == 0 || lean_passes(g, b) < 2) return false;
+    const int row = 3 * (in3d ? 3 : 2) * b->M + b->A;
+    const int64_t rows_b = (int64_t)g.wpw * row * 4;
+    auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    static_assert(64 * 12 % 16 == 0, "a tile's pos / vel block");
+    return o.obs_stride == row && al16(b->pos) && al16(b->vel) && al16(o.obs) && rows_b % 16 == 0 &&
+           2 * 768 + rows_b <= g.off_inc;
+}
+// launches that took that epilogue, this process (wg_wt_launches)
+std::atomic<long long> g_wt_launches{0};
+
 // One step of a uniform batch on the lean kernels.  ar_mode (wg_params.auto_reset) != 0: the AR instances (the auto-reset
 // tail, ABI 16); a launch that lean_fix_ok admits: the FIX instances.  One spring pass is walker_step_lean1's, with its
 // leading arguments preloaded (the compact records take the spring records' slot).
@@ -299,6 +318,7 @@ int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const Actions &
     const uint32_t lds = (uint32_t)(g.wpb * g.slice + std::max(0, env_int("WG_LDS_PAD", 0)));
     const bool e8 = use_edge8(b, g);
     const bool fix = lean_fix_ok(b, kp, a, o, g, e8, ne, ar_mode);   // (E8, 1..4 passes, no auto-reset)
+    const bool wt = lean_wt_ok(b, in3d, o, g, fix);
     const dim3 grid(g.nblk), block(64 * g.wpb);
     with_instance(in3d, ne, e8, [&](auto d3, auto n, auto c8) {
         constexpr bool D3 = decltype(d3)::value, E8 = decltype(c8)::value;
@@ -319,6 +339,7 @@ int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const Actions &
                 WG_KLAUNCH(kernel, grid, block, lds, st, batch, kp, a.ptr, a.cols, a.stride, kout(o), g, reset);
             };
             if constexpr (E8 && NE <= 4) {
+                if (wt) return go(walker_step_lean<D3, NE, true, false, true, true>, kbatch15(b), KNoReset{});
                 if (fix) return go(walker_step_lean<D3, NE, true, false, true>, kbatch15(b), KNoReset{});
             }
             if (ar_mode) go(walker_step_lean<D3, NE, E8, true>, *b, kreset(o, ar_mode));
@@ -327,6 +348,7 @@ int launch_lean(const wg_batch *b, const KParams &kp, bool in3d, const Actions &
     });
     if (const int rc = wg_launched("launch")) return rc;
     if (fix) g_fix_launches.fetch_add(1, std::memory_order_relaxed);
+    if (wt) g_wt_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }
 

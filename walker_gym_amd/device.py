@@ -283,6 +283,8 @@ class DeviceBatch:
         # this process's step launches that took the lean kernel's fixed-parameter instance so far (a counter: the
         # difference around a call tells which instance ran it; WG_FIX=0 forces the generic one)
         geo["fix_launches"] = int(_lib.load().wg_fix_launches())
+        # ... and, of those, the launches that stored their tiles as an image through LDS (WG_WT)
+        geo["wt_launches"] = int(_lib.load().wg_wt_launches())
         return geo
 
     KIND = {"pos": "mass", "vel": "mass", "acc": "mass", "contact": "mass", "radius": "mass", "muscle_x": "muscle",
