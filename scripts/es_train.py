@@ -6,6 +6,12 @@ the curve is recorded as it comes.
 
     python scripts/es_train.py [--walkers 1024] [--population 1024] [--hidden 0] [--generations 30] [--steps 200]
                                [--sigma 0.001] [--lr 1e-4] [--seed 0] [--out profiles/r10_es_balance_curve.json]
+
+--adaptive trains with AdaptiveEvolutionStrategy instead (one sigma per parameter, every entry starting at --sigma,
+adapted with the class defaults) and records sigma_vec's mean / min / max per generation as well.  Its step along the
+mean's estimate is sigma^2 times the scalar trainer's, so --lr is divided by --sigma^2 there: both trainers start with
+the same step.
+    python scripts/es_train.py --adaptive --out profiles/r13_es_adaptive_balance_curve.json
 """
 import argparse
 import json
@@ -18,7 +24,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from walker_gym_amd.batched_env import BatchedPhysicsEnv   # noqa: E402
-from walker_gym_amd.es import EvolutionStrategy            # noqa: E402
+from walker_gym_amd.es import AdaptiveEvolutionStrategy, EvolutionStrategy   # noqa: E402
 from walker_gym_amd.walker import balance_spec             # noqa: E402
 
 
@@ -32,10 +38,15 @@ def main():
     ap.add_argument("--sigma", type=float, default=0.001)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     env = BatchedPhysicsEnv(balance_spec(a.walkers), in3d=0)
-    tr = EvolutionStrategy(env, hidden=a.hidden, population=a.population, sigma=a.sigma, lr=a.lr, seed=a.seed)
+    if a.adaptive:
+        tr = AdaptiveEvolutionStrategy(env, hidden=a.hidden, population=a.population, sigma=a.sigma,
+                                       lr=a.lr / a.sigma ** 2, seed=a.seed)
+    else:
+        tr = EvolutionStrategy(env, hidden=a.hidden, population=a.population, sigma=a.sigma, lr=a.lr, seed=a.seed)
     start = env.batch.state_dict()
     curve = []
     t0 = time.perf_counter()
@@ -48,10 +59,14 @@ def main():
                       "fitness_min": float(out["fitness_min"]),
                       "diverged_candidates": int(torch.isnan(out["fitness"]).sum()),
                       "grad_norm": float(out["grad"].double().norm())})
+        if a.adaptive:
+            curve[-1].update(grad_sigma_norm=float(out["grad_sigma"].double().norm()),
+                             sigma_mean=float(out["sigma_mean"]), sigma_min=float(out["sigma_min"]),
+                             sigma_max=float(out["sigma_max"]))
         print(json.dumps(curve[-1]), flush=True)
     torch.cuda.synchronize()
     res = {"env": "Balance-v0", "walkers": env.N, "population": tr.G, "hidden": tr.H, "K": tr.K, "steps": a.steps,
-           "sigma": tr.sigma, "lr": tr.lr, "seed": tr.seed, "seconds": time.perf_counter() - t0,
+           "trainer": type(tr).__name__, "sigma": a.sigma if a.adaptive else tr.sigma, "lr": tr.lr, "seed": tr.seed, "seconds": time.perf_counter() - t0,
            "device": torch.cuda.get_device_name(0), "curve": curve}
     if a.out:
         with open(a.out, "w") as f:

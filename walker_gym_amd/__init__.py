@@ -29,9 +29,9 @@ def __getattr__(name):
     if name == "MLPPolicy":
         from . import policy
         return policy.MLPPolicy
-    if name == "EvolutionStrategy":
+    if name in ("EvolutionStrategy", "AdaptiveEvolutionStrategy"):   # the latter: one adapted sigma per parameter (PGPE)
         from . import es
-        return es.EvolutionStrategy
+        return getattr(es, name)
     if name == "pg":   # policy-gradient support: the noise and GAE restatements, gae(), collect()
         import importlib
         return importlib.import_module(".pg", __name__)

@@ -86,6 +86,13 @@ class WgEs(C.Structure):
                 ("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp)]
 
 
+class WgEsDiagStep(C.Structure):
+    """wg_es_diag_step: the scales, learning rates and sigma bounds of wg_es_update_diag."""
+    _fields_ = [("scale_theta", C.c_double), ("scale_sigma", C.c_double), ("base", C.c_float), ("lr_theta", C.c_float),
+                ("lr_sigma", C.c_float), ("shrink", C.c_float), ("grow", C.c_float), ("sigma_min", C.c_float),
+                ("sigma_max", C.c_float)]
+
+
 class WgActionNoise(C.Structure):
     """wg_action_noise: the seeded exploration noise of wg_rollout_stochastic and its optional per-step outputs."""
     _fields_ = [("seed", C.c_uint64), ("step_base", C.c_uint32), ("walker_base", C.c_uint32), ("sigma", _vp),
@@ -104,7 +111,8 @@ EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_r
            "wg_step_simple", "wg_observe_simple", "wg_reset", "wg_reset_noise", "wg_plan_ragged", "wg_plan_waves",
            "wg_wave_edge_passes", "wg_plan_errors", "wg_launch_geometry", "wg_launch_floor", "wg_time_step",
            "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches", "wg_wt_launches", "wg_es_perturb", "wg_es_update",
-           "wg_rollout_stochastic", "wg_gae", "wg_policy_forward", "wg_policy_backward_workspace", "wg_policy_backward")
+           "wg_rollout_stochastic", "wg_gae", "wg_policy_forward", "wg_policy_backward_workspace", "wg_policy_backward",
+           "wg_es_perturb_diag", "wg_es_update_diag")
 
 _lib = None
 _lock = threading.Lock()
@@ -146,6 +154,9 @@ def load(path: str | None = None):
                                          _vp, _vp, _vp, _vp, _vp]
         L.wg_es_perturb.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp]
         L.wg_es_update.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp, C.c_double, C.c_float, _vp, _vp, _vp, _vp]
+        L.wg_es_perturb_diag.argtypes = [C.POINTER(WgEs), _vp, C.c_int32, C.c_int32, _vp]
+        L.wg_es_update_diag.argtypes = [C.POINTER(WgEs), _vp, C.c_int32, C.c_int32, _vp, C.POINTER(WgEsDiagStep), _vp,
+                                        _vp, _vp, _vp, _vp, _vp]
         L.wg_step_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,
                                      C.POINTER(_vp)]
         L.wg_run_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,

@@ -11,6 +11,12 @@ biases), w2 (n2*C with n2 = H or D, element (i, c) at i*C + c), b2 (C; only with
 theta +- RN32(sigma * eps_j) (antithetic pairs).  The update is the centred-rank estimate
   grad[k] = scale * sum_j (util[2j] - util[2j+1]) * eps_j[k],   scale = 1 / (2 * n_pairs * sigma),
 summed in float64 in a fixed order (chunks of 256 pairs), then theta += lr * grad in float32.
+
+AdaptiveEvolutionStrategy over wg_es_perturb_diag / wg_es_update_diag keeps one sigma per parameter (a float32 [K]
+device vector) and adapts it from the same samples (PGPE with symmetric sampling): with d = RN32(sigma[k] * eps),
+  g_theta[k] = scale_theta * sum_j (util[2j] - util[2j+1]) * d_j[k]
+  g_sigma[k] = scale_sigma * sum_j ((util[2j] + util[2j+1]) / 2 - base) * (d_j[k]^2 - sigma[k]^2) / sigma[k],
+the same chunked float64 sums, then a float32 step on each and a clamp on sigma's (es_update_diag_numpy).
 """
 from __future__ import annotations
 
@@ -99,6 +105,65 @@ def es_update_numpy(theta, util, seed: int, generation: int, first_pair: int, n_
             S = S + P
         grad = (S * np.float64(scale)).astype(np.float32)
         return grad, theta + np.float32(lr) * grad
+
+
+def es_perturb_diag_numpy(theta, sigma_vec, seed: int, generation: int, first_pair: int, n_pairs: int) -> np.ndarray:
+    """wg_es_perturb_diag's candidates, laid out as es_perturb_numpy's: d = RN32(sigma_vec[k] * eps)."""
+    theta = np.ascontiguousarray(theta, dtype=np.float32)
+    sigma_vec = np.ascontiguousarray(sigma_vec, dtype=np.float32)
+    if sigma_vec.shape != theta.shape:
+        raise ValueError(f"sigma_vec has shape {sigma_vec.shape}, theta {theta.shape}")
+    with np.errstate(all="ignore"):
+        d = sigma_vec[None, :] * es_noise_numpy(seed, generation, first_pair, n_pairs, theta.shape[0])
+        out = np.empty((2 * n_pairs, theta.shape[0]), np.float32)
+        out[0::2] = theta[None, :] + d
+        out[1::2] = theta[None, :] - d
+    return out
+
+
+def diag_step(base=0.0, scale_theta=1.0, scale_sigma=1.0, lr_theta=0.0, lr_sigma=0.0, shrink=1.0, grow=1.0,
+              sigma_min=1e-8, sigma_max=float("inf")) -> dict:
+    """The fields of wg_es_diag_step as a dict (what es_update_diag_numpy and _lib.WgEsDiagStep(**step) take)."""
+    return dict(base=base, scale_theta=scale_theta, scale_sigma=scale_sigma, lr_theta=lr_theta, lr_sigma=lr_sigma,
+                shrink=shrink, grow=grow, sigma_min=sigma_min, sigma_max=sigma_max)
+
+
+def es_update_diag_numpy(theta, sigma_vec, util, seed: int, generation: int, first_pair: int, n_pairs: int, step):
+    """wg_es_update_diag's arithmetic: (g_theta, theta_out, g_sigma, sigma_out), float32 [K] each.  util is indexed by
+    set ([G]); step holds wg_es_diag_step's fields (a dict, see diag_step)."""
+    f32, f64 = np.float32, np.float64
+    theta = np.ascontiguousarray(theta, dtype=f32)
+    sg = np.ascontiguousarray(sigma_vec, dtype=f32)
+    util = np.ascontiguousarray(util, dtype=f32)
+    K = theta.shape[0]
+    if sg.shape != theta.shape:
+        raise ValueError(f"sigma_vec has shape {sg.shape}, theta {theta.shape}")
+    st = diag_step(**step)
+    with np.errstate(all="ignore"):
+        sets = 2 * (first_pair + np.arange(n_pairs))
+        u0, u1 = util[sets], util[sets + 1]
+        dm = (u0 - u1).astype(f64)
+        ds = ((u0 + u1) * f32(0.5) - f32(st["base"])).astype(f64)
+        ss = sg.astype(f64) * sg.astype(f64)
+        Sm, Ss = np.zeros(K, f64), np.zeros(K, f64)
+        for a in range(0, n_pairs, CHUNK):
+            n = min(CHUNK, n_pairs - a)
+            d = (sg[None, :] * es_noise_numpy(seed, generation, first_pair + a, n, K)).astype(f64)
+            q = d * d - ss[None, :]
+            Pm, Ps = np.zeros(K, f64), np.zeros(K, f64)
+            for i in range(n):
+                Pm = Pm + dm[a + i] * d[i]
+                Ps = Ps + ds[a + i] * q[i]
+            Sm, Ss = Sm + Pm, Ss + Ps
+        g_theta = (Sm * f64(st["scale_theta"])).astype(f32)
+        g_sigma = ((Ss * f64(st["scale_sigma"])) / sg.astype(f64)).astype(f32)
+        theta_out = theta + f32(st["lr_theta"]) * g_theta
+        s = sg + f32(st["lr_sigma"]) * g_sigma
+        dn, up = sg * f32(st["shrink"]), sg * f32(st["grow"])
+        lo = np.where(dn > f32(st["sigma_min"]), dn, f32(st["sigma_min"]))
+        hi = np.where(up < f32(st["sigma_max"]), up, f32(st["sigma_max"]))
+        sigma_out = np.where(s < lo, lo, np.where(s > hi, hi, s)).astype(f32)
+        return g_theta, theta_out, g_sigma, sigma_out
 
 
 def param_count(D: int, H: int, Cc: int, biases: bool) -> int:
@@ -262,3 +327,93 @@ class EvolutionStrategy:
         self.theta.copy_(t.to(self.theta.device))
         self.seed, self.generation = int(sd["seed"]), int(sd["generation"])
         self.sigma, self.lr = float(np.float32(sd["sigma"])), float(np.float32(sd["lr"]))
+
+
+class AdaptiveEvolutionStrategy(EvolutionStrategy):
+    """EvolutionStrategy with one standard deviation per parameter, adapted from the same antithetic samples (PGPE with
+    symmetric sampling) by wg_es_perturb_diag / wg_es_update_diag.  `sigma` is a scalar or a [K] vector of initial
+    values; sigma_vec, float32 [K] on the device, is updated in place by every tell(): a step of sigma_lr along the
+    estimate, at most sigma_max_change of the value per generation, within [sigma_min, sigma_max]."""
+
+    def __init__(self, env, hidden: int = 0, act_dim: Optional[int] = None, biases: bool = True,
+                 population: Optional[int] = None, sigma=0.05, lr: float = 0.05, seed: int = 0,
+                 act_limit: float = 1.0, theta0=None, sigma_lr: float = 0.1, sigma_max_change: float = 0.2,
+                 sigma_min: float = 1e-8, sigma_max: float = float("inf")):
+        import torch
+        s0 = np.asarray(sigma.detach().cpu() if hasattr(sigma, "detach") else sigma, dtype=np.float32)
+        if s0.ndim > 1:
+            raise ValueError(f"sigma has shape {s0.shape}: a scalar or a [K] vector")
+        if not (np.isfinite(s0).all() and (s0 > 0).all()):
+            raise ValueError("sigma must be finite and > 0 in every entry")
+        if not np.isfinite(sigma_lr):
+            raise ValueError(f"sigma_lr must be finite, got {sigma_lr!r}")
+        if not 0 <= sigma_max_change < 1:
+            raise ValueError(f"sigma_max_change {sigma_max_change!r} outside [0, 1)")
+        if not (np.isfinite(sigma_min) and sigma_min > 0) or not sigma_max >= sigma_min:
+            raise ValueError(f"need 0 < sigma_min <= sigma_max, got {sigma_min!r}, {sigma_max!r}")
+        super().__init__(env, hidden=hidden, act_dim=act_dim, biases=biases, population=population,
+                         sigma=float(s0.reshape(-1)[0]), lr=lr, seed=seed, act_limit=act_limit, theta0=theta0)
+        if s0.ndim == 1 and s0.shape[0] != self.K:
+            raise ValueError(f"sigma has {s0.shape[0]} entries, expected a scalar or ({self.K},)")
+        self.sigma = 0.0                 # wg_es's scalar: the _diag calls do not read it
+        dv = self.theta.device
+        self.sigma_vec = torch.from_numpy(np.array(np.broadcast_to(s0, (self.K,)), dtype=np.float32)).to(dv).contiguous()
+        f = lambda x: float(np.float32(x))
+        self.sigma_lr, self.sigma_max_change = f(sigma_lr), float(sigma_max_change)
+        self.sigma_min, self.sigma_max = f(sigma_min), f(sigma_max)
+        self._work = torch.empty((2, -(-self.n_pairs // CHUNK), self.K), dtype=torch.float64, device=dv)
+        self._grad_sigma = torch.empty(self.K, dtype=torch.float32, device=dv)
+
+    def step_fields(self) -> dict:
+        """wg_es_diag_step's fields for this trainer: base 0, the PGPE scales, shrink / grow rounded to float32."""
+        return diag_step(base=0.0, scale_theta=1.0 / (2.0 * self.n_pairs), scale_sigma=1.0 / self.n_pairs,
+                         lr_theta=self.lr, lr_sigma=self.sigma_lr,
+                         shrink=float(np.float32(1.0 - self.sigma_max_change)),
+                         grow=float(np.float32(1.0 + self.sigma_max_change)), sigma_min=self.sigma_min,
+                         sigma_max=self.sigma_max)
+
+    def ask(self):
+        """Write the generation's candidates (wg_es_perturb_diag over every pair) and return their MLPPolicy."""
+        es = self._struct()
+        _lib.check(_lib.load().wg_es_perturb_diag(C.byref(es), _lib.ptr(self.sigma_vec), 0, self.n_pairs,
+                                                  self.env._stream()), "wg_es_perturb_diag")
+        return self.policy
+
+    def tell(self, fitness) -> dict:
+        """Update theta and sigma_vec in place from the candidates' fitness [G] and move to the next generation.
+        Returns {'grad': [K] f32, 'grad_sigma': [K] f32}, the two estimates the steps were taken along."""
+        util = self.utilities(fitness).contiguous()
+        es, st, p = self._struct(), _lib.WgEsDiagStep(**self.step_fields()), _lib.ptr
+        _lib.check(_lib.load().wg_es_update_diag(C.byref(es), p(self.sigma_vec), 0, self.n_pairs, p(util), C.byref(st),
+                                                 p(self._work), p(self._grad), p(self.theta), p(self._grad_sigma),
+                                                 p(self.sigma_vec), self.env._stream()), "wg_es_update_diag")
+        self.generation += 1
+        self._told = {"grad": self._grad.clone(), "grad_sigma": self._grad_sigma.clone()}
+        return self._told
+
+    def generation_step(self, n_steps: int, restore: bool = True) -> dict:
+        """EvolutionStrategy.generation_step's dict plus 'grad_sigma' [K] f32 and the 0-d device tensors 'sigma_mean' /
+        'sigma_min' / 'sigma_max' of sigma_vec after the update (nothing here waits for the device)."""
+        out = super().generation_step(n_steps, restore)
+        out["grad_sigma"] = self._told["grad_sigma"]
+        out["sigma_mean"] = self.sigma_vec.double().mean()
+        out["sigma_min"], out["sigma_max"] = self.sigma_vec.min(), self.sigma_vec.max()
+        return out
+
+    def state_dict(self) -> dict:
+        sd = super().state_dict()
+        del sd["sigma"]
+        sd.update(sigma_vec=self.sigma_vec.detach().cpu().clone(), sigma_lr=self.sigma_lr,
+                  sigma_max_change=self.sigma_max_change, sigma_min=self.sigma_min, sigma_max=self.sigma_max)
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        import torch
+        s = torch.as_tensor(sd["sigma_vec"], dtype=torch.float32).reshape(-1)
+        if s.numel() != self.K:
+            raise ValueError(f"sigma_vec has {s.numel()} elements, expected {self.K}")
+        super().load_state_dict(dict(sd, sigma=0.0))
+        self.sigma_vec.copy_(s.to(self.sigma_vec.device))
+        f = lambda x: float(np.float32(x))
+        self.sigma_lr, self.sigma_max_change = f(sd["sigma_lr"]), float(sd["sigma_max_change"])
+        self.sigma_min, self.sigma_max = f(sd["sigma_min"]), f(sd["sigma_max"])
