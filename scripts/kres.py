@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Resource usage (VGPRs, scratch, occupancy) of every kernel in walker_hip.hip, es_hip.hip and pg_hip.hip:
+"""Resource usage (VGPRs, SGPR spills, scratch, occupancy) of every kernel in walker_hip.hip, es_hip.hip and pg_hip.hip:
     python scripts/kres.py [extra hipcc flags, e.g. -DWG_LEAN_SOA=0]"""
 import os
 import re
@@ -21,10 +21,10 @@ for unit in ("walker_hip.hip", "es_hip.hip", "pg_hip.hip"):
             cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
             cur = re.sub(r"\(anonymous namespace\)::", "", cur).split("(")[0]
             rows[cur] = {}
-        for key, pat in (("vgpr", r"VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+        for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("sspill", r"SGPRs Spill: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
                          ("occ", r"Occupancy \[waves/SIMD\]: (\d+)")):
             m = re.search(pat, line)
             if m and cur:
                 rows[cur][key] = int(m.group(1))
 for k, v in rows.items():
-    print(f"{k:60s} vgpr {v.get('vgpr'):4} scratch {v.get('scratch'):4} occ {v.get('occ')}")
+    print(f"{k:60s} vgpr {v.get('vgpr'):4} sgpr-spill {v.get('sspill'):4} scratch {v.get('scratch'):4} occ {v.get('occ')}")

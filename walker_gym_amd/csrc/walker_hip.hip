@@ -1041,11 +1041,12 @@ __device__ __forceinline__ void mass_step(const KParams &kp, const double *st, c
         if (!done && steps > 100) done = (all_stopped);     \
     } while (0)
 // A mass of a diverged walker after the integrator (the wave kernels stepped a finite stand-in): what the reference
-// computes, NaN in every component and no contact
+// computes, NaN in every component, and the contact of its y before the step (`below`: the reference tests the ground
+// on the position the step starts from, gym/optimized_env.py:154, so a mass whose NaN is in x or z only can be in contact)
 __device__ __forceinline__ void nan_state(float &px, float &py, float &pz, float &vx, float &vy, float &vz, float &ax,
-                                          float &ay, float &az, bool &hit) {
+                                          float &ay, float &az, bool &hit, bool below) {
     px = __builtin_nanf(""); py = px; pz = px; vx = px; vy = px; vz = px; ax = px; ay = px; az = px;
-    hit = false;
+    hit = below;
 }
 // The wave kernels' state stores of mass pl after a step (32-bit byte offsets, WG_ST): pos and vel, and with `aux`
 // (wave-uniform) acc and, where the batch has the array, the contact flag.  (A macro: as an inline function, with the
@@ -2528,11 +2529,12 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     // ================= diverged walkers (round 6): every mass of the walker has a NaN position component, is not pinned
     // and has a spring.  Then every spring term of the walker is NaN (norm, dx, f and the direction all are: Python's
     // max(NaN, r) keeps NaN, gym/engine.py:73-75), so each mass's a, and after run1 its v and pos, are NaN in all three
-    // components; its contact test (pos_y - ground < 0) is false; the muscle lengths still follow the actions.  The
+    // components; its contact test (pos_y - ground < 0, on the y the step starts from) is false only where that y is NaN
+    // or above the ground, so it is taken here (env_apply's comparison); the muscle lengths still follow the actions.  The
     // walker's lanes step benign finite stand-ins (mass q at (q, 0, 0), at rest) so that no exact cold path runs for it,
     // and its state, outputs and sums are then set to what the reference computes: NaN (NaN payloads aside).  A
     // walker only partly NaN, or with an inf, steps exactly as before.  Pair passes keep the plain path.
-    bool dead = false;
+    bool dead = false, dead_hit = false;
     if ((!RES || NE == 1) && kp.pair_mode == 0) {   // (the resident kernel: its latency-bound NE = 1 instance)
         // (the common test reads the positions only, the first loads to land: the pin / incidence words are waited for
         // only in the rare branch, so the springs do not start later)
@@ -2542,6 +2544,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
             const unsigned long long gm = (M == 64) ? ~0ull : (((1ull << M) - 1ull) << (lane & ~(M - 1)));
             dead = is_mass && (db & gm) == gm;
             if (dead) {
+                dead_hit = L.p3[1] - kp.ground < 0.f;
                 L.p3[0] = (float)q; L.p3[1] = 0.f; L.p3[2] = 0.f;
                 L.v3[0] = 0.f; L.v3[1] = 0.f; L.v3[2] = 0.f;
             }
@@ -2653,7 +2656,7 @@ __device__ __forceinline__ void lean_compute(const wg_batch &b, const KParams &k
     if (is_mass) {
         mass_tail(kp, mf, (float)ym, L.p3, L.v3, px, py, pz, vx, vy, vz, ax, ay, az, hit, pin,
                   !RES ? &et : nullptr);
-        if (dead) nan_state(px, py, pz, vx, vy, vz, ax, ay, az, hit);   // (a diverged walker, above)
+        if (dead) nan_state(px, py, pz, vx, vy, vz, ax, ay, az, hit, dead_hit);   // (a diverged walker, above)
         // p.r = 3 / p.r = 1 (gym/optimized_env.py:156,175)
         if (!FIX && b.radius && store) b.radius[pl] = hit ? 3.0 : 1.0;
         nv = np_norm3(vx, vy, vz);
@@ -3396,8 +3399,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
     if (!is_mus) { mx = 0.f; mlo = 0.f; mhi = 0.f; mst = 0.f; }
     if (!acts) act = 0.f;
     // diverged walkers (lean_compute): every mass of the walker NaN somewhere in its position, unpinned, with a spring ->
-    // finite stand-ins now, NaN state and outputs after the integrator
-    bool dead = false;
+    // finite stand-ins now, NaN state and outputs after the integrator, the contact of the y the step starts from
+    bool dead = false, dead_hit = false;
     {
         const bool nanp = is_mass && (__builtin_isnan(p3[0]) || __builtin_isnan(p3[1]) || __builtin_isnan(p3[2]));
         if (__builtin_expect(__ballot(nanp) != 0ull, 0)) {   // wave-uniform, rare
@@ -3406,6 +3409,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
             const unsigned long long gm = (mwn >= 64) ? ~0ull : (((1ull << mwn) - 1ull) << mlm);
             dead = is_mass && (db & gm) == gm;
             if (dead) {
+                dead_hit = p3[1] - kp.ground < 0.f;
                 p3[0] = (float)(lane - mlm); p3[1] = 0.f; p3[2] = 0.f;
                 v3[0] = 0.f; v3[1] = 0.f; v3[2] = 0.f;
             }
@@ -3469,7 +3473,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 4
         mass_accumulate_v2(ts, reinterpret_cast<const uint16_t *>(s_inc) + 2 * mlb, mlb, io0,
                            (WG_ABLATE & 2) ? min(io1, io0 + 1) : io1, mf, ym, ax, ay, az, wave_tiny);
         mass_tail(kp, mf, (float)ym, p3, v3, px, py, pz, vx, vy, vz, ax, ay, az, hit, pin != 0, &et);
-        if (dead) nan_state(px, py, pz, vx, vy, vz, ax, ay, az, hit);
+        if (dead) nan_state(px, py, pz, vx, vy, vz, ax, ay, az, hit, dead_hit);
         const uint32_t pl = (uint32_t)(P0 + lane);
         WG_STORE_STATE(b, pl, px, py, pz, vx, vy, vz, ax, ay, az, kp.keep_aux, hit)   // (as the lean kernel)
         if (b.radius) b.radius[pl] = hit ? 3.0 : 1.0;   // gym/optimized_env.py:156,175
