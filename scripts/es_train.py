@@ -12,6 +12,13 @@ adapted with the class defaults) and records sigma_vec's mean / min / max per ge
 mean's estimate is sigma^2 times the scalar trainer's, so --lr is divided by --sigma^2 there: both trainers start with
 the same step.
     python scripts/es_train.py --adaptive --out profiles/r13_es_adaptive_balance_curve.json
+
+--obs-norm puts a running observation normaliser (walker_gym_amd.normalize.ObsNorm, clip 10) in front of the policy:
+every generation's rollout records its rows, and the rows of every 64th walker update the statistics (the next
+generation's candidates and mean policy run under them; tell() does not read them, so the update's place relative to it
+changes nothing).  The rows are then of order one, so --sigma and --lr default to the trainer's own defaults (0.05,
+0.05) instead of the raw rows' 0.001 and 1e-4.
+    python scripts/es_train.py --adaptive --obs-norm --out profiles/r14_es_obs_norm_balance_curve.json
 """
 import argparse
 import json
@@ -25,6 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from walker_gym_amd.batched_env import BatchedPhysicsEnv   # noqa: E402
 from walker_gym_amd.es import AdaptiveEvolutionStrategy, EvolutionStrategy   # noqa: E402
+from walker_gym_amd.normalize import ObsNorm               # noqa: E402
 from walker_gym_amd.walker import balance_spec             # noqa: E402
 
 
@@ -35,25 +43,37 @@ def main():
     ap.add_argument("--hidden", type=int, default=0)
     ap.add_argument("--generations", type=int, default=30)
     ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--sigma", type=float, default=0.001)
-    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--sigma", type=float, default=None)
+    ap.add_argument("--lr", type=float, default=None)
+    ap.add_argument("--obs-norm", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.sigma = (0.05 if a.obs_norm else 0.001) if a.sigma is None else a.sigma
+    a.lr = (0.05 if a.obs_norm else 1e-4) if a.lr is None else a.lr
     env = BatchedPhysicsEnv(balance_spec(a.walkers), in3d=0)
+    nm = rows = mask = None
+    if a.obs_norm:
+        nm = ObsNorm(env.obs_dim, env.device, clip=10.0)
+        rows = torch.empty((a.steps, env.N, env.obs_dim), dtype=torch.float32, device=env.device)
+        mask = torch.zeros((a.steps, env.N), dtype=torch.uint8, device=env.device)
+        mask[:, ::64] = 1
     if a.adaptive:
         tr = AdaptiveEvolutionStrategy(env, hidden=a.hidden, population=a.population, sigma=a.sigma,
-                                       lr=a.lr / a.sigma ** 2, seed=a.seed)
+                                       lr=a.lr / a.sigma ** 2, seed=a.seed, obs_norm=nm)
     else:
-        tr = EvolutionStrategy(env, hidden=a.hidden, population=a.population, sigma=a.sigma, lr=a.lr, seed=a.seed)
+        tr = EvolutionStrategy(env, hidden=a.hidden, population=a.population, sigma=a.sigma, lr=a.lr, seed=a.seed,
+                               obs_norm=nm)
     start = env.batch.state_dict()
     curve = []
     t0 = time.perf_counter()
     for g in range(a.generations):
         env.batch.load_state_dict(start)
         mean_ret = env.rollout_policy(tr.mean_policy(), a.steps)["returns"].double().mean()
-        out = tr.generation_step(a.steps)
+        out = tr.generation_step(a.steps, obs_out=rows)
+        if nm is not None:
+            nm.update(rows, mask)
         curve.append({"generation": g, "mean_policy_return": float(mean_ret),
                       "fitness_mean": float(out["fitness_mean"]), "fitness_max": float(out["fitness_max"]),
                       "fitness_min": float(out["fitness_min"]),
@@ -63,10 +83,13 @@ def main():
             curve[-1].update(grad_sigma_norm=float(out["grad_sigma"].double().norm()),
                              sigma_mean=float(out["sigma_mean"]), sigma_min=float(out["sigma_min"]),
                              sigma_max=float(out["sigma_max"]))
+        if nm is not None:
+            curve[-1].update(obs_norm_rows=nm.count, obs_norm_scale_min=float(nm.scale.min()),
+                             obs_norm_scale_max=float(nm.scale.max()))
         print(json.dumps(curve[-1]), flush=True)
     torch.cuda.synchronize()
     res = {"env": "Balance-v0", "walkers": env.N, "population": tr.G, "hidden": tr.H, "K": tr.K, "steps": a.steps,
-           "trainer": type(tr).__name__, "sigma": a.sigma if a.adaptive else tr.sigma, "lr": tr.lr, "seed": tr.seed, "seconds": time.perf_counter() - t0,
+           "trainer": type(tr).__name__, "obs_norm": bool(a.obs_norm), "sigma": a.sigma if a.adaptive else tr.sigma, "lr": tr.lr, "seed": tr.seed, "seconds": time.perf_counter() - t0,
            "device": torch.cuda.get_device_name(0), "curve": curve}
     if a.out:
         with open(a.out, "w") as f:

@@ -10,6 +10,13 @@ nothing is asserted: the curve is recorded as it comes.
 
     python scripts/ppo_train.py [--walkers 1024] [--hidden 32] [--iterations 20] [--steps 64] [--epochs 4]
                                 [--sigma 0.3] [--lr 3e-4] [--seed 0] [--out profiles/r12_ppo_balance_curve.json]
+
+--obs-norm: a running observation normaliser (walker_gym_amd.normalize.ObsNorm, clip 10) in front of the actor, inside
+the rollout kernel and inside pg.policy_rows alike, and in front of the critic (the same three torch operations) in place
+of the ad-hoc obs_scale; updated once per iteration from batch["obs_before"], after the iteration's epochs, so that the
+rows are re-evaluated under the statistics they were collected with and the first-pass ratio stays exactly 1.  The
+actor's first layer then starts at 1 / sqrt(D) (unit-scale inputs) instead of 0.002.
+    python scripts/ppo_train.py --obs-norm --out profiles/r14_ppo_obs_norm_balance_curve.json
 """
 import argparse
 import json
@@ -24,6 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from walker_gym_amd import pg                              # noqa: E402
 from walker_gym_amd.batched_env import BatchedPhysicsEnv   # noqa: E402
+from walker_gym_amd.normalize import ObsNorm               # noqa: E402
 from walker_gym_amd.policy import MLPPolicy                # noqa: E402
 from walker_gym_amd.walker import balance_spec             # noqa: E402
 
@@ -43,6 +51,7 @@ def main():
     ap.add_argument("--lam", type=float, default=0.95)
     ap.add_argument("--max-steps", type=int, default=200)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--obs-norm", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.manual_seed(a.seed)
@@ -52,15 +61,19 @@ def main():
     # the actor: the MLPPolicy itself, its tensors the autograd leaves (kept by identity: Adam's in-place steps are what
     # the next rollout reads)
     p = lambda *s, k=1.0: torch.nn.Parameter(torch.randn(s, device=dev) * k)
-    w1, b1 = p(1, D, H, k=0.002), torch.nn.Parameter(torch.zeros(1, H, device=dev))
+    nm = ObsNorm(D, dev, clip=10.0) if a.obs_norm else None
+    w1, b1 = p(1, D, H, k=D ** -0.5 if nm else 0.002), torch.nn.Parameter(torch.zeros(1, H, device=dev))
     w2, b2 = p(1, H, A, k=0.01), torch.nn.Parameter(torch.zeros(1, A, device=dev))
-    pol = MLPPolicy(w2, b2, w1, b1)
+    pol = MLPPolicy(w2, b2, w1, b1, obs_norm=nm)
     assert pol.w1 is w1 and pol.w2 is w2
     log_sigma = torch.nn.Parameter(torch.full((A,), math.log(a.sigma), device=dev))
     critic = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to(dev)
     opt = torch.optim.Adam([w1, b1, w2, b2, log_sigma, *critic.parameters()], lr=a.lr)
     obs_scale = 1e-2   # the rows hold accelerations in the thousands: the critic sees them scaled
-    value_fn = lambda rows: critic((rows * obs_scale).clamp(-10.0, 10.0)).squeeze(-1)
+    if nm is not None:
+        value_fn = lambda rows: critic(nm.normalize_torch(rows)).squeeze(-1)
+    else:
+        value_fn = lambda rows: critic((rows * obs_scale).clamp(-10.0, 10.0)).squeeze(-1)
 
     def log_prob(mean, u):   # Gaussian density of u around the policy's mean
         z = (u - mean) / log_sigma.exp()
@@ -98,6 +111,8 @@ def main():
                 loss.backward()
                 torch.nn.utils.clip_grad_norm_([w1, b1, w2, b2, log_sigma, *critic.parameters()], 0.5)
                 opt.step()
+        if nm is not None:
+            nm.update(obs, ok)
         n_ep = batch["episodes"].sum().clamp(min=1)
         curve.append({"iteration": it, "reward_per_step": float(batch["reward"].double().nanmean()),
                       "episodes": int(batch["episodes"].sum()),
@@ -111,7 +126,7 @@ def main():
     torch.cuda.synchronize()
     res = {"env": "Balance-v0", "walkers": N, "hidden": H, "steps": a.steps, "iterations": a.iterations,
            "epochs": a.epochs, "minibatches": a.minibatches, "lr": a.lr, "clip": a.clip, "gamma": a.gamma,
-           "lam": a.lam, "max_steps": a.max_steps, "seed": a.seed, "seconds": time.perf_counter() - t0,
+           "lam": a.lam, "max_steps": a.max_steps, "seed": a.seed, "obs_norm": bool(a.obs_norm), "seconds": time.perf_counter() - t0,
            "device": torch.cuda.get_device_name(0), "curve": curve}
     if a.out:
         with open(a.out, "w") as f:

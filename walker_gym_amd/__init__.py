@@ -11,7 +11,9 @@ Training on the device: walker_gym_amd.policy.MLPPolicy (evaluated inside the ro
 walker_gym_amd.es.EvolutionStrategy (seeded perturb / update kernels, wg_es_* in the header);
 BatchedPhysicsEnv.rollout_stochastic and walker_gym_amd.pg (seeded action noise in the rollout kernel, the GAE kernel,
 collect() for PPO: wg_rollout_stochastic / wg_gae; policy_rows(), the MLPPolicy over recorded rows as a
-torch.autograd.Function: wg_policy_forward / wg_policy_backward).
+torch.autograd.Function: wg_policy_forward / wg_policy_backward); walker_gym_amd.normalize.ObsNorm, running observation
+statistics on the device (wg_obs_moments) and the normaliser MLPPolicy(obs_norm=...) evaluates in every kernel
+(wg_rollout_normalized, wg_policy_forward_normalized / wg_policy_backward_normalized).
 Importing the package needs no GPU; stepping does (no CPU fallback).
 """
 from .engine import Config, DingPoint, Point, to_data  # noqa: F401
@@ -38,6 +40,12 @@ def __getattr__(name):
     if name == "policy_rows":   # pg.policy_rows(policy, obs, mask=None, chunk_rows=None): differentiable in-kernel policy
         import importlib
         return importlib.import_module(".pg", __name__).policy_rows
+    if name == "normalize":   # observation normalisation: ObsNorm (wg_obs_moments) and the numpy restatements
+        import importlib
+        return importlib.import_module(".normalize", __name__)
+    if name == "ObsNorm":
+        import importlib
+        return importlib.import_module(".normalize", __name__).ObsNorm
     if name == "rollout_stochastic":   # BatchedPhysicsEnv.rollout_stochastic(env, policy, n_steps, sigma, seed, ...)
         from . import batched_env
         return batched_env.BatchedPhysicsEnv.rollout_stochastic

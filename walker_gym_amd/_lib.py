@@ -105,6 +105,11 @@ class WgPolicyRows(C.Structure):
                 ("N", C.c_int32)]
 
 
+class WgObsNorm(C.Structure):
+    """wg_obs_norm: the observation normaliser in front of wg_policy's layers."""
+    _fields_ = [("mean", _vp), ("scale", _vp), ("clip", C.c_float)]
+
+
 POLICY_GRAD_MAX_K = 16384   # WG_POLICY_GRAD_MAX_K
 
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
@@ -112,7 +117,8 @@ EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_r
            "wg_wave_edge_passes", "wg_plan_errors", "wg_launch_geometry", "wg_launch_floor", "wg_time_step",
            "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches", "wg_wt_launches", "wg_es_perturb", "wg_es_update",
            "wg_rollout_stochastic", "wg_gae", "wg_policy_forward", "wg_policy_backward_workspace", "wg_policy_backward",
-           "wg_es_perturb_diag", "wg_es_update_diag")
+           "wg_es_perturb_diag", "wg_es_update_diag", "wg_rollout_normalized", "wg_policy_forward_normalized",
+           "wg_policy_backward_normalized", "wg_obs_moments_workspace", "wg_obs_moments")
 
 _lib = None
 _lock = threading.Lock()
@@ -152,6 +158,16 @@ def load(path: str | None = None):
         L.wg_policy_backward_workspace.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgPolicyRows), C.c_int32]
         L.wg_policy_backward.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgPolicyRows), _vp, C.c_int64, C.c_int32, _vp,
                                          _vp, _vp, _vp, _vp, _vp]
+        L.wg_rollout_normalized.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), C.POINTER(WgPolicy),
+                                            C.POINTER(WgObsNorm), C.POINTER(WgActionNoise), C.POINTER(WgOutputs),
+                                            C.POINTER(WgEpisodeStats), C.c_int32, _vp]
+        L.wg_policy_forward_normalized.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgObsNorm), C.POINTER(WgPolicyRows),
+                                                   _vp, C.c_int64, _vp]
+        L.wg_policy_backward_normalized.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgObsNorm), C.POINTER(WgPolicyRows),
+                                                    _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.wg_obs_moments_workspace.argtypes = [C.POINTER(WgPolicyRows), C.c_int32, C.c_int32]
+        L.wg_obs_moments.argtypes = [C.POINTER(WgPolicyRows), C.c_int32, C.c_float, C.c_int32, _vp, _vp, C.c_double,
+                                     _vp, _vp, _vp]
         L.wg_es_perturb.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp]
         L.wg_es_update.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp, C.c_double, C.c_float, _vp, _vp, _vp, _vp]
         L.wg_es_perturb_diag.argtypes = [C.POINTER(WgEs), _vp, C.c_int32, C.c_int32, _vp]
@@ -179,6 +195,7 @@ def load(path: str | None = None):
         L.wg_fix_launches.restype = C.c_longlong
         L.wg_wt_launches.restype = C.c_longlong
         L.wg_policy_backward_workspace.restype = C.c_int64
+        L.wg_obs_moments_workspace.restype = C.c_int64
         v = L.wg_abi_version()
         if v != ABI_VERSION:
             raise WalkerHipError(f"{p}: ABI version {v}, expected {ABI_VERSION}")

@@ -555,7 +555,9 @@ class BatchedPhysicsEnv:
         action_out [T, N, C] f32 (the actions applied at each step).  Returns {'returns': [N] f32, the rewards added
         in step order up to and including the walker's first done step (or all T); 'lengths': [N] i32, the steps
         counted}.  Walkers keep stepping after done, as in rollout(); there is no auto-reset on this path.
-        Bit-identical to `for t: env.step(policy(env.obs, t))`.
+        Bit-identical to `for t: env.step(policy(env.obs, t))`.  A policy that carries an obs_norm
+        (walker_gym_amd.normalize.ObsNorm) is evaluated on the normalised row inside the kernel (wg_rollout_normalized,
+        here and in rollout_episodes / rollout_stochastic); the rows stored in obs_out stay raw.
 
         ValueError (nothing launched, no silent fallback) for a batch the resident kernel does not take (ragged, M not
         dividing 64, spring_mode or pair_mode set, WG_LEAN=0), with auto-reset enabled, or for a policy that does not
@@ -569,11 +571,22 @@ class BatchedPhysicsEnv:
         returns = torch.empty(N, dtype=torch.float32, device=dv)
         lengths = torch.empty(N, dtype=torch.int32, device=dv)
         pol.return_out, pol.length_out = _lib.ptr(returns), _lib.ptr(lengths)
-        _lib.check(_lib.load().wg_rollout_policy(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
-                                                 C.byref(o), T, self._stream()), "wg_rollout_policy")
+        if policy.obs_norm is not None:
+            self._rollout_normalized(policy, pol, None, o, None, T)
+        else:
+            _lib.check(_lib.load().wg_rollout_policy(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
+                                                     C.byref(o), T, self._stream()), "wg_rollout_policy")
         self._steps_at = -1   # (as rollout(): the env's one-step outputs are not this call's; a refused call ran nothing)
         self._stale = _ROLLOUT_STALE
         return {"returns": returns, "lengths": lengths}
+
+    def _rollout_normalized(self, policy, pol, nz, o, st, T):
+        """The launch of a policy that carries an ObsNorm (wg_rollout_normalized): the mode is the env's auto-reset
+        setting, nz / st are byref'd structs or None."""
+        nm = policy.obs_norm.struct()
+        _lib.check(_lib.load().wg_rollout_normalized(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
+                                                     C.byref(nm), nz, C.byref(o), st, T, self._stream()),
+                   "wg_rollout_normalized")
 
     def _resident_policy(self, entry: str, auto_reset: bool, policy, n_steps, episode_slots, obs_out, reward_out,
                          done_out, action_out, reset_out=None, final_obs_out=None):
@@ -607,6 +620,9 @@ class BatchedPhysicsEnv:
             t = getattr(policy, name)
             if t is not None:
                 require_tensor(t, f"policy.{name}", dv, torch.float32)
+        if policy.obs_norm is not None:
+            require_tensor(policy.obs_norm.mean, "policy.obs_norm.mean", dv, torch.float32, (D,))
+            require_tensor(policy.obs_norm.scale, "policy.obs_norm.scale", dv, torch.float32, (D,))
         for name, t, dt, shape in (("obs_out", obs_out, torch.float32, (T, N, D)),
                                    ("reward_out", reward_out, torch.float32, (T, N)),
                                    ("done_out", done_out, torch.uint8, (T, N)),
@@ -654,8 +670,12 @@ class BatchedPhysicsEnv:
                                  episodes_done=p(res["episodes"]), tail_return=p(res["tail_return"]),
                                  tail_length=p(res["tail_length"]), ep_return=p(res.get("ep_returns")),
                                  ep_length=p(res.get("ep_lengths")), ep_slots=slots)
-        _lib.check(_lib.load().wg_rollout_episodes(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
-                                                   C.byref(o), C.byref(st), T, self._stream()), "wg_rollout_episodes")
+        if policy.obs_norm is not None:
+            self._rollout_normalized(policy, pol, None, o, C.byref(st), T)
+        else:
+            _lib.check(_lib.load().wg_rollout_episodes(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
+                                                       C.byref(o), C.byref(st), T, self._stream()),
+                       "wg_rollout_episodes")
         self._steps_at = -1   # (as rollout_policy(): only after the call was accepted)
         self._stale = _ROLLOUT_STALE
         return res
@@ -728,9 +748,12 @@ class BatchedPhysicsEnv:
                    "lengths": torch.empty(N, dtype=torch.int32, device=dv)}
             pol.return_out, pol.length_out = p(res["returns"]), p(res["lengths"])
             st = None
-        _lib.check(_lib.load().wg_rollout_stochastic(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
-                                                     C.byref(nz), C.byref(o), st, T, self._stream()),
-                   "wg_rollout_stochastic")
+        if policy.obs_norm is not None:
+            self._rollout_normalized(policy, pol, C.byref(nz), o, st, T)
+        else:
+            _lib.check(_lib.load().wg_rollout_stochastic(C.byref(self.batch.struct), C.byref(self._pstruct),
+                                                         C.byref(pol), C.byref(nz), C.byref(o), st, T, self._stream()),
+                       "wg_rollout_stochastic")
         self._steps_at = -1   # (as rollout_policy(): only after the call was accepted)
         self._stale = _ROLLOUT_STALE
         return res

@@ -23,12 +23,27 @@
 //                    RN64(P + a * b) with an exact product is one float64 fma.  Blocks past the shapes compute on
 //                    zero padding and are dropped.
 //   pr_grad_tail     S = the chunks' partials added in order, g = RN32(S), one thread per element.
+//
+// The NM = PrNorm instances of pr_forward and pr_grad_partial (wg_policy_forward_normalized / _backward_normalized)
+// normalise a row where it enters LDS, in pr_stage: the forward, the backward's recompute and both outer products then
+// see xn.  The NM = PrNone instances are the kernels as they were; the normaliser is a trailing kernel argument.
+//
+// and wg_obs_moments: the float64 moments of recorded rows in a fixed order.
+//
+//   obs_moments_partial  a workgroup owns one chunk: its rows are staged in LDS tile by tile, a wave per row with the
+//                        loads of OM_U rows issued before their LDS stores; each lane folds |x| < bound over its
+//                        elements and the wave votes the row's used flag.  Then one thread per column walks the staged
+//                        rows in ascending rho, its two float64 chains in registers (OM_NC columns per thread: 256 *
+//                        OM_NC columns a pass; wider rows walk the chunk again for the next columns).
+//   obs_moments_tail     one workgroup: a thread per column adds the chunks in order into the caller's state, then
+//                        derives mean and scale.
 
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "walker_hip.h"
 #include "walker_internal.h"   // wg_fail, wg_launched: the refusals here go to the library's one error message
@@ -113,6 +128,12 @@ struct PrArgs {
     int32_t Dp, Hq, Hp, Cp;         // LDS row lengths: up4(D + 1), up4(H + 1), up4(H), up4(C) (the forward: D | 1, H | 1)
     int32_t TR;                     // rows per tile
 };
+// wg_obs_norm as a kernel argument; PrNone in its place where nothing is normalised
+struct PrNone {};
+struct PrNorm {
+    const float *mean, *scale;
+    float clip;
+};
 
 // The unit's chain, acc = RN32(acc + RN32(in[i] * w[i * stride + off])) for i ascending, of NU units side by side:
 // every unit's own operations are the contract's, in its order; NU independent chains share the loads of in[i].
@@ -133,10 +154,12 @@ __device__ __forceinline__ void pr_chain(float (&acc)[NU], const float *in, cons
 
 // Rows rho0 .. rho0 + TR of a sequence numbered rho = t * n_seq + (w - w_base), those below rho_end: row r's (t, w) to
 // rt / rw, whether it is evaluated to ok, its x (then 1.0f, then zeros up to Dp) to xs, and, with dy, its dy row (zeros
-// up to Cp) to dys.  A wave per row, lanes along the row.
+// up to Cp) to dys.  A wave per row, lanes along the row.  NM = PrNorm: the row's D values are normalised on their way in,
+//   v = RN32(RN32(x[i] - mean[i]) * scale[i]);  xn[i] = (v < -clip) ? -clip : ((v > clip) ? clip : v)
+template <class NM>
 __device__ __forceinline__ void pr_stage(const PrArgs &a, int64_t rho0, int64_t rho_end, int n_seq, int w_base,
                                          const float *__restrict__ dy, int64_t dy_step, float *xs, float *dys, int *ok,
-                                         int *rt, int *rw) {
+                                         int *rt, int *rw, const NM &nm) {
     const int lane = threadIdx.x & 63;
     for (int r = threadIdx.x >> 6; r < a.TR; r += PR_THREADS / 64) {
         const int64_t rho = rho0 + r;
@@ -150,7 +173,18 @@ __device__ __forceinline__ void pr_stage(const PrArgs &a, int64_t rho0, int64_t 
         }
         if (!on) continue;
         const float *xr = a.x + (int64_t)t * a.x_step + (int64_t)w * a.D;
-        for (int i = lane; i < a.Dp; i += 64) xs[r * a.Dp + i] = i < a.D ? xr[i] : (i == a.D ? 1.0f : 0.0f);
+        if constexpr (std::is_same<NM, PrNorm>::value) {
+            for (int i = lane; i < a.Dp; i += 64) {
+                float v = i == a.D ? 1.0f : 0.0f;
+                if (i < a.D) {
+                    v = __fmul_rn(__fsub_rn(xr[i], nm.mean[i]), nm.scale[i]);
+                    v = (v < -nm.clip) ? -nm.clip : ((v > nm.clip) ? nm.clip : v);   // (a NaN passes through)
+                }
+                xs[r * a.Dp + i] = v;
+            }
+        } else {
+            for (int i = lane; i < a.Dp; i += 64) xs[r * a.Dp + i] = i < a.D ? xr[i] : (i == a.D ? 1.0f : 0.0f);
+        }
         if (dy) {
             const float *dr = dy + (int64_t)t * dy_step + (int64_t)w * a.C;
             for (int c = lane; c < a.Cp; c += 64) dys[r * a.Cp + c] = c < a.C ? dr[c] : 0.0f;
@@ -197,9 +231,9 @@ __device__ __forceinline__ void pr_hidden(const PrArgs &a, const float *xs, cons
 }
 
 // LDS, in floats: [the weights (WLDS)] xs[TR][Dp] hs[TR][Hq] ok[TR] rt[TR] rw[TR]
-template <bool WLDS>
+template <bool WLDS, class NM = PrNone>
 __global__ __launch_bounds__(PR_THREADS) void pr_forward(PrArgs a, int64_t n_tiles, int w_floats, float *__restrict__ y,
-                                                         int64_t y_step) {
+                                                         int64_t y_step, NM nm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *lw1 = lds, *lb1 = lw1 + a.D * a.H, *lw2 = lb1 + (a.b1 ? a.H : 0), *lb2 = lw2 + a.n2 * a.C;
     float *xs = lds + w_floats, *hs = xs + a.TR * a.Dp;
@@ -212,7 +246,7 @@ __global__ __launch_bounds__(PR_THREADS) void pr_forward(PrArgs a, int64_t n_til
     }
     const int64_t rows = (int64_t)a.n_steps * a.N;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        pr_stage(a, tile * a.TR, rows, a.N, 0, nullptr, 0, xs, nullptr, ok, rt, rw);
+        pr_stage(a, tile * a.TR, rows, a.N, 0, nullptr, 0, xs, nullptr, ok, rt, rw, nm);
         __syncthreads();
         if (a.H) {
             pr_hidden<WLDS, false>(a, xs, nullptr, ok, rw, lw1, a.b1 ? lb1 : nullptr, hs, nullptr);
@@ -245,10 +279,10 @@ __global__ __launch_bounds__(PR_THREADS) void pr_forward(PrArgs a, int64_t n_til
 // LDS, in floats: xs[TR][Dp] hs[TR][Hq] dhs[TR][Hp] dys[TR][Cp] ok[TR] rt[TR] rw[TR]
 // Block q of the workgroup's list: q < T1 the layer-1 product (x|1) (x) dh, rows 4 * (q / JT1) .., columns 4 * (q % JT1)
 // ..; then the T2 blocks of (in|1) (x) dy; thread tid owns blocks tid, tid + 256, ...
-template <int NT>
+template <int NT, class NM = PrNone>
 __global__ __launch_bounds__(PR_THREADS) void pr_grad_partial(PrArgs a, const float *__restrict__ dy, int64_t dy_step,
                                                               int32_t chunk_rows, int64_t n_chunks, int32_t T1,
-                                                              double *__restrict__ ws, int32_t K) {
+                                                              double *__restrict__ ws, int32_t K, NM nm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *xs = lds, *hs = xs + a.TR * a.Dp, *dhs = hs + (a.H ? a.TR * a.Hq : 0), *dys = dhs + (a.H ? a.TR * a.Hp : 0);
     int *ok = reinterpret_cast<int *>(dys + a.TR * a.Cp), *rt = ok + a.TR, *rw = rt + a.TR;
@@ -289,7 +323,7 @@ __global__ __launch_bounds__(PR_THREADS) void pr_grad_partial(PrArgs a, const fl
             for (int j = 0; j < 4; j++) acc[u][i][j] = 0.0;
 
     for (int64_t base = lo; base < hi; base += a.TR) {
-        pr_stage(a, base, hi, a.n, g * a.n, dy, dy_step, xs, dys, ok, rt, rw);
+        pr_stage(a, base, hi, a.n, g * a.n, dy, dy_step, xs, dys, ok, rt, rw, nm);
         __syncthreads();
         if (a.H) {
             if (T1) pr_hidden<false, true>(a, xs, dys, ok, rw, nullptr, nullptr, hs, dhs);
@@ -355,6 +389,118 @@ __global__ __launch_bounds__(PR_THREADS) void pr_grad_tail(const double *__restr
     double S = 0.0;
     for (int64_t c = 0; c < n_chunks; c++) S = __dadd_rn(S, p[c * K]);
     dst[g * (hi - lo) + (e - lo)] = (float)S;
+}
+
+// ------------------------------------------------------------------------------------------------ observation moments
+constexpr int OM_ROWS = 64;   // rows per tile, at most
+constexpr int OM_U = 4;       // rows whose loads a wave issues before their LDS stores
+constexpr int OM_NC = 4;      // columns per thread and pass: two float64 chains each
+
+struct OmArgs {
+    const float *x;
+    const uint8_t *mask;
+    int64_t x_step, mask_step, rows;   // rows = n_steps * N
+    int32_t N, D, TR, chunk_rows;
+    float bound;
+};
+
+// LDS, in floats: xs[TR][D] used[TR]
+__global__ __launch_bounds__(PR_THREADS) void obs_moments_partial(OmArgs a, double *__restrict__ ws) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *xs = lds;
+    int *used = reinterpret_cast<int *>(xs + (size_t)a.TR * a.D);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t k = blockIdx.x, lo = k * a.chunk_rows;
+    const int64_t hi = a.rows - lo < a.chunk_rows ? a.rows : lo + a.chunk_rows;
+    double *out = ws + k * (1 + 2 * (int64_t)a.D);
+    for (int cb = 0; cb < a.D; cb += PR_THREADS * OM_NC) {   // (one pass up to 1,024 columns)
+        double p1[OM_NC], p2[OM_NC];
+#pragma unroll
+        for (int u = 0; u < OM_NC; u++) p1[u] = p2[u] = 0.0;
+        double cnt = 0.0;
+        for (int64_t base = lo; base < hi; base += a.TR) {
+            // a wave takes OM_U rows at a time: rows wv * OM_U + u of each group of 4 * OM_U
+            for (int r0 = wv * OM_U; r0 < a.TR; r0 += (PR_THREADS / 64) * OM_U) {
+                const float *xr[OM_U];
+                bool on[OM_U], fin[OM_U];
+#pragma unroll
+                for (int u = 0; u < OM_U; u++) {
+                    const int64_t rho = base + r0 + u;
+                    const bool in = r0 + u < a.TR && rho < hi;
+                    const int64_t t = in ? rho / a.N : 0, w = in ? rho - t * a.N : 0;
+                    on[u] = in && (!a.mask || a.mask[t * a.mask_step + w] != 0);   // (wave-uniform)
+                    xr[u] = a.x + t * a.x_step + w * a.D;
+                    fin[u] = true;
+                }
+                for (int i = lane; i < a.D; i += 64) {
+                    float v[OM_U];
+#pragma unroll
+                    for (int u = 0; u < OM_U; u++) v[u] = on[u] ? xr[u][i] : 0.0f;
+#pragma unroll
+                    for (int u = 0; u < OM_U; u++) {
+                        if (!on[u]) continue;
+                        xs[(size_t)(r0 + u) * a.D + i] = v[u];
+                        fin[u] = fin[u] && fabsf(v[u]) < a.bound;   // (a NaN compares false)
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < OM_U; u++) {
+                    const bool all = __all(fin[u]) != 0;
+                    if (lane == 0 && r0 + u < a.TR) used[r0 + u] = on[u] && all;
+                }
+            }
+            __syncthreads();
+            for (int r = 0; r < a.TR; r++) {
+                if (!used[r]) continue;
+                cnt += 1.0;
+#pragma unroll
+                for (int u = 0; u < OM_NC; u++) {
+                    const int c = cb + (int)threadIdx.x + u * PR_THREADS;
+                    if (c >= a.D) continue;
+                    const double v = (double)xs[(size_t)r * a.D + c];
+                    p1[u] = __dadd_rn(p1[u], v);
+                    p2[u] = fma(v, v, p2[u]);
+                }
+            }
+            __syncthreads();
+        }
+        if (cb == 0 && threadIdx.x == 0) out[0] = cnt;
+#pragma unroll
+        for (int u = 0; u < OM_NC; u++) {
+            const int c = cb + (int)threadIdx.x + u * PR_THREADS;
+            if (c >= a.D) continue;
+            out[1 + c] = p1[u];
+            out[1 + a.D + c] = p2[u];
+        }
+    }
+}
+
+// One workgroup.  state = n, S1[D], S2[D]; mean_out / scale_out NULL: the state alone.
+__global__ __launch_bounds__(PR_THREADS) void obs_moments_tail(const double *__restrict__ ws, int64_t n_chunks, int32_t D,
+                                                               double *__restrict__ state, double eps,
+                                                               float *__restrict__ mean_out,
+                                                               float *__restrict__ scale_out) {
+    const int64_t W = 1 + 2 * (int64_t)D;
+    double n = state[0];
+    for (int64_t k = 0; k < n_chunks; k++) n = __dadd_rn(n, ws[k * W]);   // (every thread: the counts are exact)
+    __syncthreads();   // every thread has read state[0]
+    if (threadIdx.x == 0) state[0] = n;
+    for (int c = threadIdx.x; c < D; c += PR_THREADS) {
+        double s1 = state[1 + c], s2 = state[1 + D + c];
+        for (int64_t k = 0; k < n_chunks; k++) {
+            s1 = __dadd_rn(s1, ws[k * W + 1 + c]);
+            s2 = __dadd_rn(s2, ws[k * W + 1 + D + c]);
+        }
+        state[1 + c] = s1;
+        state[1 + D + c] = s2;
+        if (n > 0.0 && mean_out) {
+            const double m = __ddiv_rn(s1, n);
+            double var = __dsub_rn(__ddiv_rn(s2, n), __dmul_rn(m, m));
+            var = var > 0.0 ? var : 0.0;
+            mean_out[c] = (float)m;
+            scale_out[c] = (float)__ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(var, eps)));
+        }
+    }
 }
 
 // [p, p + bytes) of an array of `elem`-byte elements, [n_steps][N] with `stride` elements between steps
@@ -451,6 +597,144 @@ int pr_backward_plan(PrPlan *pl, int32_t chunk_rows, const char *who, int64_t *n
     return 0;
 }
 
+// wg_obs_norm's own refusals; the normaliser's arrays join the inputs of the aliasing checks.
+int pr_norm_check(const wg_obs_norm *nm, const PrPlan &pl, const char *who, PrBuf *in, int *n_in) {
+    if (!nm) return wg_fail(WG_EINVAL, "%s: null obs norm", who);
+    if (!nm->mean) return wg_fail(WG_EINVAL, "%s: null mean", who);
+    if (!nm->scale) return wg_fail(WG_EINVAL, "%s: null scale", who);
+    if (!(nm->clip > 0.f)) return wg_fail(WG_EINVAL, "%s: clip must be > 0 (+inf allowed)", who);
+    in[(*n_in)++] = {"mean", nm->mean, span_of(nm->mean, 1, pl.a.D, 0, 4)};
+    in[(*n_in)++] = {"scale", nm->scale, span_of(nm->scale, 1, pl.a.D, 0, 4)};
+    return 0;
+}
+
+int policy_forward(const char *who, const wg_policy *pol, const wg_obs_norm *nm, bool norm, const wg_policy_rows *rows,
+                   float *y, int64_t y_step, hipStream_t stream) {
+    PrPlan pl;
+    if (const int rc = pr_check(pol, rows, who, &pl)) return rc;
+    PrArgs &a = pl.a;
+    if (!y) return wg_fail(WG_EINVAL, "%s: null y", who);
+    if (y_step < (int64_t)a.N * a.C)
+        return wg_fail(WG_EINVAL, "%s: y_step %lld < N * act_dim = %lld", who, (long long)y_step, (long long)a.N * a.C);
+    PrBuf in[8];
+    int n_in = pr_inputs(pl, in);
+    if (norm)
+        if (const int rc = pr_norm_check(nm, pl, who, in, &n_in)) return rc;
+    const Span sy = span_of(y, a.n_steps, (int64_t)a.N * a.C, y_step, 4);
+    for (int i = 0; i < n_in; i++)
+        if (overlap(sy, in[i].s)) return wg_fail(WG_EINVAL, "%s: y aliases %s", who, in[i].name);
+    a.Dp = a.D | 1; a.Hq = a.H | 1;                  // odd row lengths: the rows of a wave fall on distinct LDS banks
+    const bool stage = pl.n_sets == 1 && pl.K * 4 <= PR_W_LDS;
+    const int w_floats = stage ? up4((int)pl.K) : 0;
+    const int row = 4 * (a.Dp + (a.H ? a.Hq : 0)) + 12, room = PR_LDS - 4 * w_floats;
+    a.TR = room / row < PR_FWD_ROWS ? room / row : PR_FWD_ROWS;
+    if (a.TR < 1) return wg_fail(WG_ERANGE, "%s: one row needs %d B of LDS (> %d)", who, row, room);
+    const int64_t n_tiles = ((int64_t)a.n_steps * a.N + a.TR - 1) / a.TR;
+    const int64_t cap = stage ? 2048 : 1 << 20;     // staged weights are loaded once per workgroup: few, long-lived
+    const dim3 grid((unsigned)(n_tiles < cap ? n_tiles : cap));
+    const size_t lds = (size_t)4 * w_floats + (size_t)a.TR * row;
+    if (norm) {
+        const PrNorm kn{nm->mean, nm->scale, nm->clip};
+        if (stage) pr_forward<true, PrNorm><<<grid, PR_THREADS, lds, stream>>>(a, n_tiles, w_floats, y, y_step, kn);
+        else pr_forward<false, PrNorm><<<grid, PR_THREADS, lds, stream>>>(a, n_tiles, w_floats, y, y_step, kn);
+    } else {
+        if (stage) pr_forward<true><<<grid, PR_THREADS, lds, stream>>>(a, n_tiles, w_floats, y, y_step, PrNone{});
+        else pr_forward<false><<<grid, PR_THREADS, lds, stream>>>(a, n_tiles, w_floats, y, y_step, PrNone{});
+    }
+    return wg_launched(norm ? "wg_policy_forward_normalized: launch" : "wg_policy_forward: launch");
+}
+
+int policy_backward(const char *who, const wg_policy *pol, const wg_obs_norm *nm, bool norm, const wg_policy_rows *rows,
+                    const float *dy, int64_t dy_step, int32_t chunk_rows, double *workspace, float *g_w1, float *g_b1,
+                    float *g_w2, float *g_b2, hipStream_t stream) {
+    PrPlan pl;
+    int64_t n_chunks;
+    if (const int rc = pr_check(pol, rows, who, &pl)) return rc;
+    PrArgs &a = pl.a;
+    if (!dy) return wg_fail(WG_EINVAL, "%s: null dy", who);
+    if (!workspace) return wg_fail(WG_EINVAL, "%s: null workspace", who);
+    if (dy_step < (int64_t)a.N * a.C)
+        return wg_fail(WG_EINVAL, "%s: dy_step %lld < N * act_dim = %lld", who, (long long)dy_step, (long long)a.N * a.C);
+    if (!g_w1 && !g_b1 && !g_w2 && !g_b2) return wg_fail(WG_EINVAL, "%s: every gradient pointer is null", who);
+    if (!a.H && (g_w1 || g_b1)) return wg_fail(WG_EINVAL, "%s: g_w1 / g_b1 without a hidden layer", who);
+    if (g_b1 && !a.b1) return wg_fail(WG_EINVAL, "%s: g_b1 of a policy without b1", who);
+    if (g_b2 && !a.b2) return wg_fail(WG_EINVAL, "%s: g_b2 of a policy without b2", who);
+    if (const int rc = pr_backward_plan(&pl, chunk_rows, who, &n_chunks)) return rc;
+    PrBuf in[9], out[5];
+    int n_in = pr_inputs(pl, in), n_out = 0;
+    in[n_in++] = {"dy", dy, span_of(dy, a.n_steps, (int64_t)a.N * a.C, dy_step, 4)};
+    if (norm)
+        if (const int rc = pr_norm_check(nm, pl, who, in, &n_in)) return rc;
+    const int64_t G = pl.n_sets;
+    out[n_out++] = {"workspace", workspace, span_of(workspace, 1, G * n_chunks * pl.K, 0, 8)};
+    if (g_w1) out[n_out++] = {"g_w1", g_w1, span_of(g_w1, 1, G * a.D * a.H, 0, 4)};
+    if (g_b1) out[n_out++] = {"g_b1", g_b1, span_of(g_b1, 1, G * a.H, 0, 4)};
+    if (g_w2) out[n_out++] = {"g_w2", g_w2, span_of(g_w2, 1, G * a.n2 * a.C, 0, 4)};
+    if (g_b2) out[n_out++] = {"g_b2", g_b2, span_of(g_b2, 1, G * a.C, 0, 4)};
+    for (int o = 0; o < n_out; o++) {
+        for (int i = 0; i < n_in; i++)
+            if (overlap(out[o].s, in[i].s)) return wg_fail(WG_EINVAL, "%s: %s aliases %s", who, out[o].name, in[i].name);
+        for (int p = 0; p < o; p++)
+            if (overlap(out[o].s, out[p].s)) return wg_fail(WG_EINVAL, "%s: %s aliases %s", who, out[o].name, out[p].name);
+    }
+    const int32_t T1 = (g_w1 || g_b1) ? pl.T1 : 0;     // without them neither dh nor the layer-1 product is computed
+    const int nt = (T1 + pl.T2 + PR_THREADS - 1) / PR_THREADS;
+    const size_t lds = (size_t)a.TR * (4 * (a.Dp + (a.H ? a.Hq + a.Hp : 0) + a.Cp) + 12);
+    const dim3 grid((unsigned)(n_chunks * G));
+    const int32_t K = (int32_t)pl.K;
+    auto go = [&](auto kernel, auto kn) {
+        kernel<<<grid, PR_THREADS, lds, stream>>>(a, dy, dy_step, chunk_rows, n_chunks, T1, workspace, K, kn);
+    };
+    if (norm) {
+        const PrNorm kn{nm->mean, nm->scale, nm->clip};
+        if (nt <= 1) go(pr_grad_partial<1, PrNorm>, kn);
+        else if (nt == 2) go(pr_grad_partial<2, PrNorm>, kn);
+        else if (nt == 3) go(pr_grad_partial<3, PrNorm>, kn);
+        else go(pr_grad_partial<4, PrNorm>, kn);
+    } else {
+        if (nt <= 1) go(pr_grad_partial<1>, PrNone{});
+        else if (nt == 2) go(pr_grad_partial<2>, PrNone{});
+        else if (nt == 3) go(pr_grad_partial<3>, PrNone{});
+        else go(pr_grad_partial<4>, PrNone{});
+    }
+    if (const int rc = wg_launched(norm ? "wg_policy_backward_normalized (partial sums): launch"
+                                        : "wg_policy_backward (partial sums): launch"))
+        return rc;
+    PrGrads o{{g_w1, g_b1, g_w2, g_b2}, {pl.end[0], pl.end[1], pl.end[2], pl.end[3]}};
+    const int64_t total = G * K;
+    pr_grad_tail<<<(unsigned)((total + PR_THREADS - 1) / PR_THREADS), PR_THREADS, 0, stream>>>(workspace, o, K, n_chunks,
+                                                                                             total);
+    return wg_launched(norm ? "wg_policy_backward_normalized (tail): launch" : "wg_policy_backward (tail): launch");
+}
+
+// wg_obs_moments' checks, shared with wg_obs_moments_workspace; fills the kernel's arguments and the chunk count.
+int om_check(const wg_policy_rows *rows, int32_t obs_dim, int32_t chunk_rows, const char *who, OmArgs *a,
+             int64_t *n_chunks) {
+    if (!rows) return wg_fail(WG_EINVAL, "%s: null rows", who);
+    if (!rows->x) return wg_fail(WG_EINVAL, "%s: null x", who);
+    if (obs_dim < 1) return wg_fail(WG_EINVAL, "%s: obs_dim %d < 1", who, obs_dim);
+    if (rows->n_steps < 1) return wg_fail(WG_EINVAL, "%s: n_steps %d < 1", who, rows->n_steps);
+    if (rows->N < 1) return wg_fail(WG_EINVAL, "%s: N %d < 1", who, rows->N);
+    if (chunk_rows < 1) return wg_fail(WG_EINVAL, "%s: chunk_rows %d < 1", who, chunk_rows);
+    const int64_t D = obs_dim;
+    if (rows->x_step < rows->N * D)
+        return wg_fail(WG_EINVAL, "%s: x_step %lld < N * obs_dim = %lld", who, (long long)rows->x_step,
+                       (long long)(rows->N * D));
+    if (rows->mask && rows->mask_step < rows->N)
+        return wg_fail(WG_EINVAL, "%s: mask_step %lld < N = %d", who, (long long)rows->mask_step, rows->N);
+    if ((int64_t)rows->N * D > INT32_MAX) return wg_fail(WG_ERANGE, "%s: a step's rows pass 2^31 elements", who);
+    *a = OmArgs{};
+    a->x = rows->x; a->mask = rows->mask; a->x_step = rows->x_step; a->mask_step = rows->mask_step;
+    a->rows = (int64_t)rows->n_steps * rows->N;
+    a->N = rows->N; a->D = obs_dim; a->chunk_rows = chunk_rows;
+    const int64_t row = 4 * D + 4;
+    a->TR = (int32_t)(PR_LDS / row < OM_ROWS ? PR_LDS / row : OM_ROWS);
+    if (a->TR < 1) return wg_fail(WG_ERANGE, "%s: one row needs %lld B of LDS (> 64 KiB)", who, (long long)row);
+    *n_chunks = (a->rows + chunk_rows - 1) / chunk_rows;
+    if (*n_chunks > INT32_MAX) return wg_fail(WG_ERANGE, "%s: %lld chunks pass 2^31 workgroups", who, (long long)*n_chunks);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -493,31 +777,12 @@ int wg_gae(const float *reward, const float *value, const float *next_value, con
 }
 
 int wg_policy_forward(const wg_policy *pol, const wg_policy_rows *rows, float *y, int64_t y_step, hipStream_t stream) {
-    const char *who = "wg_policy_forward";
-    PrPlan pl;
-    if (const int rc = pr_check(pol, rows, who, &pl)) return rc;
-    PrArgs &a = pl.a;
-    if (!y) return wg_fail(WG_EINVAL, "%s: null y", who);
-    if (y_step < (int64_t)a.N * a.C)
-        return wg_fail(WG_EINVAL, "%s: y_step %lld < N * act_dim = %lld", who, (long long)y_step, (long long)a.N * a.C);
-    PrBuf in[6];
-    const int n_in = pr_inputs(pl, in);
-    const Span sy = span_of(y, a.n_steps, (int64_t)a.N * a.C, y_step, 4);
-    for (int i = 0; i < n_in; i++)
-        if (overlap(sy, in[i].s)) return wg_fail(WG_EINVAL, "%s: y aliases %s", who, in[i].name);
-    a.Dp = a.D | 1; a.Hq = a.H | 1;                  // odd row lengths: the rows of a wave fall on distinct LDS banks
-    const bool stage = pl.n_sets == 1 && pl.K * 4 <= PR_W_LDS;
-    const int w_floats = stage ? up4((int)pl.K) : 0;
-    const int row = 4 * (a.Dp + (a.H ? a.Hq : 0)) + 12, room = PR_LDS - 4 * w_floats;
-    a.TR = room / row < PR_FWD_ROWS ? room / row : PR_FWD_ROWS;
-    if (a.TR < 1) return wg_fail(WG_ERANGE, "%s: one row needs %d B of LDS (> %d)", who, row, room);
-    const int64_t n_tiles = ((int64_t)a.n_steps * a.N + a.TR - 1) / a.TR;
-    const int64_t cap = stage ? 2048 : 1 << 20;     // staged weights are loaded once per workgroup: few, long-lived
-    const dim3 grid((unsigned)(n_tiles < cap ? n_tiles : cap));
-    const size_t lds = (size_t)4 * w_floats + (size_t)a.TR * row;
-    if (stage) pr_forward<true><<<grid, PR_THREADS, lds, stream>>>(a, n_tiles, w_floats, y, y_step);
-    else pr_forward<false><<<grid, PR_THREADS, lds, stream>>>(a, n_tiles, w_floats, y, y_step);
-    return wg_launched("wg_policy_forward: launch");
+    return policy_forward("wg_policy_forward", pol, nullptr, false, rows, y, y_step, stream);
+}
+
+int wg_policy_forward_normalized(const wg_policy *pol, const wg_obs_norm *nm, const wg_policy_rows *rows, float *y,
+                                 int64_t y_step, hipStream_t stream) {
+    return policy_forward("wg_policy_forward_normalized", pol, nm, true, rows, y, y_step, stream);
 }
 
 int64_t wg_policy_backward_workspace(const wg_policy *pol, const wg_policy_rows *rows, int32_t chunk_rows) {
@@ -531,53 +796,57 @@ int64_t wg_policy_backward_workspace(const wg_policy *pol, const wg_policy_rows 
 int wg_policy_backward(const wg_policy *pol, const wg_policy_rows *rows, const float *dy, int64_t dy_step,
                        int32_t chunk_rows, double *workspace, float *g_w1, float *g_b1, float *g_w2, float *g_b2,
                        hipStream_t stream) {
-    const char *who = "wg_policy_backward";
-    PrPlan pl;
+    return policy_backward("wg_policy_backward", pol, nullptr, false, rows, dy, dy_step, chunk_rows, workspace, g_w1, g_b1,
+                           g_w2, g_b2, stream);
+}
+
+int wg_policy_backward_normalized(const wg_policy *pol, const wg_obs_norm *nm, const wg_policy_rows *rows,
+                                  const float *dy, int64_t dy_step, int32_t chunk_rows, double *workspace, float *g_w1,
+                                  float *g_b1, float *g_w2, float *g_b2, hipStream_t stream) {
+    return policy_backward("wg_policy_backward_normalized", pol, nm, true, rows, dy, dy_step, chunk_rows, workspace, g_w1,
+                           g_b1, g_w2, g_b2, stream);
+}
+
+int64_t wg_obs_moments_workspace(const wg_policy_rows *rows, int32_t obs_dim, int32_t chunk_rows) {
+    OmArgs a;
     int64_t n_chunks;
-    if (const int rc = pr_check(pol, rows, who, &pl)) return rc;
-    PrArgs &a = pl.a;
-    if (!dy) return wg_fail(WG_EINVAL, "%s: null dy", who);
+    if (const int rc = om_check(rows, obs_dim, chunk_rows, "wg_obs_moments_workspace", &a, &n_chunks)) return rc;
+    return n_chunks * (1 + 2 * (int64_t)obs_dim);
+}
+
+int wg_obs_moments(const wg_policy_rows *rows, int32_t obs_dim, float bound, int32_t chunk_rows, double *workspace,
+                   double *state, double eps, float *mean_out, float *scale_out, hipStream_t stream) {
+    const char *who = "wg_obs_moments";
+    OmArgs a;
+    int64_t n_chunks;
+    if (const int rc = om_check(rows, obs_dim, chunk_rows, who, &a, &n_chunks)) return rc;
     if (!workspace) return wg_fail(WG_EINVAL, "%s: null workspace", who);
-    if (dy_step < (int64_t)a.N * a.C)
-        return wg_fail(WG_EINVAL, "%s: dy_step %lld < N * act_dim = %lld", who, (long long)dy_step, (long long)a.N * a.C);
-    if (!g_w1 && !g_b1 && !g_w2 && !g_b2) return wg_fail(WG_EINVAL, "%s: every gradient pointer is null", who);
-    if (!a.H && (g_w1 || g_b1)) return wg_fail(WG_EINVAL, "%s: g_w1 / g_b1 without a hidden layer", who);
-    if (g_b1 && !a.b1) return wg_fail(WG_EINVAL, "%s: g_b1 of a policy without b1", who);
-    if (g_b2 && !a.b2) return wg_fail(WG_EINVAL, "%s: g_b2 of a policy without b2", who);
-    if (const int rc = pr_backward_plan(&pl, chunk_rows, who, &n_chunks)) return rc;
-    PrBuf in[7], out[5];
-    int n_in = pr_inputs(pl, in), n_out = 0;
-    in[n_in++] = {"dy", dy, span_of(dy, a.n_steps, (int64_t)a.N * a.C, dy_step, 4)};
-    const int64_t G = pl.n_sets;
-    out[n_out++] = {"workspace", workspace, span_of(workspace, 1, G * n_chunks * pl.K, 0, 8)};
-    if (g_w1) out[n_out++] = {"g_w1", g_w1, span_of(g_w1, 1, G * a.D * a.H, 0, 4)};
-    if (g_b1) out[n_out++] = {"g_b1", g_b1, span_of(g_b1, 1, G * a.H, 0, 4)};
-    if (g_w2) out[n_out++] = {"g_w2", g_w2, span_of(g_w2, 1, G * a.n2 * a.C, 0, 4)};
-    if (g_b2) out[n_out++] = {"g_b2", g_b2, span_of(g_b2, 1, G * a.C, 0, 4)};
+    if (!state) return wg_fail(WG_EINVAL, "%s: null state", who);
+    if (!(bound > 0.f)) return wg_fail(WG_EINVAL, "%s: bound must be > 0 (+inf allowed)", who);
+    if (!(eps >= 0.0)) return wg_fail(WG_EINVAL, "%s: eps must be >= 0", who);
+    if ((mean_out == nullptr) != (scale_out == nullptr))
+        return wg_fail(WG_EINVAL, "%s: mean_out and scale_out go together", who);
+    const int64_t W = 1 + 2 * (int64_t)a.D;
+    PrBuf in[2], out[4];
+    int n_in = 0, n_out = 0;
+    in[n_in++] = {"x", a.x, span_of(a.x, rows->n_steps, (int64_t)a.N * a.D, a.x_step, 4)};
+    if (a.mask) in[n_in++] = {"mask", a.mask, span_of(a.mask, rows->n_steps, a.N, a.mask_step, 1)};
+    out[n_out++] = {"workspace", workspace, span_of(workspace, 1, n_chunks * W, 0, 8)};
+    out[n_out++] = {"state", state, span_of(state, 1, W, 0, 8)};
+    if (mean_out) out[n_out++] = {"mean_out", mean_out, span_of(mean_out, 1, a.D, 0, 4)};
+    if (scale_out) out[n_out++] = {"scale_out", scale_out, span_of(scale_out, 1, a.D, 0, 4)};
     for (int o = 0; o < n_out; o++) {
         for (int i = 0; i < n_in; i++)
             if (overlap(out[o].s, in[i].s)) return wg_fail(WG_EINVAL, "%s: %s aliases %s", who, out[o].name, in[i].name);
         for (int p = 0; p < o; p++)
             if (overlap(out[o].s, out[p].s)) return wg_fail(WG_EINVAL, "%s: %s aliases %s", who, out[o].name, out[p].name);
     }
-    const int32_t T1 = (g_w1 || g_b1) ? pl.T1 : 0;     // without them neither dh nor the layer-1 product is computed
-    const int nt = (T1 + pl.T2 + PR_THREADS - 1) / PR_THREADS;
-    const size_t lds = (size_t)a.TR * (4 * (a.Dp + (a.H ? a.Hq + a.Hp : 0) + a.Cp) + 12);
-    const dim3 grid((unsigned)(n_chunks * G));
-    const int32_t K = (int32_t)pl.K;
-    auto go = [&](auto kernel) {
-        kernel<<<grid, PR_THREADS, lds, stream>>>(a, dy, dy_step, chunk_rows, n_chunks, T1, workspace, K);
-    };
-    if (nt <= 1) go(pr_grad_partial<1>);
-    else if (nt == 2) go(pr_grad_partial<2>);
-    else if (nt == 3) go(pr_grad_partial<3>);
-    else go(pr_grad_partial<4>);
-    if (const int rc = wg_launched("wg_policy_backward (partial sums): launch")) return rc;
-    PrGrads o{{g_w1, g_b1, g_w2, g_b2}, {pl.end[0], pl.end[1], pl.end[2], pl.end[3]}};
-    const int64_t total = G * K;
-    pr_grad_tail<<<(unsigned)((total + PR_THREADS - 1) / PR_THREADS), PR_THREADS, 0, stream>>>(workspace, o, K, n_chunks,
-                                                                                             total);
-    return wg_launched("wg_policy_backward (tail): launch");
+    a.bound = bound;
+    const size_t lds = (size_t)a.TR * (4 * (size_t)a.D + 4);
+    obs_moments_partial<<<(unsigned)n_chunks, PR_THREADS, lds, stream>>>(a, workspace);
+    if (const int rc = wg_launched("wg_obs_moments (partial sums): launch")) return rc;
+    obs_moments_tail<<<1, PR_THREADS, 0, stream>>>(workspace, n_chunks, a.D, state, eps, mean_out, scale_out);
+    return wg_launched("wg_obs_moments (tail): launch");
 }
 
 }  // extern "C"

@@ -3002,6 +3002,13 @@ struct KNoise {
     uint32_t step_base, walker_base;
 };
 
+// The observation normaliser of wg_rollout_normalized (wg_obs_norm): the ON instances of walker_rollout_policy take it as
+// one more trailing kernel argument (the other instances take the empty KNoReset).
+struct KObsNorm {
+    const float *mean, *scale;     // [D] each, shared by all parameter sets; read through L2
+    float clip;
+};
+
 // One unit of a layer, the contract's chain: acc = bias; acc = RN32(acc + RN32(x[i] * w[i][j])) for i ascending, the
 // multiply and the add separate roundings (no FMA).  x: the walker's input vector in LDS (the same address in every lane
 // of the walker: a broadcast); w: column j of the set's [n][stride] matrix.
@@ -3062,11 +3069,14 @@ __device__ __forceinline__ void policy_unit2(const float *x, const float *__rest
 // NZ = KNoise (wg_rollout_stochastic): the lane that owns output unit j adds RN32(sigma[set][j] * aeps(seed, step_base + s,
 // walker_base + w, j)) to the unit's chain value before the clip, its own Philox call, and stores the raw action and the
 // variate beside act_dst; s is the call's step.  NZ = KNoReset: none of that is compiled.
-template <bool IN3D, int WS = 4, class NZ = KNoReset>
+// NM = KObsNorm (wg_rollout_normalized): once the rows stand in the slice, each walker's mass lanes rewrite their own row
+// in place, lane q taking elements q, q + M, ...: xn = clip(RN32(RN32(x - mean) * scale)), and the units run on xn.  The
+// slice is the policy's private copy (lean_compute stores the step's rows itself): the stored rows stay raw.
+template <bool IN3D, int WS = 4, class NZ = KNoReset, class NM = KNoReset>
 __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &kp, const KPolicy &pol, const LeanGeo &lg,
                                              char *smem, char *sl, const LeanTile &t, const float *p3, const float *v3,
                                              const LeanPolOut &ps, float x, float *act_dst, const NZ &nz = NZ{},
-                                             int s = 0) {
+                                             int s = 0, const NM &nm = NM{}) {
     const int M = b.M, D = pol.D, H = pol.H, C = pol.C;
     float *row = reinterpret_cast<float *>(sl + pol.off_row);
     float *hid = reinterpret_cast<float *>(sl + pol.off_h);
@@ -3075,6 +3085,17 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
                         v3[0], v3[1], v3[2], ps.ax, ps.ay, ps.az, ps.sx, ps.sy, ps.sz, ps.sx * lg.invM, ps.sy * lg.invM,
                         ps.sz * lg.invM, x);
     wave_sync();
+    if constexpr (std::is_same<NM, KObsNorm>::value) {
+        if (t.is_mass) {
+            float *xr = row + t.wl * D;
+            const float lim = nm.clip;
+            for (int i = t.q; i < D; i += M) {
+                const float v = __fmul_rn(__fsub_rn(xr[i], nm.mean[i]), nm.scale[i]);
+                xr[i] = (v < -lim) ? -lim : ((v > lim) ? lim : v);   // (a NaN passes through)
+            }
+        }
+        wave_sync();
+    }
     // the walker's parameter set, from its LDS record (a register carried across the step would spill)
     const uint32_t gset = t.is_mass ? reinterpret_cast<const uint32_t *>(sl + pol.off_w)[WS * t.wl + 3] : 0u;
     const float *xin = row + t.wl * D;   // (read by the tile's mass lanes only: t.wl < t.nw)
@@ -3140,14 +3161,17 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
 // accounting of wg_episode_stats, stores an ep_return / ep_length slot when an episode ends, the sums after the last step.
 // NZ (wg_rollout_stochastic): seeded action noise in the policy's output layer (lean_policy), in either mode; dead code in
 // the NZ = false instances, whose trailing argument is the empty KNoReset.
-template <bool IN3D, int NE, bool E8, bool AR = false, bool NZ = false>
+// ON (wg_rollout_normalized): the observation normaliser in front of the policy's layers (lean_policy), in every mode,
+// carried exactly as NZ is.
+template <bool IN3D, int NE, bool E8, bool AR = false, bool NZ = false, bool ON = false>
 // (register budget: one wave per SIMD fewer than walker_rollout_lean.  The LDS slice with the rows already holds the
 // canonical walker to 4 waves per SIMD, the NE 8 shapes to 2, and the latency-bound NE 1 batches run one)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3 : 4))) void walker_rollout_policy(
     wg_batch b, KParams kp, KPolicy pol, KOut o, int n_steps, LeanGeo lg,
     typename std::conditional<AR, KReset, KNoReset>::type ar,
     typename std::conditional<AR, wg_episode_stats, KNoReset>::type st,
-    typename std::conditional<NZ, KNoise, KNoReset>::type nz) {
+    typename std::conditional<NZ, KNoise, KNoReset>::type nz,
+    typename std::conditional<ON, KObsNorm, KNoReset>::type nm) {
     constexpr int WS = AR ? 8 : 4;   // LDS words per walker
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -3210,7 +3234,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
         LeanTile ts = lean_tile_of(b, nullptr, pol.C, lg, tile, ln);
         ts.acts = ts.is_mus && ts.mu_ua < pol.C;
         float *const act_dst = pol.action_out ? pol.action_out + (size_t)s * (size_t)pol.action_out_step : nullptr;
-        if constexpr (NZ) L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst, nz, s);
+        if constexpr (ON) L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst, nz, s, nm);
+        else if constexpr (NZ) L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst, nz, s);
         else L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst);
         WG_KOUT_AT(os, o, s);
         WG_PIN_STATIC(L, NE, E8)
@@ -3701,6 +3726,12 @@ int wg_rollout_episodes(const wg_batch *b, const wg_params *p, const wg_policy *
 int wg_rollout_stochastic(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_action_noise *nz,
                           const wg_outputs *o, const wg_episode_stats *st, int32_t n_steps, hipStream_t stream) {
     return rollout_policy(b, p, pol, o, n_steps, stream, p && p->auto_reset != 0, st, true, nz);
+}
+
+int wg_rollout_normalized(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_obs_norm *nm,
+                          const wg_action_noise *nz, const wg_outputs *o, const wg_episode_stats *st, int32_t n_steps,
+                          hipStream_t stream) {
+    return rollout_policy(b, p, pol, o, n_steps, stream, p && p->auto_reset != 0, st, nz != nullptr, nz, true, nm);
 }
 
 int wg_run_ranges(const wg_range *ranges, int32_t n, const wg_params *p, const float *action, int32_t action_cols,

@@ -409,14 +409,18 @@ int obs_row_len(const wg_batch *b, const wg_params *p) {
 // episodes (wg_rollout_episodes): the AR instances, with auto-reset's own checks in place of the auto_reset refusal, the
 // accounting of `st`, and eight words per walker in the slice instead of four.
 // stochastic (wg_rollout_stochastic): either mode, chosen by p->auto_reset, with the NZ instances and the checks of `nz`.
+// normalized (wg_rollout_normalized): either mode likewise, with or without the noise, the ON instances and the checks of
+// `nm`.
 int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o, int32_t n_steps,
                    hipStream_t stream, bool episodes = false, const wg_episode_stats *st = nullptr,
-                   bool stochastic = false, const wg_action_noise *nz = nullptr) {
-    const char *fn = stochastic ? "wg_rollout_stochastic" : episodes ? "wg_rollout_episodes" : "wg_rollout_policy";
+                   bool stochastic = false, const wg_action_noise *nz = nullptr, bool normalized = false,
+                   const wg_obs_norm *nm = nullptr) {
+    const char *fn = normalized ? "wg_rollout_normalized"
+                     : stochastic ? "wg_rollout_stochastic" : episodes ? "wg_rollout_episodes" : "wg_rollout_policy";
     int rc = validate(b);
     if (rc) return rc;
     if (!p) return wg_fail(WG_EINVAL, "null params");
-    if (stochastic && !episodes && st)
+    if ((stochastic || normalized) && !episodes && st)
         return wg_fail(WG_EINVAL, "%s: episode stats with auto_reset 0 (st must be NULL without episode roll-over)", fn);
     if (!pol) return wg_fail(WG_EINVAL, "%s: null policy", fn);
     if (!pol->w2) return wg_fail(WG_EINVAL, "%s: null w2", fn);
@@ -461,6 +465,12 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
             return wg_fail(WG_EINVAL, "%s: step_base %u + n_steps %d passes 2^32", fn, nz->step_base, n_steps);
         if ((uint64_t)nz->walker_base + (uint64_t)b->N > (1ull << 32))
             return wg_fail(WG_EINVAL, "%s: walker_base %u + N %d passes 2^32", fn, nz->walker_base, b->N);
+    }
+    if (normalized) {
+        if (!nm) return wg_fail(WG_EINVAL, "%s: null obs norm", fn);
+        if (!nm->mean) return wg_fail(WG_EINVAL, "%s: null mean", fn);
+        if (!nm->scale) return wg_fail(WG_EINVAL, "%s: null scale", fn);
+        if (!(nm->clip > 0.f)) return wg_fail(WG_EINVAL, "%s: clip must be > 0 (+inf allowed)", fn);
     }
     if ((rc = check_integrator(p)) || (rc = check_muscle_bounds(b)) || (rc = check_discrete(b, p))) return rc;
     wg_outputs out = o ? *o : wg_outputs{};
@@ -513,18 +523,28 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
     if (stochastic)
         kn = KNoise{nz->sigma, nz->raw_out, nz->eps_out, nz->raw_out_step, nz->eps_out_step,
                     (uint32_t)(nz->seed & 0xffffffffu), (uint32_t)(nz->seed >> 32), nz->step_base, nz->walker_base};
+    const KObsNorm kon = normalized ? KObsNorm{nm->mean, nm->scale, nm->clip} : KObsNorm{};
     with_instance(p->in3d != 0, ne, use_edge8(b, lg), [&](auto d3, auto n, auto c8) {
         constexpr bool D3 = decltype(d3)::value, E8 = decltype(c8)::value;
         constexpr int NE = decltype(n)::value;
-        auto go = [&](auto kernel, const auto &reset, const auto &stats, const auto &noise) {
-            hipLaunchKernelGGL(kernel, grid, block, lds, stream, *b, kp, kpol, kout(out), n_steps, lg, reset, stats, noise);
+        auto go = [&](auto kernel, const auto &reset, const auto &stats, const auto &noise, const auto &norm) {
+            hipLaunchKernelGGL(kernel, grid, block, lds, stream, *b, kp, kpol, kout(out), n_steps, lg, reset, stats, noise,
+                               norm);
         };
-        if (stochastic) {
-            if (episodes) go(walker_rollout_policy<D3, NE, E8, true, true>, ar, *st, kn);
-            else go(walker_rollout_policy<D3, NE, E8, false, true>, KNoReset{}, KNoReset{}, kn);
+        if (normalized) {
+            if (stochastic) {
+                if (episodes) go(walker_rollout_policy<D3, NE, E8, true, true, true>, ar, *st, kn, kon);
+                else go(walker_rollout_policy<D3, NE, E8, false, true, true>, KNoReset{}, KNoReset{}, kn, kon);
+            } else {
+                if (episodes) go(walker_rollout_policy<D3, NE, E8, true, false, true>, ar, *st, KNoReset{}, kon);
+                else go(walker_rollout_policy<D3, NE, E8, false, false, true>, KNoReset{}, KNoReset{}, KNoReset{}, kon);
+            }
+        } else if (stochastic) {
+            if (episodes) go(walker_rollout_policy<D3, NE, E8, true, true>, ar, *st, kn, KNoReset{});
+            else go(walker_rollout_policy<D3, NE, E8, false, true>, KNoReset{}, KNoReset{}, kn, KNoReset{});
         } else {
-            if (episodes) go(walker_rollout_policy<D3, NE, E8, true>, ar, *st, KNoReset{});
-            else go(walker_rollout_policy<D3, NE, E8>, KNoReset{}, KNoReset{}, KNoReset{});
+            if (episodes) go(walker_rollout_policy<D3, NE, E8, true>, ar, *st, KNoReset{}, KNoReset{});
+            else go(walker_rollout_policy<D3, NE, E8>, KNoReset{}, KNoReset{}, KNoReset{}, KNoReset{});
         }
     });
     return wg_launched("launch");

@@ -189,11 +189,13 @@ def split_theta(flat, D: int, H: int, Cc: int, biases: bool) -> dict:
 class EvolutionStrategy:
     """Antithetic evolution strategies with centred-rank utilities over an MLPPolicy of `population` parameter sets on
     env's device.  ask() -> MLPPolicy of the generation's candidates; tell(fitness) -> the update; generation_step() a
-    whole generation from the state captured at construction."""
+    whole generation from the state captured at construction.  obs_norm (walker_gym_amd.normalize.ObsNorm): the
+    observation normaliser every candidate and mean_policy() evaluate; the caller updates it (generation_step's obs_out
+    records the rows), the trainer carries it in its state_dict."""
 
     def __init__(self, env, hidden: int = 0, act_dim: Optional[int] = None, biases: bool = True,
                  population: Optional[int] = None, sigma: float = 0.05, lr: float = 0.05, seed: int = 0,
-                 act_limit: float = 1.0, theta0=None):
+                 act_limit: float = 1.0, theta0=None, obs_norm=None):
         import torch
         from .policy import MLPPolicy
         self.env = env
@@ -232,7 +234,9 @@ class EvolutionStrategy:
         w1 = e(G, D, H) if H else None
         b1 = e(G, H) if H and self.biases else None
         b2 = e(G, Cc) if self.biases else None
-        self.policy = MLPPolicy(e(G, n2, Cc), b2, w1, b1, act_limit=act_limit)
+        # obs_norm (walker_gym_amd.normalize.ObsNorm, shared by every candidate and by mean_policy(); its owner updates it)
+        self.obs_norm = obs_norm
+        self.policy = MLPPolicy(e(G, n2, Cc), b2, w1, b1, act_limit=act_limit, obs_norm=obs_norm)
         self.act_limit = self.policy.act_limit
         self.n_pairs = G // 2
         self._work = torch.empty((-(-self.n_pairs // CHUNK), self.K), dtype=torch.float64, device=dv)
@@ -289,9 +293,10 @@ class EvolutionStrategy:
         tot = res["return_sum"].double() + res["tail_return"].double()
         return (tot.view(self.G, wps).sum(dim=1) / (wps * int(n_steps))).to(torch.float32)
 
-    def generation_step(self, n_steps: int, restore: bool = True) -> dict:
+    def generation_step(self, n_steps: int, restore: bool = True, obs_out=None) -> dict:
         """One generation: (restore the state captured at construction,) ask, one closed-loop rollout of every
-        candidate (rollout_policy, or rollout_episodes when the env has auto-reset on), tell.  ValueError for what the
+        candidate (rollout_policy, or rollout_episodes when the env has auto-reset on; obs_out [T, N, D] records its rows,
+        raw, for an ObsNorm.update before the next generation), tell.  ValueError for what the
         rollout refuses (resident batches only).  Returns the generation's number, 'fitness' [G] f32, 'grad' [K] f32
         and the fitness statistics 'fitness_mean' / 'fitness_max' / 'fitness_min' over the candidates that did not
         diverge, as 0-d device tensors (nothing here waits for the device)."""
@@ -300,7 +305,8 @@ class EvolutionStrategy:
         if restore:
             env.batch.load_state_dict(self._state0)
         pol = self.ask()
-        res = env.rollout_episodes(pol, n_steps) if env._ar_mode else env.rollout_policy(pol, n_steps)
+        res = (env.rollout_episodes(pol, n_steps, obs_out=obs_out) if env._ar_mode
+               else env.rollout_policy(pol, n_steps, obs_out=obs_out))
         fit = self.fitness_of(res, n_steps)
         out = self.tell(fit)
         nan = torch.isnan(fit)
@@ -313,11 +319,14 @@ class EvolutionStrategy:
         """The G = 1 policy of theta (a copy)."""
         from .policy import MLPPolicy
         seg = split_theta(self.theta.clone(), self.D, self.H, self.C, self.biases)
-        return MLPPolicy(seg["w2"], seg["b2"], seg["w1"], seg["b1"], act_limit=self.act_limit)
+        return MLPPolicy(seg["w2"], seg["b2"], seg["w1"], seg["b1"], act_limit=self.act_limit, obs_norm=self.obs_norm)
 
     def state_dict(self) -> dict:
-        return {"theta": self.theta.detach().cpu().clone(), "seed": self.seed, "generation": self.generation,
-                "sigma": self.sigma, "lr": self.lr}
+        sd = {"theta": self.theta.detach().cpu().clone(), "seed": self.seed, "generation": self.generation,
+              "sigma": self.sigma, "lr": self.lr}
+        if self.obs_norm is not None:
+            sd["obs_norm"] = self.obs_norm.state_dict()
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         import torch
@@ -327,6 +336,8 @@ class EvolutionStrategy:
         self.theta.copy_(t.to(self.theta.device))
         self.seed, self.generation = int(sd["seed"]), int(sd["generation"])
         self.sigma, self.lr = float(np.float32(sd["sigma"])), float(np.float32(sd["lr"]))
+        if self.obs_norm is not None and "obs_norm" in sd:
+            self.obs_norm.load_state_dict(sd["obs_norm"])
 
 
 class AdaptiveEvolutionStrategy(EvolutionStrategy):
@@ -338,7 +349,7 @@ class AdaptiveEvolutionStrategy(EvolutionStrategy):
     def __init__(self, env, hidden: int = 0, act_dim: Optional[int] = None, biases: bool = True,
                  population: Optional[int] = None, sigma=0.05, lr: float = 0.05, seed: int = 0,
                  act_limit: float = 1.0, theta0=None, sigma_lr: float = 0.1, sigma_max_change: float = 0.2,
-                 sigma_min: float = 1e-8, sigma_max: float = float("inf")):
+                 sigma_min: float = 1e-8, sigma_max: float = float("inf"), obs_norm=None):
         import torch
         s0 = np.asarray(sigma.detach().cpu() if hasattr(sigma, "detach") else sigma, dtype=np.float32)
         if s0.ndim > 1:
@@ -352,7 +363,8 @@ class AdaptiveEvolutionStrategy(EvolutionStrategy):
         if not (np.isfinite(sigma_min) and sigma_min > 0) or not sigma_max >= sigma_min:
             raise ValueError(f"need 0 < sigma_min <= sigma_max, got {sigma_min!r}, {sigma_max!r}")
         super().__init__(env, hidden=hidden, act_dim=act_dim, biases=biases, population=population,
-                         sigma=float(s0.reshape(-1)[0]), lr=lr, seed=seed, act_limit=act_limit, theta0=theta0)
+                         sigma=float(s0.reshape(-1)[0]), lr=lr, seed=seed, act_limit=act_limit, theta0=theta0,
+                         obs_norm=obs_norm)
         if s0.ndim == 1 and s0.shape[0] != self.K:
             raise ValueError(f"sigma has {s0.shape[0]} entries, expected a scalar or ({self.K},)")
         self.sigma = 0.0                 # wg_es's scalar: the _diag calls do not read it
@@ -391,10 +403,10 @@ class AdaptiveEvolutionStrategy(EvolutionStrategy):
         self._told = {"grad": self._grad.clone(), "grad_sigma": self._grad_sigma.clone()}
         return self._told
 
-    def generation_step(self, n_steps: int, restore: bool = True) -> dict:
+    def generation_step(self, n_steps: int, restore: bool = True, obs_out=None) -> dict:
         """EvolutionStrategy.generation_step's dict plus 'grad_sigma' [K] f32 and the 0-d device tensors 'sigma_mean' /
         'sigma_min' / 'sigma_max' of sigma_vec after the update (nothing here waits for the device)."""
-        out = super().generation_step(n_steps, restore)
+        out = super().generation_step(n_steps, restore, obs_out)
         out["grad_sigma"] = self._told["grad_sigma"]
         out["sigma_mean"] = self.sigma_vec.double().mean()
         out["sigma_min"], out["sigma_max"] = self.sigma_vec.min(), self.sigma_vec.max()

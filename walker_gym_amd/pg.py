@@ -25,7 +25,9 @@ exact products in a fixed order:
   S[e] = +0.0; k ascending: S[e] = RN64(S[e] + P_k[e]);   grad[e] = RN32(S[e])
 with (a, b) = (in[i], dy[c]) for w2[i][c], (1, dy[c]) for b2[c], (x[i], dh[j]) for w1[i][j], (1, dh[j]) for b1[j].
 policy_rows_numpy and policy_grad_numpy restate both on the host, bit for bit.  There is no gradient with respect to
-obs.
+obs.  A policy that carries an obs_norm (walker_gym_amd.normalize) is evaluated on the normalised rows xn in all of
+these (wg_policy_forward_normalized / wg_policy_backward_normalized): xn[i] takes x[i]'s place as the left factor, and
+there is no gradient with respect to mean or scale.
 """
 from __future__ import annotations
 
@@ -65,7 +67,8 @@ def stochastic_forward_numpy(policy, obs_rows, sigma, seed: int, t: int, walker_
     float32 [n, C] each: the raw action, the clipped action, the variate."""
     x = np.ascontiguousarray(obs_rows, dtype=np.float32)
     n = x.shape[0]
-    inf = policy.__class__(policy.w2, policy.b2, policy.w1, policy.b1, act_limit=float("inf"))
+    inf = policy.__class__(policy.w2, policy.b2, policy.w1, policy.b1, act_limit=float("inf"),
+                           obs_norm=getattr(policy, "obs_norm", None))
     y = inf.forward_numpy(x, first_walker, n_walkers_total)            # the chain value: no clip at L = inf
     sets = policy._sets(n, first_walker, n_walkers_total)
     sg = np.asarray(sigma.detach().cpu().numpy() if hasattr(sigma, "detach") else sigma, dtype=np.float32)
@@ -123,7 +126,8 @@ def policy_rows_numpy(policy, x, mask=None):
     Returns float32 [T, N, C]; the rows mask skips (mask [T, N], 0 = skipped) are zero."""
     x, on, _ = _rows_arrays(policy, x, mask)
     T, N, _ = x.shape
-    inf = policy.__class__(policy.w2, policy.b2, policy.w1, policy.b1, act_limit=float("inf"))
+    inf = policy.__class__(policy.w2, policy.b2, policy.w1, policy.b1, act_limit=float("inf"),
+                           obs_norm=getattr(policy, "obs_norm", None))
     y = np.zeros((T, N, policy.C), np.float32)
     for t in range(T):
         y[t] = np.where(on[t][:, None], inf.forward_numpy(x[t], 0, N), np.float32(0.0))
@@ -135,6 +139,8 @@ def policy_grad_numpy(policy, x, dy, mask=None, chunk_rows: int = 256):
     docstring).  x [T, N, D], dy [T, N, C], mask [T, N] or None.  Returns (g_w1, g_b1, g_w2, g_b2), float32 arrays
     shaped like the policy's tensors ([G, D, H], [G, H], [G, n2, C], [G, C]), None for what the policy does not have."""
     x, on, sets = _rows_arrays(policy, x, mask)
+    if getattr(policy, "obs_norm", None) is not None:
+        x = policy.obs_norm.normalize_numpy(x)      # the layers and both outer products see xn
     T, N, D = x.shape
     G, H, Cc = policy.G, policy.H, policy.C
     dy = np.ascontiguousarray(dy, dtype=np.float32)
@@ -187,14 +193,20 @@ def policy_grad_numpy(policy, x, dy, mask=None, chunk_rows: int = 256):
 # ---------------------------------------------------------------------------------------------------- the kernels
 def _rows_struct(policy, obs, mask, who):
     """(wg_policy, wg_policy_rows, T, N, the 3-D views kept alive) of obs [T, N, D] / [R, D] and mask [T, N] / [R]."""
+    rows, T, N, o3, m3, flat = _rows_of(policy.D, policy.device, obs, mask, who)
+    return policy.struct(N), rows, T, N, o3, m3, flat
+
+
+def _rows_of(width, device, obs, mask, who):
+    """_rows_struct without the policy: rows of `width` values on `device`."""
     import torch
     if not isinstance(obs, torch.Tensor) or obs.dim() not in (2, 3) or obs.dtype != torch.float32:
         raise ValueError(f"{who}: obs must be a float32 device tensor [T, N, D] or [R, D]")
     flat = obs.dim() == 2
     o3 = obs[None] if flat else obs
     T, N, D = (int(v) for v in o3.shape)
-    if D != policy.D or obs.device != policy.device:
-        raise ValueError(f"{who}: obs is [.., {D}] on {obs.device}, the policy takes {policy.D} values on {policy.device}")
+    if D != width or obs.device != device:
+        raise ValueError(f"{who}: obs is [.., {D}] on {obs.device}, the policy takes {width} values on {device}")
     if T < 1 or N < 1:
         raise ValueError(f"{who}: no rows")
     if o3.stride(2) != 1 or o3.stride(1) != D or (T > 1 and o3.stride(0) < N * D):
@@ -210,7 +222,16 @@ def _rows_struct(policy, obs, mask, who):
             raise ValueError(f"{who}: mask must be uint8 / bool {(T, N)} with only its step dimension strided")
     rows = _lib.WgPolicyRows(x=_lib.ptr(o3), x_step=o3.stride(0) if T > 1 else N * D, mask=_lib.ptr(m3),
                              mask_step=(m3.stride(0) if T > 1 else N) if m3 is not None else 0, n_steps=T, N=N)
-    return policy.struct(N), rows, T, N, o3, m3, flat
+    return rows, T, N, o3, m3, flat
+
+
+def _obs_norm_of(policy, who):
+    """policy.obs_norm, checked against the policy (None: a plain policy)."""
+    nm = getattr(policy, "obs_norm", None)
+    if nm is not None and (nm.D != policy.D or nm.device != policy.device):
+        raise ValueError(f"{who}: obs_norm is [{nm.D}] on {nm.device}, the policy takes {policy.D} values on "
+                         f"{policy.device}")
+    return nm
 
 
 def default_chunk_rows(T: int, n: int) -> int:
@@ -234,8 +255,13 @@ def policy_rows_forward(policy, obs, mask=None, y_out=None):
                 or y.stride(2) != 1 or y.stride(1) != Cc):
             raise ValueError(f"policy_rows_forward: y_out must be float32 {(T, N, Cc)} with only its step dimension strided")
     stream = torch.cuda.current_stream(dv).cuda_stream
-    _lib.check(_lib.load().wg_policy_forward(pol, rows, _lib.ptr(y), y.stride(0) if T > 1 else N * Cc, stream),
-               "wg_policy_forward")
+    nm, L = _obs_norm_of(policy, "policy_rows_forward"), _lib.load()
+    if nm is None:
+        _lib.check(L.wg_policy_forward(pol, rows, _lib.ptr(y), y.stride(0) if T > 1 else N * Cc, stream),
+                   "wg_policy_forward")
+    else:
+        _lib.check(L.wg_policy_forward_normalized(pol, nm.struct(), rows, _lib.ptr(y), y.stride(0) if T > 1 else N * Cc,
+                                                  stream), "wg_policy_forward_normalized")
     return y[0] if flat else y
 
 
@@ -303,9 +329,13 @@ def policy_rows_backward(policy, obs, dy, mask=None, chunk_rows: Optional[int] =
     grads = [torch.empty_like(t) if (k and t is not None) else None
              for t, k in zip((policy.w1, policy.b1, policy.w2, policy.b2), want)]
     p = _lib.ptr
-    _lib.check(L.wg_policy_backward(pol, rows, p(d3), d3.stride(0) if T > 1 else N * policy.C, chunk, p(ws),
-                                    *(p(g) for g in grads), torch.cuda.current_stream(dv).cuda_stream),
-               "wg_policy_backward")
+    nm = _obs_norm_of(policy, "policy_rows_backward")
+    tail = (p(d3), d3.stride(0) if T > 1 else N * policy.C, chunk, p(ws), *(p(g) for g in grads),
+            torch.cuda.current_stream(dv).cuda_stream)
+    if nm is None:
+        _lib.check(L.wg_policy_backward(pol, rows, *tail), "wg_policy_backward")
+    else:
+        _lib.check(L.wg_policy_backward_normalized(pol, nm.struct(), rows, *tail), "wg_policy_backward_normalized")
     return tuple(grads)
 
 

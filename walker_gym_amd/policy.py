@@ -7,6 +7,9 @@ The arithmetic is the contract, float32 with separately rounded multiply and add
   hidden:  h = (z > 0) ? z : +0.0                       (a NaN becomes 0)
   output:  a = (y < -L) ? -L : ((y > L) ? L : y)        (L = act_limit > 0, inf allowed; a NaN passes through)
 Weights are input-major (y = x @ w): w1 [G, D, H], b1 [G, H] (only with a hidden layer), w2 [G, H or D, C], b2 [G, C].
+With obs_norm (a walker_gym_amd.normalize.ObsNorm, wg_obs_norm in the header) the layers run on the normalised row
+  input:   v = RN32(RN32(x[i] - mean[i]) * scale[i]);  xn[i] = (v < -clip) ? -clip : ((v > clip) ? clip : v)
+in all three and in the kernels; mean / scale [D] are shared by every parameter set and read at every call.
 G parameter sets: of N walkers, walker w uses set w // (N // G) (G = 1 shared, G = N one candidate per walker).
 With G > 1 the torch restatement must know which walkers its rows are: for_rows(first_walker, N) / for_row_index(rows,
 N) bind it (BatchedPhysicsEnv.policy_loop does so for each of its walker ranges); unbound, __call__ raises, it never
@@ -79,7 +82,7 @@ class MLPPolicy:
     differentiates with respect to exactly those, so an optimizer over the same parameters updates the policy the
     rollout kernel reads, with no copy in between."""
 
-    def __init__(self, w2, b2=None, w1=None, b1=None, act_limit: float = 1.0):
+    def __init__(self, w2, b2=None, w1=None, b1=None, act_limit: float = 1.0, obs_norm=None):
         w2 = _as_tensor(w2, "w2")
         if w2.dim() == 2:
             w2 = w2[None]
@@ -125,6 +128,11 @@ class MLPPolicy:
         self.G, self.C = int(G), int(Cc)
         self.H = 0 if w1 is None else int(n2)
         self.D = int(n2) if w1 is None else int(w1.shape[1])
+        # walker_gym_amd.normalize.ObsNorm, kept by identity: its mean / scale are updated in place.  Every evaluator
+        # runs the layers on xn = clip((x - mean) * scale); None: the plain policy
+        if obs_norm is not None and (obs_norm.D != self.D or obs_norm.device != dev):
+            raise ValueError(f"obs_norm is [{obs_norm.D}] on {obs_norm.device}, the policy takes {self.D} values on {dev}")
+        self.obs_norm = obs_norm
 
     @property
     def device(self):
@@ -140,7 +148,8 @@ class MLPPolicy:
 
     def to(self, device) -> "MLPPolicy":
         mv = lambda t: None if t is None else t.to(device)
-        return MLPPolicy(mv(self.w2), mv(self.b2), mv(self.w1), mv(self.b1), self.act_limit)
+        return MLPPolicy(mv(self.w2), mv(self.b2), mv(self.w1), mv(self.b1), self.act_limit,
+                         None if self.obs_norm is None else self.obs_norm.to(device))
 
     def _sets(self, n: int, first_walker: int, n_total: Optional[int]):
         """The parameter set of each of n rows starting at walker first_walker of n_total (numpy int64), or None for
@@ -163,6 +172,8 @@ class MLPPolicy:
             raise ValueError(f"obs_rows must be [n, {self.D}], got {x.shape}")
         sets = self._sets(x.shape[0], first_walker, n_walkers_total)
         host = lambda t: None if t is None else t.detach().cpu().numpy()
+        if self.obs_norm is not None:
+            x = self.obs_norm.normalize_numpy(x)
 
         def layer(x, w, b):
             n, J = x.shape[0], w.shape[2]
@@ -203,7 +214,7 @@ class MLPPolicy:
                 acc = torch.add(acc, torch.mul(x[:, i:i + 1], wi))    # two roundings: never addcmul / matmul
             return acc
 
-        x = rows
+        x = rows if self.obs_norm is None else self.obs_norm.normalize_torch(rows)
         if self.H:
             z = layer(x, self.w1, self.b1)
             x = torch.where(z > 0, z, torch.zeros_like(z))
