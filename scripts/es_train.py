@@ -19,6 +19,10 @@ generation's candidates and mean policy run under them; tell() does not read the
 changes nothing).  The rows are then of order one, so --sigma and --lr default to the trainer's own defaults (0.05,
 0.05) instead of the raw rows' 0.001 and 1e-4.
     python scripts/es_train.py --adaptive --obs-norm --out profiles/r14_es_obs_norm_balance_curve.json
+
+--act-every K: the candidates and the mean policy decide every K steps and hold their action between
+(generation_step(act_every=K): the deterministic rollout_held).
+    python scripts/es_train.py --act-every 4 --out profiles/r15_es_act_every4_balance_curve.json
 """
 import argparse
 import json
@@ -48,6 +52,7 @@ def main():
     ap.add_argument("--obs-norm", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--adaptive", action="store_true")
+    ap.add_argument("--act-every", type=int, default=1)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     a.sigma = (0.05 if a.obs_norm else 0.001) if a.sigma is None else a.sigma
@@ -70,8 +75,11 @@ def main():
     t0 = time.perf_counter()
     for g in range(a.generations):
         env.batch.load_state_dict(start)
-        mean_ret = env.rollout_policy(tr.mean_policy(), a.steps)["returns"].double().mean()
-        out = tr.generation_step(a.steps, obs_out=rows)
+        if a.act_every > 1:
+            mean_ret = env.rollout_held(tr.mean_policy(), a.steps, a.act_every)["returns"].double().mean()
+        else:
+            mean_ret = env.rollout_policy(tr.mean_policy(), a.steps)["returns"].double().mean()
+        out = tr.generation_step(a.steps, obs_out=rows, act_every=a.act_every)
         if nm is not None:
             nm.update(rows, mask)
         curve.append({"generation": g, "mean_policy_return": float(mean_ret),
@@ -89,7 +97,7 @@ def main():
         print(json.dumps(curve[-1]), flush=True)
     torch.cuda.synchronize()
     res = {"env": "Balance-v0", "walkers": env.N, "population": tr.G, "hidden": tr.H, "K": tr.K, "steps": a.steps,
-           "trainer": type(tr).__name__, "obs_norm": bool(a.obs_norm), "sigma": a.sigma if a.adaptive else tr.sigma, "lr": tr.lr, "seed": tr.seed, "seconds": time.perf_counter() - t0,
+           "trainer": type(tr).__name__, "obs_norm": bool(a.obs_norm), "act_every": a.act_every, "sigma": a.sigma if a.adaptive else tr.sigma, "lr": tr.lr, "seed": tr.seed, "seconds": time.perf_counter() - t0,
            "device": torch.cuda.get_device_name(0), "curve": curve}
     if a.out:
         with open(a.out, "w") as f:

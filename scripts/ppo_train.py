@@ -17,6 +17,12 @@ of the ad-hoc obs_scale; updated once per iteration from batch["obs_before"], af
 rows are re-evaluated under the statistics they were collected with and the first-pass ratio stays exactly 1.  The
 actor's first layer then starts at 1 / sqrt(D) (unit-scale inputs) instead of 0.002.
     python scripts/ppo_train.py --obs-norm --out profiles/r14_ppo_obs_norm_balance_curve.json
+
+--act-every K: the actor decides every K steps and holds its action between (pg.collect(act_every=K): rollout_held and
+the GAE on the decision grid, `held` carried from one iteration's rollout to the next).  The update's rows are the
+decided ones (the mask becomes ok & decided: the density, the surrogate and the critic's loss are put on those alone); a
+row's return is the hold's summed reward plus the discounted value at the next decision.
+    python scripts/ppo_train.py --act-every 4 --out profiles/r15_ppo_act_every4_balance_curve.json
 """
 import argparse
 import json
@@ -52,6 +58,7 @@ def main():
     ap.add_argument("--max-steps", type=int, default=200)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--obs-norm", action="store_true")
+    ap.add_argument("--act-every", type=int, default=1)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.manual_seed(a.seed)
@@ -79,13 +86,17 @@ def main():
         z = (u - mean) / log_sigma.exp()
         return (-0.5 * z * z - log_sigma - 0.5 * math.log(2 * math.pi)).sum(-1)
 
-    curve, t0 = [], time.perf_counter()
+    curve, t0, held = [], time.perf_counter(), None
     for it in range(a.iterations):
         sigma = log_sigma.exp().detach().reshape(1, A).contiguous()
-        batch = pg.collect(env, pol, sigma, a.steps, a.seed, it * a.steps, value_fn, a.gamma, a.lam)
+        batch = pg.collect(env, pol, sigma, a.steps, a.seed, it * a.steps, value_fn, a.gamma, a.lam,
+                           act_every=a.act_every, held=held)
+        held = batch.get("held")
         obs, u = batch["obs_before"], batch["raw_action"]          # [T, N, D], [T, N, A]
         adv, ret = batch["adv"], batch["ret"]
         ok = torch.isfinite(adv) & torch.isfinite(ret) & torch.isfinite(obs).all(-1) & torch.isfinite(u).all(-1)
+        if a.act_every > 1:
+            ok = ok & (batch["decided"] != 0)
         adv_n = torch.where(ok, (adv - adv[ok].mean()) / (adv[ok].std() + 1e-8), torch.zeros_like(adv))
         ret_0 = torch.where(ok, ret, torch.zeros_like(ret))
         with torch.no_grad():   # the old policy's density: the same function on the same rows, before any update
@@ -121,12 +132,13 @@ def main():
                       "value_loss": float(v_loss.detach()), "sigma": [float(s) for s in log_sigma.exp()],
                       "clipped_action_fraction": float((batch["raw_action"].abs() > 1).float().mean()),
                       "first_pass_max_ratio_minus_1": first_ratio_dev,
-                      "samples_dropped_nonfinite": int((~ok).sum())})
+                      "samples_dropped_nonfinite": int((~ok).sum()) if a.act_every == 1 else
+                      int((~ok & (batch["decided"] != 0)).sum()), "samples": int(ok.sum())})
         print(json.dumps(curve[-1]), flush=True)
     torch.cuda.synchronize()
     res = {"env": "Balance-v0", "walkers": N, "hidden": H, "steps": a.steps, "iterations": a.iterations,
            "epochs": a.epochs, "minibatches": a.minibatches, "lr": a.lr, "clip": a.clip, "gamma": a.gamma,
-           "lam": a.lam, "max_steps": a.max_steps, "seed": a.seed, "obs_norm": bool(a.obs_norm), "seconds": time.perf_counter() - t0,
+           "lam": a.lam, "max_steps": a.max_steps, "seed": a.seed, "obs_norm": bool(a.obs_norm), "act_every": a.act_every, "seconds": time.perf_counter() - t0,
            "device": torch.cuda.get_device_name(0), "curve": curve}
     if a.out:
         with open(a.out, "w") as f:

@@ -13,7 +13,9 @@ BatchedPhysicsEnv.rollout_stochastic and walker_gym_amd.pg (seeded action noise 
 collect() for PPO: wg_rollout_stochastic / wg_gae; policy_rows(), the MLPPolicy over recorded rows as a
 torch.autograd.Function: wg_policy_forward / wg_policy_backward); walker_gym_amd.normalize.ObsNorm, running observation
 statistics on the device (wg_obs_moments) and the normaliser MLPPolicy(obs_norm=...) evaluates in every kernel
-(wg_rollout_normalized, wg_policy_forward_normalized / wg_policy_backward_normalized).
+(wg_rollout_normalized, wg_policy_forward_normalized / wg_policy_backward_normalized); BatchedPhysicsEnv.rollout_held,
+the resident closed loop with an action hold (decide every k steps: wg_rollout_held), and pg.gae_held on its decision
+grid (wg_gae_held).
 Importing the package needs no GPU; stepping does (no CPU fallback).
 """
 from .engine import Config, DingPoint, Point, to_data  # noqa: F401
@@ -49,6 +51,12 @@ def __getattr__(name):
     if name == "rollout_stochastic":   # BatchedPhysicsEnv.rollout_stochastic(env, policy, n_steps, sigma, seed, ...)
         from . import batched_env
         return batched_env.BatchedPhysicsEnv.rollout_stochastic
+    if name == "rollout_held":   # BatchedPhysicsEnv.rollout_held(env, policy, n_steps, every, sigma=None, ...): action hold
+        from . import batched_env
+        return batched_env.BatchedPhysicsEnv.rollout_held
+    if name in ("gae_held", "gae_held_numpy", "hold_decide_numpy"):   # pg's GAE on the hold's decision grid
+        import importlib
+        return getattr(importlib.import_module(".pg", __name__), name)
     if name in ("PhysicsEnv", "make_env"):
         from . import optimized_env
         return getattr(optimized_env, name)

@@ -110,6 +110,12 @@ class WgObsNorm(C.Structure):
     _fields_ = [("mean", _vp), ("scale", _vp), ("clip", C.c_float)]
 
 
+class WgActionHold(C.Structure):
+    """wg_action_hold: the action hold of wg_rollout_held and its optional per-step outputs."""
+    _fields_ = [("every", C.c_int32), ("held", _vp), ("decided_out", _vp), ("decided_out_step", C.c_int64),
+                ("hold_reward_out", _vp), ("hold_reward_out_step", C.c_int64)]
+
+
 POLICY_GRAD_MAX_K = 16384   # WG_POLICY_GRAD_MAX_K
 
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
@@ -118,7 +124,7 @@ EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_r
            "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches", "wg_wt_launches", "wg_es_perturb", "wg_es_update",
            "wg_rollout_stochastic", "wg_gae", "wg_policy_forward", "wg_policy_backward_workspace", "wg_policy_backward",
            "wg_es_perturb_diag", "wg_es_update_diag", "wg_rollout_normalized", "wg_policy_forward_normalized",
-           "wg_policy_backward_normalized", "wg_obs_moments_workspace", "wg_obs_moments")
+           "wg_policy_backward_normalized", "wg_obs_moments_workspace", "wg_obs_moments", "wg_rollout_held", "wg_gae_held")
 
 _lib = None
 _lock = threading.Lock()
@@ -165,6 +171,11 @@ def load(path: str | None = None):
                                                    _vp, C.c_int64, _vp]
         L.wg_policy_backward_normalized.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgObsNorm), C.POINTER(WgPolicyRows),
                                                     _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.wg_rollout_held.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), C.POINTER(WgPolicy), C.POINTER(WgObsNorm),
+                                      C.POINTER(WgActionNoise), C.POINTER(WgActionHold), C.POINTER(WgOutputs),
+                                      C.POINTER(WgEpisodeStats), C.c_int32, _vp]
+        L.wg_gae_held.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_float,
+                                  _vp, _vp, _vp]
         L.wg_obs_moments_workspace.argtypes = [C.POINTER(WgPolicyRows), C.c_int32, C.c_int32]
         L.wg_obs_moments.argtypes = [C.POINTER(WgPolicyRows), C.c_int32, C.c_float, C.c_int32, _vp, _vp, C.c_double,
                                      _vp, _vp, _vp]

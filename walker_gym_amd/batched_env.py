@@ -758,6 +758,96 @@ class BatchedPhysicsEnv:
         self._stale = _ROLLOUT_STALE
         return res
 
+    def rollout_held(self, policy, n_steps: int, every: int, sigma=None, seed: int = 0, step_base: int = 0,
+                     walker_base: int = 0, held=None, decided_out=None, hold_reward_out=None, obs_out=None,
+                     reward_out=None, done_out=None, steps_out=None, action_out=None, raw_action_out=None, eps_out=None,
+                     reset_out=None, final_obs_out=None, episode_slots: int = 0) -> dict:
+        """The resident closed loop with an action hold (frame skip), in ONE launch (wg_rollout_held): a walker decides
+        at the steps where its step counter at the start of the step (info['steps'], which auto-reset zeroes) is a
+        multiple of `every`, and applies the action in force at the steps between.  A deciding walker's action is what
+        rollout_policy / rollout_episodes (auto-reset off / on) computes at that step, or with `sigma` given what
+        rollout_stochastic does (noise on counter step_base + s; a held step makes no draw); policy.obs_norm is
+        honoured.  action_out holds the action applied at every step; raw_action_out / eps_out are written on the
+        deciding rows only; decided_out [T, N] u8 marks them; hold_reward_out [T, N] f32 is the running reward of the
+        open hold after each step (reward at a decision, then added in step order in float32).  held: float32 device
+        tensor [N, C + 1], in and out: each walker's action in force and the running reward of its open hold; None
+        starts from zeros.  It is returned under 'held' and passed to the next call, with step_base advanced, to
+        continue: two calls of a and b steps equal one of a + b.  every = 1 is the existing entry bit for bit.
+
+        Returns the mode's dict (rollout_policy's or rollout_episodes') plus 'held'.  The ValueErrors of the mode's
+        entry and of rollout_stochastic, and for every < 1 or a held / decided_out / hold_reward_out that does not
+        fit."""
+        N, dv = self.N, self.device
+        entry = "rollout_held"
+        ar = bool(self._ar_mode)
+        slots = int(episode_slots)
+        if not ar and (slots != 0 or reset_out is not None or final_obs_out is not None):
+            raise ValueError(f"{entry}: episode_slots / reset_out / final_obs_out need auto-reset (enable_auto_reset)")
+        pol, o, T = self._resident_policy(entry, ar, policy, n_steps, slots if ar else None, obs_out, reward_out,
+                                          done_out, action_out, reset_out, final_obs_out)
+        G, Cc = policy.G, policy.C
+        if int(every) < 1:
+            raise ValueError(f"{entry}: every {every} < 1")
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"{entry}: seed is a uint64")
+        if not (0 <= int(step_base) and int(step_base) + T <= 1 << 32):
+            raise ValueError(f"{entry}: step_base {step_base} + n_steps {T} outside 0 .. 2^32")
+        if not (0 <= int(walker_base) and int(walker_base) + N <= 1 << 32):
+            raise ValueError(f"{entry}: walker_base {walker_base} + N {N} outside 0 .. 2^32")
+        if sigma is None:
+            if raw_action_out is not None or eps_out is not None:
+                raise ValueError(f"{entry}: raw_action_out / eps_out need sigma (the stochastic form)")
+        elif not isinstance(sigma, torch.Tensor):
+            sigma = torch.full((G, Cc), float(sigma), dtype=torch.float32, device=dv)
+        elif sigma.dim() == 1 and G == 1:
+            sigma = sigma[None]
+        if sigma is not None:
+            require_tensor(sigma, "sigma", dv, torch.float32, (G, Cc))
+        if held is None:
+            held = torch.zeros((N, Cc + 1), dtype=torch.float32, device=dv)
+        for name, t, dt, shape in (("steps_out", steps_out, torch.int32, (T, N)),
+                                   ("raw_action_out", raw_action_out, torch.float32, (T, N, Cc)),
+                                   ("eps_out", eps_out, torch.float32, (T, N, Cc)),
+                                   ("held", held, torch.float32, (N, Cc + 1)),
+                                   ("decided_out", decided_out, torch.uint8, (T, N)),
+                                   ("hold_reward_out", hold_reward_out, torch.float32, (T, N))):
+            if t is not None:
+                require_tensor(t, name, dv, dt, shape)
+        p = _lib.ptr
+        o.steps = p(steps_out)
+        nz = None
+        if sigma is not None:
+            nz = C.byref(_lib.WgActionNoise(seed=int(seed), step_base=int(step_base), walker_base=int(walker_base),
+                                            sigma=p(sigma), raw_out=p(raw_action_out), raw_out_step=N * Cc,
+                                            eps_out=p(eps_out), eps_out_step=N * Cc))
+        hold = _lib.WgActionHold(every=int(every), held=p(held), decided_out=p(decided_out), decided_out_step=N,
+                                 hold_reward_out=p(hold_reward_out), hold_reward_out_step=N)
+        if ar:
+            res = {"return_sum": torch.empty(N, dtype=torch.float32, device=dv),
+                   "length_sum": torch.empty(N, dtype=torch.int32, device=dv),
+                   "episodes": torch.empty(N, dtype=torch.int32, device=dv),
+                   "tail_return": torch.empty(N, dtype=torch.float32, device=dv),
+                   "tail_length": torch.empty(N, dtype=torch.int32, device=dv)}
+            if slots > 0:
+                res["ep_returns"] = torch.full((N, slots), float("nan"), dtype=torch.float32, device=dv)
+                res["ep_lengths"] = torch.full((N, slots), -1, dtype=torch.int32, device=dv)
+            st = C.byref(_lib.WgEpisodeStats(return_sum=p(res["return_sum"]), length_sum=p(res["length_sum"]),
+                                             episodes_done=p(res["episodes"]), tail_return=p(res["tail_return"]),
+                                             tail_length=p(res["tail_length"]), ep_return=p(res.get("ep_returns")),
+                                             ep_length=p(res.get("ep_lengths")), ep_slots=slots))
+        else:
+            res = {"returns": torch.empty(N, dtype=torch.float32, device=dv),
+                   "lengths": torch.empty(N, dtype=torch.int32, device=dv)}
+            pol.return_out, pol.length_out = p(res["returns"]), p(res["lengths"])
+            st = None
+        nm = C.byref(policy.obs_norm.struct()) if policy.obs_norm is not None else None
+        _lib.check(_lib.load().wg_rollout_held(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol), nm, nz,
+                                               C.byref(hold), C.byref(o), st, T, self._stream()), "wg_rollout_held")
+        self._steps_at = -1   # (as rollout_policy(): only after the call was accepted)
+        self._stale = _ROLLOUT_STALE
+        res["held"] = held
+        return res
+
     def run(self, actions, n_steps: int, info: bool = True, lanes: Optional[int] = None, resident: bool = False,
             record: Optional[dict] = None, _only: Optional[int] = None):
         """Throughput path: n_steps env steps in one C call; step s acts with actions[s % T]

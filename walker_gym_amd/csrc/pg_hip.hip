@@ -9,6 +9,7 @@
 //              already in registers: with vmcnt counting in order the chain waits for its own block only, and 5 * GAE_U
 //              loads per lane stay in flight behind it.  Six dependent float32 operations per step, no FMA
 //              (-ffp-contract=off, and the intrinsics round once each).  Every element offset is 64-bit.
+//   gae_held_scan  wg_gae_held: the same scan on wg_rollout_held's decision grid (a sixth load, `decided`, per step).
 //
 // and wg_policy_forward / wg_policy_backward: wg_policy's layers over recorded observation rows, and their gradient.
 //
@@ -101,6 +102,71 @@ __global__ __launch_bounds__(GAE_THREADS) void gae_scan(const float *__restrict_
             const int64_t at = (int64_t)t * stride + w;
             adv[at] = carry;
             if (ret) ret[at] = __fadd_rn(carry, cur[k].v);
+        }
+#pragma unroll
+        for (int k = 0; k < GAE_U; k++) cur[k] = nxt[k];
+    }
+}
+
+// wg_gae_held: gae_scan on the decision grid of wg_rollout_held.  The same structure (one thread per walker, a step's
+// seven loads contiguous across the wave, the next block's loads ahead of the chain); beside `carry` a thread carries
+// the open hold's closing values (R, nv, cf) and whether the step above it decided (that step then closes a hold).
+struct GaeHeldIn {
+    float r, v, nv;
+    uint32_t dc, tm, ct;
+};
+template <bool TERM, bool CUT>
+__device__ __forceinline__ void gae_held_load(GaeHeldIn (&x)[GAE_U], const float *__restrict__ hold_reward,
+                                              const float *__restrict__ value, const float *__restrict__ next_value,
+                                              const uint8_t *__restrict__ decided, const uint8_t *__restrict__ term,
+                                              const uint8_t *__restrict__ cut, int t_hi, int64_t stride, int w) {
+#pragma unroll
+    for (int k = 0; k < GAE_U; k++) {
+        const int t = t_hi - k > 0 ? t_hi - k : 0;
+        const int64_t at = (int64_t)t * stride + w;
+        x[k].r = hold_reward[at];
+        x[k].v = value[at];
+        x[k].nv = next_value[at];
+        x[k].dc = decided[at];
+        x[k].tm = TERM ? term[at] : 0u;
+        x[k].ct = CUT ? cut[at] : 0u;
+    }
+}
+
+template <bool TERM, bool CUT>
+__global__ __launch_bounds__(GAE_THREADS) void gae_held_scan(
+    const float *__restrict__ hold_reward, const float *__restrict__ value, const float *__restrict__ next_value,
+    const uint8_t *__restrict__ decided, const uint8_t *__restrict__ term, const uint8_t *__restrict__ cut, int n_steps,
+    int N, int64_t stride, float gamma, float gl, float *__restrict__ adv, float *__restrict__ ret) {
+    const int w = (int)(blockIdx.x * GAE_THREADS + threadIdx.x);
+    if (w >= N) return;
+    GaeHeldIn cur[GAE_U], nxt[GAE_U];
+    float carry = 0.f, R = 0.f, nv = 0.f;
+    uint32_t cf = 0u;
+    bool closes = true;   // the call's last step closes the hold it is in
+    gae_held_load<TERM, CUT>(cur, hold_reward, value, next_value, decided, term, cut, n_steps - 1, stride, w);
+    for (int t_hi = n_steps - 1; t_hi >= 0; t_hi -= GAE_U) {
+        gae_held_load<TERM, CUT>(nxt, hold_reward, value, next_value, decided, term, cut, t_hi - GAE_U, stride, w);
+#pragma unroll
+        for (int k = 0; k < GAE_U; k++) {
+            const int t = t_hi - k;
+            if (t < 0) break;
+            if (closes) {
+                R = cur[k].r;
+                nv = cur[k].tm ? 0.f : cur[k].nv;
+                cf = cur[k].ct;
+            }
+            closes = cur[k].dc != 0u;
+            float a = 0.f, r = 0.f;
+            if (closes) {   // the step decided
+                const float delta = __fsub_rn(__fadd_rn(R, __fmul_rn(gamma, nv)), cur[k].v);
+                const float c = cf ? 0.f : carry;
+                a = carry = __fadd_rn(delta, __fmul_rn(gl, c));
+                r = __fadd_rn(carry, cur[k].v);
+            }
+            const int64_t at = (int64_t)t * stride + w;
+            adv[at] = a;
+            if (ret) ret[at] = r;
         }
 #pragma unroll
         for (int k = 0; k < GAE_U; k++) cur[k] = nxt[k];
@@ -774,6 +840,46 @@ int wg_gae(const float *reward, const float *value, const float *next_value, con
     else if (cut) go(gae_scan<false, true>);
     else go(gae_scan<false, false>);
     return wg_launched("wg_gae: launch");
+}
+
+int wg_gae_held(const float *hold_reward, const float *value, const float *next_value, const uint8_t *decided,
+                const uint8_t *term, const uint8_t *cut, int32_t n_steps, int32_t N, int64_t step_stride, float gamma,
+                float lam, float *adv, float *ret, hipStream_t stream) {
+    if (!hold_reward) return wg_fail(WG_EINVAL, "wg_gae_held: null hold_reward");
+    if (!value) return wg_fail(WG_EINVAL, "wg_gae_held: null value");
+    if (!next_value) return wg_fail(WG_EINVAL, "wg_gae_held: null next_value");
+    if (!decided) return wg_fail(WG_EINVAL, "wg_gae_held: null decided");
+    if (!adv) return wg_fail(WG_EINVAL, "wg_gae_held: null adv");
+    if (n_steps < 1) return wg_fail(WG_EINVAL, "wg_gae_held: n_steps %d < 1", n_steps);
+    if (N < 1) return wg_fail(WG_EINVAL, "wg_gae_held: N %d < 1", N);
+    if (step_stride < N)
+        return wg_fail(WG_EINVAL, "wg_gae_held: step_stride %lld < N = %d", (long long)step_stride, N);
+    if (!std::isfinite(gamma)) return wg_fail(WG_EINVAL, "wg_gae_held: gamma is not finite");
+    if (!std::isfinite(lam)) return wg_fail(WG_EINVAL, "wg_gae_held: lam is not finite");
+    const struct { const char *name; const void *p; int elem; } in[] = {
+        {"hold_reward", hold_reward, 4}, {"value", value, 4}, {"next_value", next_value, 4}, {"decided", decided, 1},
+        {"term", term, 1}, {"cut", cut, 1}};
+    const Span sa = span_of(adv, n_steps, N, step_stride, 4);
+    for (const auto &i : in) {
+        if (!i.p) continue;
+        const Span si = span_of(i.p, n_steps, N, step_stride, i.elem);
+        if (overlap(sa, si)) return wg_fail(WG_EINVAL, "wg_gae_held: adv aliases %s", i.name);
+        if (ret && overlap(span_of(ret, n_steps, N, step_stride, 4), si))
+            return wg_fail(WG_EINVAL, "wg_gae_held: ret aliases %s", i.name);
+    }
+    if (ret && overlap(sa, span_of(ret, n_steps, N, step_stride, 4)))
+        return wg_fail(WG_EINVAL, "wg_gae_held: adv aliases ret");
+    const float gl = gamma * lam;   // one float32 multiply (-ffp-contract=off)
+    const dim3 grid((N + GAE_THREADS - 1) / GAE_THREADS);
+    auto go = [&](auto kernel) {
+        kernel<<<grid, GAE_THREADS, 0, stream>>>(hold_reward, value, next_value, decided, term, cut, n_steps, N,
+                                                 step_stride, gamma, gl, adv, ret);
+    };
+    if (term && cut) go(gae_held_scan<true, true>);
+    else if (term) go(gae_held_scan<true, false>);
+    else if (cut) go(gae_held_scan<false, true>);
+    else go(gae_held_scan<false, false>);
+    return wg_launched("wg_gae_held: launch");
 }
 
 int wg_policy_forward(const wg_policy *pol, const wg_policy_rows *rows, float *y, int64_t y_step, hipStream_t stream) {

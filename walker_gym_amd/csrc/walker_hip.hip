@@ -3009,6 +3009,18 @@ struct KObsNorm {
     float clip;
 };
 
+// The action hold of wg_rollout_held (wg_action_hold): the HOLD instances of walker_rollout_policy take it as their last
+// kernel argument (the other instances take the empty KNoReset).  A walker's held action stands in the slice's action
+// region (pol.off_a), where the deciding walkers' output lanes overwrite it; its running hold reward in one more word.
+struct KHold {
+    float *held;                   // optional in/out [N][C + 1]
+    uint8_t *decided_out;          // optional [n_steps][N]
+    float *hold_reward_out;        // optional [n_steps][N]
+    int64_t decided_out_step, hold_reward_out_step;
+    int every;
+    int off_hr;                    // byte offset in the wave's LDS slice: one float per walker, the open hold's reward
+};
+
 // One unit of a layer, the contract's chain: acc = bias; acc = RN32(acc + RN32(x[i] * w[i][j])) for i ascending, the
 // multiply and the add separate roundings (no FMA).  x: the walker's input vector in LDS (the same address in every lane
 // of the walker: a broadcast); w: column j of the set's [n][stride] matrix.
@@ -3072,12 +3084,18 @@ __device__ __forceinline__ void policy_unit2(const float *x, const float *__rest
 // NM = KObsNorm (wg_rollout_normalized): once the rows stand in the slice, each walker's mass lanes rewrite their own row
 // in place, lane q taking elements q, q + M, ...: xn = clip(RN32(RN32(x - mean) * scale)), and the units run on xn.  The
 // slice is the policy's private copy (lean_compute stores the step's rows itself): the stored rows stay raw.
-template <bool IN3D, int WS = 4, class NZ = KNoReset, class NM = KNoReset>
+// HOLD (wg_rollout_held): db has the bit of lane q == 0 of every walker that decides at this step.  Only those walkers'
+// lanes run the layers: the others load no weight, make no Philox call and store nothing, so their actions in the slice
+// stay the held ones, which is what their muscle lanes get back.  NZ and NM are then both given and each is in force
+// iff its first pointer is set (wave-uniform): one HOLD instance serves the four forms, with the arithmetic of each.
+template <bool IN3D, int WS = 4, class NZ = KNoReset, class NM = KNoReset, bool HOLD = false>
 __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &kp, const KPolicy &pol, const LeanGeo &lg,
                                              char *smem, char *sl, const LeanTile &t, const float *p3, const float *v3,
                                              const LeanPolOut &ps, float x, float *act_dst, const NZ &nz = NZ{},
-                                             int s = 0, const NM &nm = NM{}) {
+                                             int s = 0, const NM &nm = NM{}, unsigned long long db = ~0ull) {
     const int M = b.M, D = pol.D, H = pol.H, C = pol.C;
+    // the lanes that run the layers: the tile's mass lanes, under a hold those of the deciding walkers
+    const bool run = HOLD ? (t.is_mass && ((db >> ((t.wl * M) & 63)) & 1ull) != 0ull) : t.is_mass;
     float *row = reinterpret_cast<float *>(sl + pol.off_row);
     float *hid = reinterpret_cast<float *>(sl + pol.off_h);
     float *act = reinterpret_cast<float *>(sl + pol.off_a);
@@ -3086,7 +3104,7 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
                         ps.sz * lg.invM, x);
     wave_sync();
     if constexpr (std::is_same<NM, KObsNorm>::value) {
-        if (t.is_mass) {
+        if (run && (!HOLD || nm.mean)) {
             float *xr = row + t.wl * D;
             const float lim = nm.clip;
             for (int i = t.q; i < D; i += M) {
@@ -3101,7 +3119,7 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
     const float *xin = row + t.wl * D;   // (read by the tile's mass lanes only: t.wl < t.nw)
     int n = D;
     if (H > 0) {   // wave-uniform
-        if (t.is_mass) {
+        if (run) {
             // the lane's units two at a time (j and j + M; a lane with an odd count repeats its last unit and drops
             // the copy)
             for (int j = t.q; j < H; j += 2 * M) {
@@ -3123,7 +3141,7 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
         xin = hid + t.wl * H;
         n = H;
     }
-    if (t.is_mass) {
+    if (run) {
         const float lim = pol.act_limit;
         for (int j = t.q; j < C; j += M) {
             const float bias = pol.b2 ? pol.b2[(size_t)gset * (size_t)C + j] : 0.f;
@@ -3132,7 +3150,7 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
                                               bias)
                                 : policy_unit(xin, pol.w2 + (size_t)gset * (size_t)n * (size_t)C + j, n, C, bias);
             float u = y;
-            if constexpr (std::is_same<NZ, KNoise>::value) {
+            if constexpr (std::is_same<NZ, KNoise>::value) if (!HOLD || nz.sigma) {
                 const uint32_t wg = (uint32_t)(t.w0 + t.wl);
                 const float e = wg_eps<WG_ACT_TAG>(nz.k0, nz.k1, nz.step_base + (uint32_t)s, nz.walker_base + wg, (uint32_t)j);
                 u = __fadd_rn(y, __fmul_rn(nz.sigma[(size_t)gset * (size_t)C + j], e));
@@ -3163,7 +3181,15 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
 // the NZ = false instances, whose trailing argument is the empty KNoReset.
 // ON (wg_rollout_normalized): the observation normaliser in front of the policy's layers (lean_policy), in every mode,
 // carried exactly as NZ is.
-template <bool IN3D, int NE, bool E8, bool AR = false, bool NZ = false, bool ON = false>
+// HOLD (wg_rollout_held): a walker decides at the steps where its counter at the start of the step is a multiple of
+// hd.every and applies the action in force otherwise.  Lane q == 0 of a walker holds the counter (lean_compute keeps it
+// there), so the deciding walkers are a ballot of those lanes; the policy runs when the ballot is not empty (a
+// wave-uniform branch) and only the deciding walkers' lanes run its layers (lean_policy).  The action in force stands in
+// the slice's action region from entry (the caller's `held` rows, or +0.0) to the store after the last step; the muscle
+// lanes store every step's action_out row from their registers.  The running hold reward is one more LDS word per
+// walker, kept by lane q == 0.  Instantiated with NZ and ON both set: the noise and the normaliser are in force iff
+// their pointers are, so 40 instances serve the four forms of either mode (see DESIGN 9i for the cost).
+template <bool IN3D, int NE, bool E8, bool AR = false, bool NZ = false, bool ON = false, bool HOLD = false>
 // (register budget: one wave per SIMD fewer than walker_rollout_lean.  The LDS slice with the rows already holds the
 // canonical walker to 4 waves per SIMD, the NE 8 shapes to 2, and the latency-bound NE 1 batches run one)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3 : 4))) void walker_rollout_policy(
@@ -3171,7 +3197,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
     typename std::conditional<AR, KReset, KNoReset>::type ar,
     typename std::conditional<AR, wg_episode_stats, KNoReset>::type st,
     typename std::conditional<NZ, KNoise, KNoReset>::type nz,
-    typename std::conditional<ON, KObsNorm, KNoReset>::type nm) {
+    typename std::conditional<ON, KObsNorm, KNoReset>::type nm,
+    typename std::conditional<HOLD, KHold, KNoReset>::type hd) {
+    static_assert(!HOLD || (NZ && ON), "the HOLD instances carry the noise and the normaliser as runtime options");
     constexpr int WS = AR ? 8 : 4;   // LDS words per walker
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -3226,6 +3254,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
             wk[6] = (uint32_t)at_u32(b.episodes, 4u * (uint32_t)(t.w0 + t.wl));
         }
     }
+    if constexpr (HOLD) {   // the action in force and the open hold's reward at entry
+        float *act = reinterpret_cast<float *>(sl + pol.off_a), *hr = reinterpret_cast<float *>(sl + hd.off_hr);
+        if (t.is_mass) {
+            const float *hw = hd.held ? hd.held + (size_t)(uint32_t)(t.w0 + t.wl) * (size_t)(pol.C + 1) : nullptr;
+            for (int j = t.q; j < pol.C; j += b.M) act[t.wl * pol.C + j] = hw ? hw[j] : 0.f;
+            if (t.q == 0) hr[t.wl] = hw ? hw[pol.C] : 0.f;
+        }
+        wave_sync();
+        L.a = t.acts ? act[t.mu_wl * pol.C + t.mu_ua] : 0.f;
+    }
 #pragma clang loop unroll(disable)
     for (int s = 0; s < n_steps; s++) {
         // (the lane index opaque each step, the static inputs pinned: as walker_rollout_lean)
@@ -3234,7 +3272,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
         LeanTile ts = lean_tile_of(b, nullptr, pol.C, lg, tile, ln);
         ts.acts = ts.is_mus && ts.mu_ua < pol.C;
         float *const act_dst = pol.action_out ? pol.action_out + (size_t)s * (size_t)pol.action_out_step : nullptr;
-        if constexpr (ON) L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst, nz, s, nm);
+        unsigned long long db = ~0ull;   // (HOLD) lane q == 0 of every walker that decides at this step
+        if constexpr (HOLD) {
+            db = __ballot(ts.is_mass && ts.q == 0 && (uint32_t)L.wsteps % (uint32_t)hd.every == 0u);
+            if (db != 0ull)   // wave-uniform
+                L.a = lean_policy<IN3D, WS, KNoise, KObsNorm, true>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x,
+                                                                    nullptr, nz, s, nm, db);
+            if (act_dst && ts.acts)   // the action applied, deciding or held
+                act_dst[(size_t)(uint32_t)(ts.w0 + ts.mu_wl) * (size_t)pol.C + ts.mu_ua] = L.a;
+        } else if constexpr (ON) L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst, nz, s, nm);
         else if constexpr (NZ) L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst, nz, s);
         else L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst);
         WG_KOUT_AT(os, o, s);
@@ -3268,6 +3314,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
                 wk[1] = wk[1] + 1u;
                 wk[2] = ps.done == 0;
             }
+            if constexpr (HOLD) {   // hr = decided ? reward : RN32(hr + reward)
+                float *hr = reinterpret_cast<float *>(sl + hd.off_hr) + ts.wl;
+                const bool dec = ((db >> ((ts.wl * b.M) & 63)) & 1ull) != 0ull;
+                const float h = dec ? ps.reward : __fadd_rn(*hr, ps.reward);
+                *hr = h;
+                const size_t wg = (size_t)(uint32_t)(ts.w0 + ts.wl);   // (64-bit offsets; plain vector stores)
+                if (hd.decided_out) hd.decided_out[(size_t)s * (size_t)hd.decided_out_step + wg] = (uint8_t)dec;
+                if (hd.hold_reward_out) hd.hold_reward_out[(size_t)s * (size_t)hd.hold_reward_out_step + wg] = h;
+            }
         }
         wave_sync();   // this step's LDS reads stay ahead of the next step's writes
     }
@@ -3283,6 +3338,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
         } else {
             if (pol.return_out) pol.return_out[wg] = __uint_as_float(wk[0]);
             if (pol.length_out) pol.length_out[wg] = (int32_t)wk[1];
+        }
+    }
+    if constexpr (HOLD) {   // what the next call starts from
+        if (hd.held && t.is_mass) {
+            const float *act = reinterpret_cast<const float *>(sl + pol.off_a);
+            float *hw = hd.held + (size_t)(uint32_t)(t.w0 + t.wl) * (size_t)(pol.C + 1);
+            for (int j = t.q; j < pol.C; j += b.M) hw[j] = act[t.wl * pol.C + j];
+            if (t.q == 0) hw[pol.C] = reinterpret_cast<const float *>(sl + hd.off_hr)[t.wl];
         }
     }
 }
@@ -3732,6 +3795,12 @@ int wg_rollout_normalized(const wg_batch *b, const wg_params *p, const wg_policy
                           const wg_action_noise *nz, const wg_outputs *o, const wg_episode_stats *st, int32_t n_steps,
                           hipStream_t stream) {
     return rollout_policy(b, p, pol, o, n_steps, stream, p && p->auto_reset != 0, st, nz != nullptr, nz, true, nm);
+}
+int wg_rollout_held(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_obs_norm *nm,
+                    const wg_action_noise *nz, const wg_action_hold *hold, const wg_outputs *o,
+                    const wg_episode_stats *st, int32_t n_steps, hipStream_t stream) {
+    return rollout_policy(b, p, pol, o, n_steps, stream, p && p->auto_reset != 0, st, nz != nullptr, nz, nm != nullptr, nm,
+                          true, hold);
 }
 
 int wg_run_ranges(const wg_range *ranges, int32_t n, const wg_params *p, const float *action, int32_t action_cols,

@@ -404,6 +404,17 @@ int obs_row_len(const wg_batch *b, const wg_params *p) {
     return 3 * (p->in3d ? 3 : 2) * b->M + (p->conmid ? 3 : 0) + b->A;
 }
 
+// [p, p + bytes) of a caller's buffer: wg_rollout_held's test of `held` against the call's other outputs
+struct HostSpan {
+    const char *name;
+    const void *p;
+    int64_t bytes;
+};
+bool host_overlap(const HostSpan &a, const HostSpan &c) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), c0 = reinterpret_cast<uintptr_t>(c.p);
+    return a.p && c.p && a.bytes > 0 && c.bytes > 0 && a0 < c0 + (uintptr_t)c.bytes && c0 < a0 + (uintptr_t)a.bytes;
+}
+
 // wg_rollout_policy: every argument checked, then one walker_rollout_policy launch.  The wave's LDS slice is the lean
 // kernel's plus the walkers' observation rows, hidden vectors and actions.
 // episodes (wg_rollout_episodes): the AR instances, with auto-reset's own checks in place of the auto_reset refusal, the
@@ -411,16 +422,18 @@ int obs_row_len(const wg_batch *b, const wg_params *p) {
 // stochastic (wg_rollout_stochastic): either mode, chosen by p->auto_reset, with the NZ instances and the checks of `nz`.
 // normalized (wg_rollout_normalized): either mode likewise, with or without the noise, the ON instances and the checks of
 // `nm`.
+// held (wg_rollout_held): the mode and the form by p->auto_reset, nz and nm as above, the HOLD instances (which carry the
+// noise and the normaliser as runtime options), the checks of `hold`, and one more word per walker in the slice.
 int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o, int32_t n_steps,
                    hipStream_t stream, bool episodes = false, const wg_episode_stats *st = nullptr,
                    bool stochastic = false, const wg_action_noise *nz = nullptr, bool normalized = false,
-                   const wg_obs_norm *nm = nullptr) {
-    const char *fn = normalized ? "wg_rollout_normalized"
+                   const wg_obs_norm *nm = nullptr, bool held = false, const wg_action_hold *hold = nullptr) {
+    const char *fn = held ? "wg_rollout_held" : normalized ? "wg_rollout_normalized"
                      : stochastic ? "wg_rollout_stochastic" : episodes ? "wg_rollout_episodes" : "wg_rollout_policy";
     int rc = validate(b);
     if (rc) return rc;
     if (!p) return wg_fail(WG_EINVAL, "null params");
-    if ((stochastic || normalized) && !episodes && st)
+    if ((stochastic || normalized || held) && !episodes && st)
         return wg_fail(WG_EINVAL, "%s: episode stats with auto_reset 0 (st must be NULL without episode roll-over)", fn);
     if (!pol) return wg_fail(WG_EINVAL, "%s: null policy", fn);
     if (!pol->w2) return wg_fail(WG_EINVAL, "%s: null w2", fn);
@@ -472,6 +485,42 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
         if (!nm->scale) return wg_fail(WG_EINVAL, "%s: null scale", fn);
         if (!(nm->clip > 0.f)) return wg_fail(WG_EINVAL, "%s: clip must be > 0 (+inf allowed)", fn);
     }
+    if (held) {
+        if (!hold) return wg_fail(WG_EINVAL, "%s: null action hold", fn);
+        if (hold->every < 1) return wg_fail(WG_EINVAL, "%s: every %d < 1", fn, hold->every);
+        if (hold->decided_out && hold->decided_out_step < b->N)
+            return wg_fail(WG_EINVAL, "%s: decided_out_step %lld < N = %d", fn, (long long)hold->decided_out_step, b->N);
+        if (hold->hold_reward_out && hold->hold_reward_out_step < b->N)
+            return wg_fail(WG_EINVAL, "%s: hold_reward_out_step %lld < N = %d", fn,
+                           (long long)hold->hold_reward_out_step, b->N);
+        if (hold->held) {   // in and out: no other output of the call may lie in it
+            const int64_t N = b->N, C = pol->act_dim, T = n_steps, slots = st ? st->ep_slots : 0;
+            const auto steps = [&](int64_t step, int64_t row, int elem) { return ((T - 1) * step + row) * elem; };
+            const wg_outputs oo = o ? *o : wg_outputs{};
+            const int64_t orow = (N - 1) * (int64_t)oo.obs_stride + pol->obs_dim;
+            const HostSpan hs{"held", hold->held, N * (C + 1) * 4};
+            const HostSpan outs[] = {
+                {"action_out", pol->action_out, steps(pol->action_out_step, N * C, 4)},
+                {"return_out", pol->return_out, N * 4}, {"length_out", pol->length_out, N * 4},
+                {"raw_out", nz ? nz->raw_out : nullptr, nz ? steps(nz->raw_out_step, N * C, 4) : 0},
+                {"eps_out", nz ? nz->eps_out : nullptr, nz ? steps(nz->eps_out_step, N * C, 4) : 0},
+                {"decided_out", hold->decided_out, steps(hold->decided_out_step, N, 1)},
+                {"hold_reward_out", hold->hold_reward_out, steps(hold->hold_reward_out_step, N, 4)},
+                {"obs", oo.obs, steps(oo.obs_step, orow, 4)}, {"final_obs", oo.final_obs, steps(oo.obs_step, orow, 4)},
+                {"reward", oo.reward, steps(oo.out_step, N, 4)}, {"done", oo.done, steps(oo.out_step, N, 1)},
+                {"centroid", oo.centroid, steps(3 * oo.out_step, 3 * N, 4)},
+                {"energy", oo.energy, steps(oo.out_step, N, 4)}, {"steps", oo.steps, steps(oo.out_step, N, 4)},
+                {"reset", oo.reset, steps(oo.out_step, N, 1)},
+                {"return_sum", st ? st->return_sum : nullptr, N * 4}, {"length_sum", st ? st->length_sum : nullptr, N * 4},
+                {"episodes_done", st ? st->episodes_done : nullptr, N * 4},
+                {"tail_return", st ? st->tail_return : nullptr, N * 4},
+                {"tail_length", st ? st->tail_length : nullptr, N * 4},
+                {"ep_return", st ? st->ep_return : nullptr, N * slots * 4},
+                {"ep_length", st ? st->ep_length : nullptr, N * slots * 4}};
+            for (const HostSpan &x : outs)
+                if (host_overlap(hs, x)) return wg_fail(WG_EINVAL, "%s: held aliases %s", fn, x.name);
+        }
+    }
     if ((rc = check_integrator(p)) || (rc = check_muscle_bounds(b)) || (rc = check_discrete(b, p))) return rc;
     wg_outputs out = o ? *o : wg_outputs{};
     if ((out.obs || (episodes && out.final_obs)) && out.obs_stride < pol->obs_dim)
@@ -500,6 +549,12 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
     kpol.off_a = kpol.off_h + align16(std::max(1, lg.wpw * kpol.H) * 4);
     kpol.off_w = kpol.off_a + align16(lg.wpw * kpol.C * 4);
     lg.slice = kpol.off_w + lg.wpw * (episodes ? 32 : 16);
+    KHold kh{};
+    if (held) {   // one more float per walker: the open hold's reward
+        kh = KHold{hold->held, hold->decided_out, hold->hold_reward_out, hold->decided_out_step,
+                   hold->hold_reward_out_step, hold->every, lg.slice};
+        lg.slice += align16(lg.wpw * 4);
+    }
     int lds = lg.wpb * lg.slice;
     if (lds > 80 * 1024) return wg_fail(WG_ERANGE, "%s: workgroup needs %d B of LDS (> 80 KiB)", fn, lds);
     // a shared policy's weights staged in LDS where that costs no resident wave: as many workgroups per CU (160 KiB of
@@ -523,15 +578,22 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
     if (stochastic)
         kn = KNoise{nz->sigma, nz->raw_out, nz->eps_out, nz->raw_out_step, nz->eps_out_step,
                     (uint32_t)(nz->seed & 0xffffffffu), (uint32_t)(nz->seed >> 32), nz->step_base, nz->walker_base};
-    const KObsNorm kon = normalized ? KObsNorm{nm->mean, nm->scale, nm->clip} : KObsNorm{};
+    const KObsNorm kon = normalized ? KObsNorm{nm->mean, nm->scale, nm->clip} : KObsNorm{};   // (held: a null mean = off)
     with_instance(p->in3d != 0, ne, use_edge8(b, lg), [&](auto d3, auto n, auto c8) {
         constexpr bool D3 = decltype(d3)::value, E8 = decltype(c8)::value;
         constexpr int NE = decltype(n)::value;
         auto go = [&](auto kernel, const auto &reset, const auto &stats, const auto &noise, const auto &norm) {
             hipLaunchKernelGGL(kernel, grid, block, lds, stream, *b, kp, kpol, kout(out), n_steps, lg, reset, stats, noise,
-                               norm);
+                               norm, KNoReset{});
         };
-        if (normalized) {
+        if (held) {   // (kn with a null sigma, kon with a null mean: that option is off)
+            if (episodes)
+                hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8, true, true, true, true>), grid, block, lds, stream, *b,
+                                   kp, kpol, kout(out), n_steps, lg, ar, *st, kn, kon, kh);
+            else
+                hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8, false, true, true, true>), grid, block, lds, stream,
+                                   *b, kp, kpol, kout(out), n_steps, lg, KNoReset{}, KNoReset{}, kn, kon, kh);
+        } else if (normalized) {
             if (stochastic) {
                 if (episodes) go(walker_rollout_policy<D3, NE, E8, true, true, true>, ar, *st, kn, kon);
                 else go(walker_rollout_policy<D3, NE, E8, false, true, true>, KNoReset{}, KNoReset{}, kn, kon);

@@ -293,20 +293,26 @@ class EvolutionStrategy:
         tot = res["return_sum"].double() + res["tail_return"].double()
         return (tot.view(self.G, wps).sum(dim=1) / (wps * int(n_steps))).to(torch.float32)
 
-    def generation_step(self, n_steps: int, restore: bool = True, obs_out=None) -> dict:
+    def generation_step(self, n_steps: int, restore: bool = True, obs_out=None, act_every: int = 1) -> dict:
         """One generation: (restore the state captured at construction,) ask, one closed-loop rollout of every
         candidate (rollout_policy, or rollout_episodes when the env has auto-reset on; obs_out [T, N, D] records its rows,
         raw, for an ObsNorm.update before the next generation), tell.  ValueError for what the
         rollout refuses (resident batches only).  Returns the generation's number, 'fitness' [G] f32, 'grad' [K] f32
         and the fitness statistics 'fitness_mean' / 'fitness_max' / 'fitness_min' over the candidates that did not
-        diverge, as 0-d device tensors (nothing here waits for the device)."""
+        diverge, as 0-d device tensors (nothing here waits for the device).  act_every > 1: the candidates decide every
+        act_every steps and hold their action between (the deterministic rollout_held, every generation from zeros)."""
         import torch
         env = self.env
+        if int(act_every) < 1:
+            raise ValueError(f"generation_step: act_every {act_every} < 1")
         if restore:
             env.batch.load_state_dict(self._state0)
         pol = self.ask()
-        res = (env.rollout_episodes(pol, n_steps, obs_out=obs_out) if env._ar_mode
-               else env.rollout_policy(pol, n_steps, obs_out=obs_out))
+        if int(act_every) > 1:
+            res = env.rollout_held(pol, n_steps, int(act_every), obs_out=obs_out)
+        else:
+            res = (env.rollout_episodes(pol, n_steps, obs_out=obs_out) if env._ar_mode
+                   else env.rollout_policy(pol, n_steps, obs_out=obs_out))
         fit = self.fitness_of(res, n_steps)
         out = self.tell(fit)
         nan = torch.isnan(fit)
@@ -403,10 +409,10 @@ class AdaptiveEvolutionStrategy(EvolutionStrategy):
         self._told = {"grad": self._grad.clone(), "grad_sigma": self._grad_sigma.clone()}
         return self._told
 
-    def generation_step(self, n_steps: int, restore: bool = True, obs_out=None) -> dict:
+    def generation_step(self, n_steps: int, restore: bool = True, obs_out=None, act_every: int = 1) -> dict:
         """EvolutionStrategy.generation_step's dict plus 'grad_sigma' [K] f32 and the 0-d device tensors 'sigma_mean' /
         'sigma_min' / 'sigma_max' of sigma_vec after the update (nothing here waits for the device)."""
-        out = super().generation_step(n_steps, restore, obs_out)
+        out = super().generation_step(n_steps, restore, obs_out, act_every)
         out["grad_sigma"] = self._told["grad_sigma"]
         out["sigma_mean"] = self.sigma_vec.double().mean()
         out["sigma_min"], out["sigma_max"] = self.sigma_vec.min(), self.sigma_vec.max()

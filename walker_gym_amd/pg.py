@@ -15,6 +15,14 @@ GAE.  With gl = RN32(gamma * lam), carry = +0.0, t descending, float32, every op
 Non-finite inputs flow through; the sign and payload of a NaN the arithmetic produces are not part of the contract (the
 host keeps the NaN operand of a subtraction, the GPU computes a + (-b)).
 
+Action hold.  wg_rollout_held's walker decides at the steps where its counter at the start of the step is a multiple of
+`every` (hold_decide_numpy) and applies the action in force between; hold_reward is the running reward of the open hold.
+gae_held_numpy / gae_held are the GAE on that grid: step t closes a hold iff t == T - 1 or decided[t + 1]; a closing step
+sets R = hold_reward[t], nv = term[t] ? +0.0 : next_value[t], cf = cut[t]; a decided step takes
+  delta = RN32(RN32(R + RN32(gamma * nv)) - value[t]);  c = cf ? +0.0 : carry;  adv[t] = carry = RN32(delta + RN32(gl * c))
+and the other steps get +0.0.  The discount is per decision (a hold is one transition), not per physics step, and a hold
+the rollout's end cuts bootstraps from next_value[T - 1].
+
 Differentiable rows.  policy_rows(policy, obs) is the MLPPolicy over recorded rows [T, N, D] as the rollout kernel
 evaluated it (wg_policy_forward: the chain value before the clip), a torch.autograd.Function whose backward is
 wg_policy_backward: per row, float32, every operation rounded by itself,
@@ -103,6 +111,46 @@ def gae_numpy(reward, value, next_value, term=None, cut=None, gamma: float = 0.9
             carry = (delta + (gl * c).astype(np.float32)).astype(np.float32)
             adv[t] = carry
             ret[t] = carry + v[t]
+    return adv, ret
+
+
+def hold_decide_numpy(steps, every: int):
+    """wg_rollout_held's decision rule: uint8, 1 where a walker whose counter at the start of the step is steps[w]
+    decides, (uint32)steps % every == 0."""
+    every = int(every)
+    if every < 1:
+        raise ValueError("every < 1")
+    st = np.asarray(steps).astype(np.int64) & 0xFFFFFFFF
+    return (st % every == 0).astype(np.uint8)
+
+
+def gae_held_numpy(hold_reward, value, next_value, decided, term=None, cut=None, gamma: float = 0.99, lam: float = 0.95):
+    """wg_gae_held's arithmetic on [T, N] host arrays: (adv, ret), float32 [T, N] each."""
+    hr = np.ascontiguousarray(hold_reward, dtype=np.float32)
+    v = np.ascontiguousarray(value, dtype=np.float32)
+    nvs = np.ascontiguousarray(next_value, dtype=np.float32)
+    dec = np.asarray(decided).reshape(hr.shape) != 0
+    T, N = hr.shape
+    g, zero = np.float32(gamma), np.float32(0.0)
+    adv, ret = np.zeros((T, N), np.float32), np.zeros((T, N), np.float32)
+    carry, R, nv = np.zeros(N, np.float32), np.zeros(N, np.float32), np.zeros(N, np.float32)
+    cf = np.zeros(N, bool)
+    closes = np.ones(N, bool)
+    with np.errstate(all="ignore"):
+        gl = np.float32(g * np.float32(lam))
+        for t in range(T - 1, -1, -1):
+            tm = np.zeros(N, bool) if term is None else np.asarray(term[t]) != 0
+            ct = np.zeros(N, bool) if cut is None else np.asarray(cut[t]) != 0
+            R = np.where(closes, hr[t], R).astype(np.float32)
+            nv = np.where(closes, np.where(tm, zero, nvs[t]), nv).astype(np.float32)
+            cf = np.where(closes, ct, cf)
+            delta = ((R + g * nv).astype(np.float32) - v[t]).astype(np.float32)
+            c = np.where(cf, zero, carry).astype(np.float32)
+            a = (delta + (gl * c).astype(np.float32)).astype(np.float32)
+            carry = np.where(dec[t], a, carry).astype(np.float32)
+            adv[t] = np.where(dec[t], a, zero)
+            ret[t] = np.where(dec[t], (a + v[t]).astype(np.float32), zero)
+            closes = dec[t]
     return adv, ret
 
 
@@ -372,8 +420,80 @@ def gae(reward, value, next_value, term=None, cut=None, gamma: float = 0.99, lam
     return adv, ret
 
 
+def gae_held(hold_reward, value, next_value, decided, term=None, cut=None, gamma: float = 0.99, lam: float = 0.95,
+             adv_out=None, ret_out=None, want_ret: bool = True):
+    """wg_gae_held on device tensors: gae() on the decision grid of rollout_held.  hold_reward / value / next_value
+    float32 [T, N], decided uint8 (or bool) [T, N], term / cut likewise or None, all contiguous on one device.  value is
+    read on the decided steps, next_value / term / cut on the steps that close a hold.  Returns (adv, ret), zero on the
+    steps that did not decide; one launch on the current stream; ValueError for what the library refuses."""
+    import torch
+    from .batched_env import require_tensor
+    if not isinstance(hold_reward, torch.Tensor) or hold_reward.dim() != 2:
+        raise ValueError("gae_held: hold_reward must be a [T, N] float32 device tensor")
+    T, N = (int(s) for s in hold_reward.shape)
+    dv = hold_reward.device
+    require_tensor(hold_reward, "hold_reward", dv, torch.float32)
+    require_tensor(value, "value", dv, torch.float32, (T, N))
+    require_tensor(next_value, "next_value", dv, torch.float32, (T, N))
+    if decided is None:
+        raise ValueError("gae_held: decided is required")
+    flags = []
+    for name, t in (("decided", decided), ("term", term), ("cut", cut)):
+        if t is not None:
+            if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+                t = t.view(torch.uint8)
+            require_tensor(t, name, dv, torch.uint8, (T, N))
+        flags.append(t)
+    adv = torch.empty((T, N), dtype=torch.float32, device=dv) if adv_out is None else adv_out
+    require_tensor(adv, "adv_out", dv, torch.float32, (T, N))
+    ret = ret_out if ret_out is not None else (torch.empty((T, N), dtype=torch.float32, device=dv) if want_ret else None)
+    if ret is not None:
+        require_tensor(ret, "ret_out", dv, torch.float32, (T, N))
+    p = _lib.ptr
+    stream = torch.cuda.current_stream(dv).cuda_stream
+    _lib.check(_lib.load().wg_gae_held(p(hold_reward), p(value), p(next_value), p(flags[0]), p(flags[1]), p(flags[2]), T,
+                                       N, N, float(gamma), float(lam), p(adv), p(ret), stream), "wg_gae_held")
+    return adv, ret
+
+
+def _collect_held(envs, policy, sigma, T, seed, step_base, value_fn, gamma, lam, walker_base, every, held) -> dict:
+    """collect() with an action hold: the rollout through rollout_held, the values on the decision grid."""
+    import torch
+    if not envs._ar_mode & 1:
+        raise ValueError("collect: act_every > 1 needs 'done' in the auto-reset set (a hold ends with its episode)")
+    N, D, Cc, dv = envs.N, envs.obs_dim, policy.C, envs.device
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dv)
+    z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dv)
+    u8 = lambda *s: torch.empty(s, dtype=torch.uint8, device=dv)
+    buf = dict(obs_out=f(T, N, D), reward_out=f(T, N), done_out=u8(T, N),
+               steps_out=torch.empty((T, N), dtype=torch.int32, device=dv), action_out=f(T, N, Cc),
+               raw_action_out=z(T, N, Cc), eps_out=z(T, N, Cc), reset_out=u8(T, N), final_obs_out=z(T, N, D),
+               decided_out=u8(T, N), hold_reward_out=f(T, N))
+    obs0 = envs.observe()[0].clone()
+    res = envs.rollout_held(policy, T, every, sigma=sigma, seed=seed, step_base=step_base, walker_base=walker_base,
+                            held=held, **buf)
+    obs, reset, decided = buf["obs_out"], buf["reset_out"], buf["decided_out"]
+    obs_before = torch.cat([obs0[None], obs[:-1]], dim=0)
+    dec = decided != 0
+    closes = torch.cat([dec[1:], torch.ones((1, N), dtype=torch.bool, device=dv)], dim=0)
+    value, next_value = z(T, N), z(T, N)
+    with torch.no_grad():
+        if bool(dec.any()):
+            value[dec] = value_fn(obs_before[dec]).reshape(-1).to(torch.float32)
+        after = torch.where((reset != 0)[:, :, None], buf["final_obs_out"], obs)
+        next_value[closes] = value_fn(after[closes]).reshape(-1).to(torch.float32)
+    term = ((buf["done_out"] != 0) & (buf["steps_out"] != int(envs.params.max_steps))).to(torch.uint8).contiguous()
+    adv, ret = gae_held(buf["hold_reward_out"], value, next_value, decided, term, reset, gamma, lam)
+    out = dict(res)
+    out.update(obs_before=obs_before, obs=obs, reward=buf["reward_out"], done=buf["done_out"], steps=buf["steps_out"],
+               reset=reset, final_obs=buf["final_obs_out"], action=buf["action_out"], raw_action=buf["raw_action_out"],
+               eps=buf["eps_out"], value=value, next_value=next_value, term=term, cut=reset, adv=adv, ret=ret,
+               decided=decided, hold_reward=buf["hold_reward_out"])
+    return out
+
+
 def collect(envs, policy, sigma, n_steps: int, seed: int, step_base: int = 0, value_fn=None, gamma: float = 0.99,
-            lam: float = 0.95, walker_base: int = 0) -> dict:
+            lam: float = 0.95, walker_base: int = 0, act_every: int = 1, held=None) -> dict:
     """One stochastic rollout of `envs` (a BatchedPhysicsEnv with auto-reset on) under `policy` with the buffers a PPO
     update reads, and its advantages.  value_fn maps observation rows [n, D] to values [n] (or [n, 1]); it is called
     under no_grad on all T * N recorded rows at once, on the N rows the rollout starts from, and on the final_obs rows
@@ -383,12 +503,24 @@ def collect(envs, policy, sigma, n_steps: int, seed: int, step_base: int = 0, va
     cut = reset: the trace stops at an episode boundary.
 
     Returns the rollout's stats dict plus 'obs_before', 'obs', 'reward', 'done', 'steps', 'reset', 'final_obs', 'action',
-    'raw_action', 'eps' ([T, N, ...] device tensors), 'value', 'next_value', 'term', 'cut', 'adv', 'ret' ([T, N])."""
+    'raw_action', 'eps' ([T, N, ...] device tensors), 'value', 'next_value', 'term', 'cut', 'adv', 'ret' ([T, N]).
+
+    act_every > 1 (needs 'done' in the auto-reset set): the rollout is rollout_held's with that hold, `held` its in/out
+    state (None: zeros; pass the returned 'held' and an advanced step_base to continue).  value_fn is then called on the
+    decided rows of obs_before and on the rows that close a hold (final_obs where the walker was reset, obs elsewhere);
+    'value' and 'next_value' are zero elsewhere, as are 'raw_action' / 'eps' on the held rows; 'adv' / 'ret' are
+    gae_held's (zero on the held rows); 'decided', 'hold_reward' and 'held' are added.  A PPO update masks its rows
+    with 'decided'."""
     import torch
     if value_fn is None:
         raise ValueError("collect: value_fn is required")
     if not envs._ar_mode:
         raise ValueError("collect: auto-reset is off (enable_auto_reset first): a PPO batch spans episode boundaries")
+    if int(act_every) < 1:
+        raise ValueError(f"collect: act_every {act_every} < 1")
+    if int(act_every) > 1:
+        return _collect_held(envs, policy, sigma, int(n_steps), seed, step_base, value_fn, gamma, lam, walker_base,
+                             int(act_every), held)
     T, N, D, Cc, dv = int(n_steps), envs.N, envs.obs_dim, policy.C, envs.device
     f = lambda *s: torch.empty(s, dtype=torch.float32, device=dv)
     u8 = lambda *s: torch.empty(s, dtype=torch.uint8, device=dv)
