@@ -23,6 +23,11 @@ the GAE on the decision grid, `held` carried from one iteration's rollout to the
 decided ones (the mask becomes ok & decided: the density, the surrogate and the critic's loss are put on those alone); a
 row's return is the hold's summed reward plus the discounted value at the next decision.
     python scripts/ppo_train.py --act-every 4 --out profiles/r15_ppo_act_every4_balance_curve.json
+
+--hidden2 H2: a second hidden layer of H2 units between the two (MLPPolicy(wm=..., bm=...): the rollout runs through
+wg_rollout_deep, pg.policy_rows through wg_policy_forward_deep / wg_policy_backward_deep); the 64 x 64 or 32 x 32 actor of
+the PPO baselines is --hidden 64 --hidden2 64.  The middle matrix starts at 1 / sqrt(hidden).
+    python scripts/ppo_train.py --hidden 64 --hidden2 64
 """
 import argparse
 import json
@@ -46,6 +51,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--walkers", type=int, default=1024)
     ap.add_argument("--hidden", type=int, default=32)
+    ap.add_argument("--hidden2", type=int, default=0)
     ap.add_argument("--iterations", type=int, default=20)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--epochs", type=int, default=4)
@@ -70,12 +76,15 @@ def main():
     p = lambda *s, k=1.0: torch.nn.Parameter(torch.randn(s, device=dev) * k)
     nm = ObsNorm(D, dev, clip=10.0) if a.obs_norm else None
     w1, b1 = p(1, D, H, k=D ** -0.5 if nm else 0.002), torch.nn.Parameter(torch.zeros(1, H, device=dev))
-    w2, b2 = p(1, H, A, k=0.01), torch.nn.Parameter(torch.zeros(1, A, device=dev))
-    pol = MLPPolicy(w2, b2, w1, b1, obs_norm=nm)
-    assert pol.w1 is w1 and pol.w2 is w2
+    H2 = a.hidden2
+    wm, bm = (p(1, H, H2, k=H ** -0.5), torch.nn.Parameter(torch.zeros(1, H2, device=dev))) if H2 else (None, None)
+    w2, b2 = p(1, H2 or H, A, k=0.01), torch.nn.Parameter(torch.zeros(1, A, device=dev))
+    pol = MLPPolicy(w2, b2, w1, b1, obs_norm=nm, wm=wm, bm=bm)
+    assert pol.w1 is w1 and pol.w2 is w2 and pol.wm is wm
+    actor = [t for t in (w1, b1, wm, bm, w2, b2) if t is not None]
     log_sigma = torch.nn.Parameter(torch.full((A,), math.log(a.sigma), device=dev))
     critic = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to(dev)
-    opt = torch.optim.Adam([w1, b1, w2, b2, log_sigma, *critic.parameters()], lr=a.lr)
+    opt = torch.optim.Adam([*actor, log_sigma, *critic.parameters()], lr=a.lr)
     obs_scale = 1e-2   # the rows hold accelerations in the thousands: the critic sees them scaled
     if nm is not None:
         value_fn = lambda rows: critic(nm.normalize_torch(rows)).squeeze(-1)
@@ -120,7 +129,7 @@ def main():
                 loss = -(surr * mask).sum() / cnt + 0.5 * v_loss
                 opt.zero_grad(set_to_none=True)
                 loss.backward()
-                torch.nn.utils.clip_grad_norm_([w1, b1, w2, b2, log_sigma, *critic.parameters()], 0.5)
+                torch.nn.utils.clip_grad_norm_([*actor, log_sigma, *critic.parameters()], 0.5)
                 opt.step()
         if nm is not None:
             nm.update(obs, ok)
@@ -136,7 +145,7 @@ def main():
                       int((~ok & (batch["decided"] != 0)).sum()), "samples": int(ok.sum())})
         print(json.dumps(curve[-1]), flush=True)
     torch.cuda.synchronize()
-    res = {"env": "Balance-v0", "walkers": N, "hidden": H, "steps": a.steps, "iterations": a.iterations,
+    res = {"env": "Balance-v0", "walkers": N, "hidden": H, "hidden2": H2, "steps": a.steps, "iterations": a.iterations,
            "epochs": a.epochs, "minibatches": a.minibatches, "lr": a.lr, "clip": a.clip, "gamma": a.gamma,
            "lam": a.lam, "max_steps": a.max_steps, "seed": a.seed, "obs_norm": bool(a.obs_norm), "act_every": a.act_every, "seconds": time.perf_counter() - t0,
            "device": torch.cuda.get_device_name(0), "curve": curve}

@@ -15,7 +15,8 @@ torch.autograd.Function: wg_policy_forward / wg_policy_backward); walker_gym_amd
 statistics on the device (wg_obs_moments) and the normaliser MLPPolicy(obs_norm=...) evaluates in every kernel
 (wg_rollout_normalized, wg_policy_forward_normalized / wg_policy_backward_normalized); BatchedPhysicsEnv.rollout_held,
 the resident closed loop with an action hold (decide every k steps: wg_rollout_held), and pg.gae_held on its decision
-grid (wg_gae_held).
+grid (wg_gae_held); MLPPolicy(wm=..., bm=...), a second hidden layer in the rollouts and the row kernels (wg_rollout_deep,
+wg_policy_forward_deep / wg_policy_backward_deep).
 Importing the package needs no GPU; stepping does (no CPU fallback).
 """
 from .engine import Config, DingPoint, Point, to_data  # noqa: F401

@@ -116,6 +116,11 @@ class WgActionHold(C.Structure):
                 ("hold_reward_out", _vp), ("hold_reward_out_step", C.c_int64)]
 
 
+class WgPolicyMid(C.Structure):
+    """wg_policy_mid: the second hidden layer of a deep policy (wg_rollout_deep, wg_policy_forward_deep / _backward_deep)."""
+    _fields_ = [("hidden2", C.c_int32), ("wm", _vp), ("bm", _vp)]
+
+
 POLICY_GRAD_MAX_K = 16384   # WG_POLICY_GRAD_MAX_K
 
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
@@ -124,7 +129,8 @@ EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_r
            "wg_rollout_policy", "wg_rollout_episodes", "wg_fix_launches", "wg_wt_launches", "wg_es_perturb", "wg_es_update",
            "wg_rollout_stochastic", "wg_gae", "wg_policy_forward", "wg_policy_backward_workspace", "wg_policy_backward",
            "wg_es_perturb_diag", "wg_es_update_diag", "wg_rollout_normalized", "wg_policy_forward_normalized",
-           "wg_policy_backward_normalized", "wg_obs_moments_workspace", "wg_obs_moments", "wg_rollout_held", "wg_gae_held")
+           "wg_policy_backward_normalized", "wg_obs_moments_workspace", "wg_obs_moments", "wg_rollout_held", "wg_gae_held",
+           "wg_rollout_deep", "wg_policy_forward_deep", "wg_policy_backward_deep_workspace", "wg_policy_backward_deep")
 
 _lib = None
 _lock = threading.Lock()
@@ -174,6 +180,16 @@ def load(path: str | None = None):
         L.wg_rollout_held.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), C.POINTER(WgPolicy), C.POINTER(WgObsNorm),
                                       C.POINTER(WgActionNoise), C.POINTER(WgActionHold), C.POINTER(WgOutputs),
                                       C.POINTER(WgEpisodeStats), C.c_int32, _vp]
+        L.wg_rollout_deep.argtypes = [C.POINTER(WgBatch), C.POINTER(WgParams), C.POINTER(WgPolicy), C.POINTER(WgPolicyMid),
+                                      C.POINTER(WgObsNorm), C.POINTER(WgActionNoise), C.POINTER(WgActionHold),
+                                      C.POINTER(WgOutputs), C.POINTER(WgEpisodeStats), C.c_int32, _vp]
+        L.wg_policy_forward_deep.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgPolicyMid), C.POINTER(WgObsNorm),
+                                             C.POINTER(WgPolicyRows), _vp, C.c_int64, _vp]
+        L.wg_policy_backward_deep_workspace.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgPolicyMid),
+                                                        C.POINTER(WgPolicyRows), C.c_int32]
+        L.wg_policy_backward_deep.argtypes = [C.POINTER(WgPolicy), C.POINTER(WgPolicyMid), C.POINTER(WgObsNorm),
+                                              C.POINTER(WgPolicyRows), _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, _vp]
         L.wg_gae_held.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_float,
                                   _vp, _vp, _vp]
         L.wg_obs_moments_workspace.argtypes = [C.POINTER(WgPolicyRows), C.c_int32, C.c_int32]
@@ -206,6 +222,7 @@ def load(path: str | None = None):
         L.wg_fix_launches.restype = C.c_longlong
         L.wg_wt_launches.restype = C.c_longlong
         L.wg_policy_backward_workspace.restype = C.c_int64
+        L.wg_policy_backward_deep_workspace.restype = C.c_int64
         L.wg_obs_moments_workspace.restype = C.c_int64
         v = L.wg_abi_version()
         if v != ABI_VERSION:

@@ -557,7 +557,9 @@ class BatchedPhysicsEnv:
         counted}.  Walkers keep stepping after done, as in rollout(); there is no auto-reset on this path.
         Bit-identical to `for t: env.step(policy(env.obs, t))`.  A policy that carries an obs_norm
         (walker_gym_amd.normalize.ObsNorm) is evaluated on the normalised row inside the kernel (wg_rollout_normalized,
-        here and in rollout_episodes / rollout_stochastic); the rows stored in obs_out stay raw.
+        here and in rollout_episodes / rollout_stochastic); the rows stored in obs_out stay raw.  A policy with a
+        second hidden layer (MLPPolicy(wm=...)) runs through wg_rollout_deep, here and in rollout_episodes /
+        rollout_stochastic / rollout_held, with the same arguments and results.
 
         ValueError (nothing launched, no silent fallback) for a batch the resident kernel does not take (ragged, M not
         dividing 64, spring_mode or pair_mode set, WG_LEAN=0), with auto-reset enabled, or for a policy that does not
@@ -571,7 +573,9 @@ class BatchedPhysicsEnv:
         returns = torch.empty(N, dtype=torch.float32, device=dv)
         lengths = torch.empty(N, dtype=torch.int32, device=dv)
         pol.return_out, pol.length_out = _lib.ptr(returns), _lib.ptr(lengths)
-        if policy.obs_norm is not None:
+        if policy.H2:
+            self._rollout_deep(policy, pol, None, None, o, None, T)
+        elif policy.obs_norm is not None:
             self._rollout_normalized(policy, pol, None, o, None, T)
         else:
             _lib.check(_lib.load().wg_rollout_policy(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
@@ -587,6 +591,15 @@ class BatchedPhysicsEnv:
         _lib.check(_lib.load().wg_rollout_normalized(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
                                                      C.byref(nm), nz, C.byref(o), st, T, self._stream()),
                    "wg_rollout_normalized")
+
+    def _rollout_deep(self, policy, pol, nz, hold, o, st, T):
+        """The launch of a policy with a second hidden layer (wg_rollout_deep, whatever the public method): the mode is
+        the env's auto-reset setting; nz / hold / st are byref'd structs or None; the policy's ObsNorm is honoured."""
+        mid = policy.mid_struct()
+        nm = C.byref(policy.obs_norm.struct()) if policy.obs_norm is not None else None
+        _lib.check(_lib.load().wg_rollout_deep(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
+                                               C.byref(mid), nm, nz, hold, C.byref(o), st, T, self._stream()),
+                   "wg_rollout_deep")
 
     def _resident_policy(self, entry: str, auto_reset: bool, policy, n_steps, episode_slots, obs_out, reward_out,
                          done_out, action_out, reset_out=None, final_obs_out=None):
@@ -616,7 +629,7 @@ class BatchedPhysicsEnv:
         if self.N % policy.G != 0:
             raise ValueError(f"{entry}: {policy.G} parameter sets do not divide N = {self.N}; {alt}")
         dv, N, D = self.device, self.N, self.obs_dim
-        for name in ("w1", "b1", "w2", "b2"):
+        for name in ("w1", "b1", "wm", "bm", "w2", "b2"):
             t = getattr(policy, name)
             if t is not None:
                 require_tensor(t, f"policy.{name}", dv, torch.float32)
@@ -670,7 +683,9 @@ class BatchedPhysicsEnv:
                                  episodes_done=p(res["episodes"]), tail_return=p(res["tail_return"]),
                                  tail_length=p(res["tail_length"]), ep_return=p(res.get("ep_returns")),
                                  ep_length=p(res.get("ep_lengths")), ep_slots=slots)
-        if policy.obs_norm is not None:
+        if policy.H2:
+            self._rollout_deep(policy, pol, None, None, o, C.byref(st), T)
+        elif policy.obs_norm is not None:
             self._rollout_normalized(policy, pol, None, o, C.byref(st), T)
         else:
             _lib.check(_lib.load().wg_rollout_episodes(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol),
@@ -748,7 +763,9 @@ class BatchedPhysicsEnv:
                    "lengths": torch.empty(N, dtype=torch.int32, device=dv)}
             pol.return_out, pol.length_out = p(res["returns"]), p(res["lengths"])
             st = None
-        if policy.obs_norm is not None:
+        if policy.H2:
+            self._rollout_deep(policy, pol, C.byref(nz), None, o, st, T)
+        elif policy.obs_norm is not None:
             self._rollout_normalized(policy, pol, C.byref(nz), o, st, T)
         else:
             _lib.check(_lib.load().wg_rollout_stochastic(C.byref(self.batch.struct), C.byref(self._pstruct),
@@ -840,9 +857,12 @@ class BatchedPhysicsEnv:
                    "lengths": torch.empty(N, dtype=torch.int32, device=dv)}
             pol.return_out, pol.length_out = p(res["returns"]), p(res["lengths"])
             st = None
-        nm = C.byref(policy.obs_norm.struct()) if policy.obs_norm is not None else None
-        _lib.check(_lib.load().wg_rollout_held(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol), nm, nz,
-                                               C.byref(hold), C.byref(o), st, T, self._stream()), "wg_rollout_held")
+        if policy.H2:
+            self._rollout_deep(policy, pol, nz, C.byref(hold), o, st, T)
+        else:
+            nm = C.byref(policy.obs_norm.struct()) if policy.obs_norm is not None else None
+            _lib.check(_lib.load().wg_rollout_held(C.byref(self.batch.struct), C.byref(self._pstruct), C.byref(pol), nm, nz,
+                                                   C.byref(hold), C.byref(o), st, T, self._stream()), "wg_rollout_held")
         self._steps_at = -1   # (as rollout_policy(): only after the call was accepted)
         self._stale = _ROLLOUT_STALE
         res["held"] = held

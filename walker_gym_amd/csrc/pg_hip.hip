@@ -457,8 +457,230 @@ __global__ __launch_bounds__(PR_THREADS) void pr_grad_tail(const double *__restr
     dst[g * (hi - lo) + (e - lo)] = (float)S;
 }
 
+// ------------------------------------------------------------------------------------------------ deep policy rows
+// wg_policy_mid as a kernel argument of the *_deep kernels (kernels of their own: the shallow ones above keep their
+// arguments and their registers).  There a.H is H1, a.n2 = H2 and a.w2 is [H2][C].
+struct PrMid {
+    const float *wm, *bm;
+    int32_t H2;
+    int32_t Gq, Gp;                 // LDS row lengths of h2 | 1 and of dh2: up4(H2 + 1), up4(H2) (the forward: H2 | 1)
+};
+
+// The second hidden layer of the tile's rows, a thread per (row, unit k): h2 to h2s and, with dh2s,
+//   d = +0.0f; for c ascending: d = RN32(d + RN32(dy[c] * w2[k][c]));  dh2[k] = (z2[k] > 0) ? d : +0.0f
+template <bool WLDS>
+__device__ __forceinline__ void pr_mid(const PrArgs &a, const PrMid &m, const float *hs, const float *dys, const int *ok,
+                                       const int *rw, const float *lwm, const float *lbm, float *h2s, float *dh2s) {
+    for (int item = threadIdx.x; item < a.TR * m.H2; item += PR_THREADS) {
+        const int r = item / m.H2, k = item - r * m.H2;
+        if (!ok[r]) continue;
+        const int64_t g = rw[r] / a.n;
+        const float *wm = WLDS ? lwm : m.wm + g * a.H * m.H2;
+        const float *bm = WLDS ? lbm : (m.bm ? m.bm + g * m.H2 : nullptr);
+        float z[1] = {bm ? bm[k] : 0.0f};
+        const int at[1] = {k};
+        pr_chain<1>(z, hs + r * a.Hq, wm, a.H, m.H2, at);
+        const float h = z[0] > 0.0f ? z[0] : 0.0f;
+        h2s[r * m.Gq + k] = h;
+        if (dh2s) {
+            float d[1] = {0.0f};
+            const int at0[1] = {0};
+            pr_chain<1>(d, dys + r * a.Cp, a.w2 + (g * m.H2 + k) * a.C, a.C, 1, at0);
+            dh2s[r * m.Gp + k] = h > 0.0f ? d[0] : 0.0f;
+        }
+    }
+}
+
+// dh1 of the tile's rows, a thread per (row, unit j):
+//   d = +0.0f; for k ascending: d = RN32(d + RN32(dh2[k] * wm[j][k]));  dh1[j] = (z1[j] > 0) ? d : +0.0f   (h1 > 0 iff z1 > 0)
+__device__ __forceinline__ void pr_dh1(const PrArgs &a, const PrMid &m, const float *hs, const float *dh2s, const int *ok,
+                                       const int *rw, float *dhs) {
+    for (int item = threadIdx.x; item < a.TR * a.H; item += PR_THREADS) {
+        const int r = item / a.H, j = item - r * a.H;
+        if (!ok[r]) continue;
+        const int64_t g = rw[r] / a.n;
+        float d[1] = {0.0f};
+        const int at0[1] = {0};
+        pr_chain<1>(d, dh2s + r * m.Gp, m.wm + (g * a.H + j) * m.H2, m.H2, 1, at0);
+        dhs[r * a.Hp + j] = hs[r * a.Hq + j] > 0.0f ? d[0] : 0.0f;
+    }
+}
+
+// LDS, in floats: [the weights (WLDS): w1 b1 wm bm w2 b2] xs[TR][Dp] hs[TR][Hq] h2s[TR][Gq] ok[TR] rt[TR] rw[TR]
+template <bool WLDS, class NM = PrNone>
+__global__ __launch_bounds__(PR_THREADS) void pr_forward_deep(PrArgs a, PrMid m, int64_t n_tiles, int w_floats,
+                                                              float *__restrict__ y, int64_t y_step, NM nm) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *lw1 = lds, *lb1 = lw1 + a.D * a.H, *lwm = lb1 + (a.b1 ? a.H : 0), *lbm = lwm + a.H * m.H2;
+    float *lw2 = lbm + (m.bm ? m.H2 : 0), *lb2 = lw2 + m.H2 * a.C;
+    float *xs = lds + w_floats, *hs = xs + a.TR * a.Dp, *h2s = hs + a.TR * a.Hq;
+    int *ok = reinterpret_cast<int *>(h2s + a.TR * m.Gq), *rt = ok + a.TR, *rw = rt + a.TR;
+    if (WLDS) {
+        for (int i = threadIdx.x; i < a.D * a.H; i += PR_THREADS) lw1[i] = a.w1[i];
+        for (int i = threadIdx.x; i < a.H && a.b1; i += PR_THREADS) lb1[i] = a.b1[i];
+        for (int i = threadIdx.x; i < a.H * m.H2; i += PR_THREADS) lwm[i] = m.wm[i];
+        for (int i = threadIdx.x; i < m.H2 && m.bm; i += PR_THREADS) lbm[i] = m.bm[i];
+        for (int i = threadIdx.x; i < m.H2 * a.C; i += PR_THREADS) lw2[i] = a.w2[i];
+        for (int i = threadIdx.x; i < a.C && a.b2; i += PR_THREADS) lb2[i] = a.b2[i];
+    }
+    const int64_t rows = (int64_t)a.n_steps * a.N;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        pr_stage(a, tile * a.TR, rows, a.N, 0, nullptr, 0, xs, nullptr, ok, rt, rw, nm);
+        __syncthreads();
+        pr_hidden<WLDS, false>(a, xs, nullptr, ok, rw, lw1, a.b1 ? lb1 : nullptr, hs, nullptr);
+        __syncthreads();
+        pr_mid<WLDS>(a, m, hs, nullptr, ok, rw, lwm, m.bm ? lbm : nullptr, h2s, nullptr);
+        __syncthreads();
+        for (int item = threadIdx.x; item < a.TR * a.C; item += PR_THREADS) {
+            const int r = item / a.C, c = item - r * a.C;
+            if (!ok[r]) continue;
+            const int64_t g = rw[r] / a.n;
+            const float *w2 = WLDS ? lw2 : a.w2 + g * m.H2 * a.C;
+            const float *b2 = WLDS ? (a.b2 ? lb2 : nullptr) : (a.b2 ? a.b2 + g * a.C : nullptr);
+            float acc[1] = {b2 ? b2[c] : 0.0f};
+            const int at[1] = {c};
+            pr_chain<1>(acc, h2s + r * m.Gq, w2, m.H2, a.C, at);
+            y[(int64_t)rt[r] * y_step + (int64_t)rw[r] * a.C + c] = acc[0];
+        }
+        __syncthreads();
+    }
+}
+
+// LDS, in floats: xs[TR][Dp] hs[TR][Hq] dhs[TR][Hp] h2s[TR][Gq] dh2s[TR][Gp] dys[TR][Cp] ok[TR] rt[TR] rw[TR]
+// Block q of the workgroup's list: q < T1 the product (x|1) (x) dh1, then the Tm blocks of (h1|1) (x) dh2, then the T2
+// blocks of (h2|1) (x) dy; rows 4 * (q' / JT) .., columns 4 * (q' % JT) .. of its product; thread tid owns blocks tid,
+// tid + 256, ...  T1 == 0: dh1 is not formed; T1 == 0 and Tm == 0: neither is dh2.
+template <int NT, class NM = PrNone>
+__global__ __launch_bounds__(PR_THREADS) void pr_grad_partial_deep(PrArgs a, PrMid m, const float *__restrict__ dy,
+                                                                   int64_t dy_step, int32_t chunk_rows, int64_t n_chunks,
+                                                                   int32_t T1, int32_t Tm, double *__restrict__ ws,
+                                                                   int32_t K, NM nm) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *xs = lds, *hs = xs + a.TR * a.Dp, *dhs = hs + a.TR * a.Hq, *h2s = dhs + a.TR * a.Hp;
+    float *dh2s = h2s + a.TR * m.Gq, *dys = dh2s + a.TR * m.Gp;
+    int *ok = reinterpret_cast<int *>(dys + a.TR * a.Cp), *rt = ok + a.TR, *rw = rt + a.TR;
+    const int g = (int)(blockIdx.x / n_chunks);
+    const int64_t k = blockIdx.x - (int64_t)g * n_chunks;
+    const int64_t lo = k * chunk_rows, set_rows = (int64_t)a.n_steps * a.n;
+    const int64_t hi = set_rows - lo < chunk_rows ? set_rows : lo + chunk_rows;
+
+    // the padding that no tile rewrites: hs[r][H] = h2s[r][H2] = 1 (the bias rows), zeros behind them and behind dh1, dh2
+    // (the whole dh rows: a product whose dh is not formed is not accumulated, but nothing is left unwritten)
+    for (int r = threadIdx.x; r < a.TR; r += PR_THREADS) {
+        for (int j = a.H; j < a.Hq; j++) hs[r * a.Hq + j] = j == a.H ? 1.0f : 0.0f;
+        for (int j = 0; j < a.Hp; j++) dhs[r * a.Hp + j] = 0.0f;
+        for (int j = m.H2; j < m.Gq; j++) h2s[r * m.Gq + j] = j == m.H2 ? 1.0f : 0.0f;
+        for (int j = 0; j < m.Gp; j++) dh2s[r * m.Gp + j] = 0.0f;
+    }
+
+    const int JT1 = a.Hp >> 2, JTm = m.Gp >> 2, JT2 = a.Cp >> 2, T2 = (m.Gq >> 2) * JT2;
+    const float *pa[NT], *pb[NT];
+    int sa[NT], sb[NT];
+#pragma unroll
+    for (int u = 0; u < NT; u++) {
+        const int q = (int)threadIdx.x + u * PR_THREADS;
+        if (q < T1) {
+            pa[u] = xs + 4 * (q / JT1); sa[u] = a.Dp;
+            pb[u] = dhs + 4 * (q % JT1); sb[u] = a.Hp;
+        } else if (q < T1 + Tm) {
+            const int qm = q - T1;
+            pa[u] = hs + 4 * (qm / JTm); sa[u] = a.Hq;
+            pb[u] = dh2s + 4 * (qm % JTm); sb[u] = m.Gp;
+        } else {
+            const int q2 = q - T1 - Tm < T2 ? q - T1 - Tm : 0;      // a thread past the list repeats block 0 and drops it
+            pa[u] = h2s + 4 * (q2 / JT2); sa[u] = m.Gq;
+            pb[u] = dys + 4 * (q2 % JT2); sb[u] = a.Cp;
+        }
+    }
+    double acc[NT][4][4];
+#pragma unroll
+    for (int u = 0; u < NT; u++)
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[u][i][j] = 0.0;
+
+    for (int64_t base = lo; base < hi; base += a.TR) {
+        pr_stage(a, base, hi, a.n, g * a.n, dy, dy_step, xs, dys, ok, rt, rw, nm);
+        __syncthreads();
+        pr_hidden<false, false>(a, xs, dys, ok, rw, nullptr, nullptr, hs, nullptr);
+        __syncthreads();
+        pr_mid<false>(a, m, hs, dys, ok, rw, nullptr, nullptr, h2s, (T1 || Tm) ? dh2s : nullptr);
+        __syncthreads();
+        if (T1) {
+            pr_dh1(a, m, hs, dh2s, ok, rw, dhs);
+            __syncthreads();
+        }
+        for (int r = 0; r < a.TR; r++) {
+            if (!ok[r]) continue;
+#pragma unroll
+            for (int u = 0; u < NT; u++) {
+                const float4 va = *reinterpret_cast<const float4 *>(pa[u] + r * sa[u]);
+                const float4 vb = *reinterpret_cast<const float4 *>(pb[u] + r * sb[u]);
+                const double da[4] = {va.x, va.y, va.z, va.w}, db[4] = {vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) acc[u][i][j] = fma(da[i], db[j], acc[u][i][j]);
+            }
+        }
+        __syncthreads();
+    }
+
+    // the segment order: w1 [D][H], b1 [H] (if set), wm [H][H2], bm [H2] (if set), w2 [H2][C], b2 [C] (if set)
+    double *out = ws + ((int64_t)g * n_chunks + k) * K;
+    const int basem = a.D * a.H + (a.b1 ? a.H : 0);
+    const int base2 = basem + a.H * m.H2 + (m.bm ? m.H2 : 0);
+#pragma unroll
+    for (int u = 0; u < NT; u++) {
+        const int q = (int)threadIdx.x + u * PR_THREADS;
+        int i0, j0, I, J, off;
+        bool bias;
+        if (q < T1) {
+            i0 = 4 * (q / JT1); j0 = 4 * (q % JT1); I = a.D; J = a.H; off = 0; bias = a.b1 != nullptr;
+        } else if (q < T1 + Tm) {
+            const int qm = q - T1;
+            i0 = 4 * (qm / JTm); j0 = 4 * (qm % JTm); I = a.H; J = m.H2; off = basem; bias = m.bm != nullptr;
+        } else {
+            const int q2 = q - T1 - Tm;
+            if (q2 >= T2) continue;
+            i0 = 4 * (q2 / JT2); j0 = 4 * (q2 % JT2); I = m.H2; J = a.C; off = base2; bias = a.b2 != nullptr;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int ii = i0 + i, jj = j0 + j;
+                if (jj < J && (ii < I || (ii == I && bias))) out[off + ii * J + jj] = acc[u][i][j];
+            }
+    }
+}
+
+struct PrGrads6 {
+    float *g[6];        // w1, b1, wm, bm, w2, b2 (NULL: not wanted)
+    int32_t end[6];     // the segments' ends in [0, K]
+};
+
+__global__ __launch_bounds__(PR_THREADS) void pr_grad_tail_deep(const double *__restrict__ ws, PrGrads6 o, int32_t K,
+                                                                int64_t n_chunks, int64_t total) {
+    const int64_t idx = (int64_t)blockIdx.x * PR_THREADS + threadIdx.x;
+    if (idx >= total) return;
+    const int64_t g = idx / K;
+    const int e = (int)(idx - g * K);
+    float *dst = o.g[5];
+    int lo = o.end[4], hi = o.end[5];
+#pragma unroll
+    for (int s = 4; s >= 0; s--)   // (the first segment that holds e; constant indices: the argument stays in SGPRs)
+        if (e < o.end[s]) dst = o.g[s], lo = s ? o.end[s - 1] : 0, hi = o.end[s];
+    if (!dst) return;
+    const double *p = ws + g * n_chunks * K + e;
+    double S = 0.0;
+    for (int64_t c = 0; c < n_chunks; c++) S = __dadd_rn(S, p[c * K]);
+    dst[g * (hi - lo) + (e - lo)] = (float)S;
+}
+
 // ------------------------------------------------------------------------------------------------ observation moments
-constexpr int OM_ROWS = 64;   // rows per tile, at most
+constexpr int OM_ROWS = 64;  // rows per tile, at most
 constexpr int OM_U = 4;       // rows whose loads a wave issues before their LDS stores
 constexpr int OM_NC = 4;      // columns per thread and pass: two float64 chains each
 
@@ -773,6 +995,167 @@ int policy_backward(const char *who, const wg_policy *pol, const wg_obs_norm *nm
     return wg_launched(norm ? "wg_policy_backward_normalized (tail): launch" : "wg_policy_backward (tail): launch");
 }
 
+// ---- deep policy rows: host
+struct PrPlanDeep {
+    PrPlan p;             // a.H = H1, a.n2 = H2; K over the six segments; p.end unused
+    PrMid m;
+    int32_t end[6];       // the ends of w1, b1, wm, bm, w2, b2 in [0, K]
+    int32_t T1, Tm, T2;   // 4 x 4 blocks of the three outer products
+};
+
+// pr_check and the middle layer's own refusals; fills the plan (TR stays 0).
+int pr_check_deep(const wg_policy *pol, const wg_policy_mid *mid, const wg_policy_rows *rows, const char *who,
+                  PrPlanDeep *pl) {
+    if (const int rc = pr_check(pol, rows, who, &pl->p)) return rc;
+    if (!mid) return wg_fail(WG_EINVAL, "%s: null middle layer", who);
+    if (mid->hidden2 < 1 || mid->hidden2 > 256) return wg_fail(WG_EINVAL, "%s: hidden2 %d outside 1..256", who, mid->hidden2);
+    if (!mid->wm) return wg_fail(WG_EINVAL, "%s: null wm", who);
+    if (pol->hidden == 0) return wg_fail(WG_EINVAL, "%s: a middle layer needs hidden > 0", who);
+    PrArgs &a = pl->p.a;
+    const int32_t H2 = mid->hidden2;
+    a.n2 = H2;
+    pl->m = PrMid{mid->wm, mid->bm, H2, up4(H2 + 1), up4(H2)};
+    const int32_t seg[6] = {a.D * a.H, a.b1 ? a.H : 0, a.H * H2, mid->bm ? H2 : 0, H2 * a.C, a.b2 ? a.C : 0};
+    int32_t at = 0;
+    for (int i = 0; i < 6; i++) pl->end[i] = (at += seg[i]);
+    pl->p.K = at;
+    return 0;
+}
+
+int pr_inputs_deep(const PrPlanDeep &pl, PrBuf *in) {
+    const PrArgs &a = pl.p.a;
+    const int64_t G = pl.p.n_sets;
+    int n = pr_inputs(pl.p, in);      // (w2 over a.n2 = H2 inputs)
+    in[n++] = {"wm", pl.m.wm, span_of(pl.m.wm, 1, G * a.H * pl.m.H2, 0, 4)};
+    if (pl.m.bm) in[n++] = {"bm", pl.m.bm, span_of(pl.m.bm, 1, G * pl.m.H2, 0, 4)};
+    return n;
+}
+
+int pr_backward_plan_deep(PrPlanDeep *pl, int32_t chunk_rows, const char *who, int64_t *n_chunks) {
+    if (chunk_rows < 1) return wg_fail(WG_EINVAL, "%s: chunk_rows %d < 1", who, chunk_rows);
+    PrArgs &a = pl->p.a;
+    const PrMid &m = pl->m;
+    const int64_t t1 = (int64_t)(a.Dp / 4) * (a.Hp / 4), tm = (int64_t)(a.Hq / 4) * (m.Gp / 4),
+                  t2 = (int64_t)(m.Gq / 4) * (a.Cp / 4);
+    if (pl->p.K > WG_POLICY_GRAD_MAX_K || 16 * (t1 + tm + t2) > WG_POLICY_GRAD_MAX_K)
+        return wg_fail(WG_ERANGE, "%s: %lld parameters per set, %lld in 4 x 4 blocks (at most WG_POLICY_GRAD_MAX_K = %d)",
+                       who, (long long)pl->p.K, (long long)(16 * (t1 + tm + t2)), WG_POLICY_GRAD_MAX_K);
+    pl->T1 = (int32_t)t1; pl->Tm = (int32_t)tm; pl->T2 = (int32_t)t2;
+    const int row = 4 * (a.Dp + a.Hq + a.Hp + m.Gq + m.Gp + a.Cp) + 12;
+    a.TR = PR_LDS / row < PR_BWD_ROWS ? PR_LDS / row : PR_BWD_ROWS;
+    if (a.TR < 1) return wg_fail(WG_ERANGE, "%s: one row needs %d B of LDS (> 64 KiB)", who, row);
+    *n_chunks = ((int64_t)a.n_steps * a.n + chunk_rows - 1) / chunk_rows;
+    if (*n_chunks * pl->p.n_sets > INT32_MAX)
+        return wg_fail(WG_ERANGE, "%s: %lld chunks in %d sets pass 2^31 workgroups", who, (long long)*n_chunks,
+                       pl->p.n_sets);
+    return 0;
+}
+
+int policy_forward_deep(const char *who, const wg_policy *pol, const wg_policy_mid *mid, const wg_obs_norm *nm,
+                        const wg_policy_rows *rows, float *y, int64_t y_step, hipStream_t stream) {
+    PrPlanDeep pl;
+    if (const int rc = pr_check_deep(pol, mid, rows, who, &pl)) return rc;
+    PrArgs &a = pl.p.a;
+    PrMid &m = pl.m;
+    if (!y) return wg_fail(WG_EINVAL, "%s: null y", who);
+    if (y_step < (int64_t)a.N * a.C)
+        return wg_fail(WG_EINVAL, "%s: y_step %lld < N * act_dim = %lld", who, (long long)y_step, (long long)a.N * a.C);
+    PrBuf in[10];
+    int n_in = pr_inputs_deep(pl, in);
+    if (nm)
+        if (const int rc = pr_norm_check(nm, pl.p, who, in, &n_in)) return rc;
+    const Span sy = span_of(y, a.n_steps, (int64_t)a.N * a.C, y_step, 4);
+    for (int i = 0; i < n_in; i++)
+        if (overlap(sy, in[i].s)) return wg_fail(WG_EINVAL, "%s: y aliases %s", who, in[i].name);
+    a.Dp = a.D | 1; a.Hq = a.H | 1; m.Gq = m.H2 | 1;   // odd row lengths: the rows of a wave fall on distinct LDS banks
+    const bool stage = pl.p.n_sets == 1 && pl.p.K * 4 <= PR_W_LDS;   // (the middle matrix counted)
+    const int w_floats = stage ? up4((int)pl.p.K) : 0;
+    const int row = 4 * (a.Dp + a.Hq + m.Gq) + 12, room = PR_LDS - 4 * w_floats;
+    a.TR = room / row < PR_FWD_ROWS ? room / row : PR_FWD_ROWS;
+    if (a.TR < 1) return wg_fail(WG_ERANGE, "%s: one row needs %d B of LDS (> %d)", who, row, room);
+    const int64_t n_tiles = ((int64_t)a.n_steps * a.N + a.TR - 1) / a.TR;
+    const int64_t cap = stage ? 2048 : 1 << 20;
+    const dim3 grid((unsigned)(n_tiles < cap ? n_tiles : cap));
+    const size_t lds = (size_t)4 * w_floats + (size_t)a.TR * row;
+    if (nm) {
+        const PrNorm kn{nm->mean, nm->scale, nm->clip};
+        if (stage) pr_forward_deep<true, PrNorm><<<grid, PR_THREADS, lds, stream>>>(a, m, n_tiles, w_floats, y, y_step, kn);
+        else pr_forward_deep<false, PrNorm><<<grid, PR_THREADS, lds, stream>>>(a, m, n_tiles, w_floats, y, y_step, kn);
+    } else {
+        if (stage) pr_forward_deep<true><<<grid, PR_THREADS, lds, stream>>>(a, m, n_tiles, w_floats, y, y_step, PrNone{});
+        else pr_forward_deep<false><<<grid, PR_THREADS, lds, stream>>>(a, m, n_tiles, w_floats, y, y_step, PrNone{});
+    }
+    return wg_launched("wg_policy_forward_deep: launch");
+}
+
+int policy_backward_deep(const char *who, const wg_policy *pol, const wg_policy_mid *mid, const wg_obs_norm *nm,
+                         const wg_policy_rows *rows, const float *dy, int64_t dy_step, int32_t chunk_rows,
+                         double *workspace, float *g_w1, float *g_b1, float *g_wm, float *g_bm, float *g_w2, float *g_b2,
+                         hipStream_t stream) {
+    PrPlanDeep pl;
+    int64_t n_chunks;
+    if (const int rc = pr_check_deep(pol, mid, rows, who, &pl)) return rc;
+    PrArgs &a = pl.p.a;
+    const PrMid &m = pl.m;
+    if (!dy) return wg_fail(WG_EINVAL, "%s: null dy", who);
+    if (!workspace) return wg_fail(WG_EINVAL, "%s: null workspace", who);
+    if (dy_step < (int64_t)a.N * a.C)
+        return wg_fail(WG_EINVAL, "%s: dy_step %lld < N * act_dim = %lld", who, (long long)dy_step, (long long)a.N * a.C);
+    if (!g_w1 && !g_b1 && !g_wm && !g_bm && !g_w2 && !g_b2)
+        return wg_fail(WG_EINVAL, "%s: every gradient pointer is null", who);
+    if (g_b1 && !a.b1) return wg_fail(WG_EINVAL, "%s: g_b1 of a policy without b1", who);
+    if (g_bm && !m.bm) return wg_fail(WG_EINVAL, "%s: g_bm of a policy without bm", who);
+    if (g_b2 && !a.b2) return wg_fail(WG_EINVAL, "%s: g_b2 of a policy without b2", who);
+    if (const int rc = pr_backward_plan_deep(&pl, chunk_rows, who, &n_chunks)) return rc;
+    PrBuf in[11], out[7];
+    int n_in = pr_inputs_deep(pl, in), n_out = 0;
+    in[n_in++] = {"dy", dy, span_of(dy, a.n_steps, (int64_t)a.N * a.C, dy_step, 4)};
+    if (nm)
+        if (const int rc = pr_norm_check(nm, pl.p, who, in, &n_in)) return rc;
+    const int64_t G = pl.p.n_sets;
+    out[n_out++] = {"workspace", workspace, span_of(workspace, 1, G * n_chunks * pl.p.K, 0, 8)};
+    if (g_w1) out[n_out++] = {"g_w1", g_w1, span_of(g_w1, 1, G * a.D * a.H, 0, 4)};
+    if (g_b1) out[n_out++] = {"g_b1", g_b1, span_of(g_b1, 1, G * a.H, 0, 4)};
+    if (g_wm) out[n_out++] = {"g_wm", g_wm, span_of(g_wm, 1, G * a.H * m.H2, 0, 4)};
+    if (g_bm) out[n_out++] = {"g_bm", g_bm, span_of(g_bm, 1, G * m.H2, 0, 4)};
+    if (g_w2) out[n_out++] = {"g_w2", g_w2, span_of(g_w2, 1, G * m.H2 * a.C, 0, 4)};
+    if (g_b2) out[n_out++] = {"g_b2", g_b2, span_of(g_b2, 1, G * a.C, 0, 4)};
+    for (int o = 0; o < n_out; o++) {
+        for (int i = 0; i < n_in; i++)
+            if (overlap(out[o].s, in[i].s)) return wg_fail(WG_EINVAL, "%s: %s aliases %s", who, out[o].name, in[i].name);
+        for (int p = 0; p < o; p++)
+            if (overlap(out[o].s, out[p].s)) return wg_fail(WG_EINVAL, "%s: %s aliases %s", who, out[o].name, out[p].name);
+    }
+    // without g_w1 / g_b1 neither dh1 nor the first product is computed; without g_wm / g_bm too, neither is dh2
+    const int32_t T1 = (g_w1 || g_b1) ? pl.T1 : 0, Tm = (g_wm || g_bm) ? pl.Tm : 0;
+    const int nt = (T1 + Tm + pl.T2 + PR_THREADS - 1) / PR_THREADS;
+    const size_t lds = (size_t)a.TR * (4 * (a.Dp + a.Hq + a.Hp + m.Gq + m.Gp + a.Cp) + 12);
+    const dim3 grid((unsigned)(n_chunks * G));
+    const int32_t K = (int32_t)pl.p.K;
+    auto go = [&](auto kernel, auto kn) {
+        kernel<<<grid, PR_THREADS, lds, stream>>>(a, m, dy, dy_step, chunk_rows, n_chunks, T1, Tm, workspace, K, kn);
+    };
+    if (nm) {
+        const PrNorm kn{nm->mean, nm->scale, nm->clip};
+        if (nt <= 1) go(pr_grad_partial_deep<1, PrNorm>, kn);
+        else if (nt == 2) go(pr_grad_partial_deep<2, PrNorm>, kn);
+        else if (nt == 3) go(pr_grad_partial_deep<3, PrNorm>, kn);
+        else go(pr_grad_partial_deep<4, PrNorm>, kn);
+    } else {
+        if (nt <= 1) go(pr_grad_partial_deep<1>, PrNone{});
+        else if (nt == 2) go(pr_grad_partial_deep<2>, PrNone{});
+        else if (nt == 3) go(pr_grad_partial_deep<3>, PrNone{});
+        else go(pr_grad_partial_deep<4>, PrNone{});
+    }
+    if (const int rc = wg_launched("wg_policy_backward_deep (partial sums): launch")) return rc;
+    PrGrads6 o{{g_w1, g_b1, g_wm, g_bm, g_w2, g_b2},
+               {pl.end[0], pl.end[1], pl.end[2], pl.end[3], pl.end[4], pl.end[5]}};
+    const int64_t total = G * K;
+    pr_grad_tail_deep<<<(unsigned)((total + PR_THREADS - 1) / PR_THREADS), PR_THREADS, 0, stream>>>(workspace, o, K,
+                                                                                                  n_chunks, total);
+    return wg_launched("wg_policy_backward_deep (tail): launch");
+}
+
 // wg_obs_moments' checks, shared with wg_obs_moments_workspace; fills the kernel's arguments and the chunk count.
 int om_check(const wg_policy_rows *rows, int32_t obs_dim, int32_t chunk_rows, const char *who, OmArgs *a,
              int64_t *n_chunks) {
@@ -911,6 +1294,28 @@ int wg_policy_backward_normalized(const wg_policy *pol, const wg_obs_norm *nm, c
                                   float *g_b1, float *g_w2, float *g_b2, hipStream_t stream) {
     return policy_backward("wg_policy_backward_normalized", pol, nm, true, rows, dy, dy_step, chunk_rows, workspace, g_w1,
                            g_b1, g_w2, g_b2, stream);
+}
+
+int wg_policy_forward_deep(const wg_policy *pol, const wg_policy_mid *mid, const wg_obs_norm *nm,
+                           const wg_policy_rows *rows, float *y, int64_t y_step, hipStream_t stream) {
+    return policy_forward_deep("wg_policy_forward_deep", pol, mid, nm, rows, y, y_step, stream);
+}
+
+int64_t wg_policy_backward_deep_workspace(const wg_policy *pol, const wg_policy_mid *mid, const wg_policy_rows *rows,
+                                          int32_t chunk_rows) {
+    PrPlanDeep pl;
+    int64_t n_chunks;
+    if (const int rc = pr_check_deep(pol, mid, rows, "wg_policy_backward_deep_workspace", &pl)) return rc;
+    if (const int rc = pr_backward_plan_deep(&pl, chunk_rows, "wg_policy_backward_deep_workspace", &n_chunks)) return rc;
+    return (int64_t)pl.p.n_sets * n_chunks * pl.p.K;
+}
+
+int wg_policy_backward_deep(const wg_policy *pol, const wg_policy_mid *mid, const wg_obs_norm *nm,
+                            const wg_policy_rows *rows, const float *dy, int64_t dy_step, int32_t chunk_rows,
+                            double *workspace, float *g_w1, float *g_b1, float *g_wm, float *g_bm, float *g_w2,
+                            float *g_b2, hipStream_t stream) {
+    return policy_backward_deep("wg_policy_backward_deep", pol, mid, nm, rows, dy, dy_step, chunk_rows, workspace, g_w1,
+                                g_b1, g_wm, g_bm, g_w2, g_b2, stream);
 }
 
 int64_t wg_obs_moments_workspace(const wg_policy_rows *rows, int32_t obs_dim, int32_t chunk_rows) {

@@ -3021,6 +3021,15 @@ struct KHold {
     int off_hr;                    // byte offset in the wave's LDS slice: one float per walker, the open hold's reward
 };
 
+// The middle layer of wg_rollout_deep (wg_policy_mid): the DEEP instances of walker_rollout_policy take it as one more
+// trailing kernel argument (the other instances take the empty KNoReset).  The second hidden vector has a region of its
+// own in the slice; a shared policy's staged weights are then w1 | wm | w2.
+struct KDeep {
+    const float *wm, *bm;          // [n_sets][H][H2], [n_sets][H2] (bm NULL = +0.0)
+    int H2;
+    int off_h2;                    // byte offset in the wave's LDS slice: the second hidden vectors
+};
+
 // One unit of a layer, the contract's chain: acc = bias; acc = RN32(acc + RN32(x[i] * w[i][j])) for i ascending, the
 // multiply and the add separate roundings (no FMA).  x: the walker's input vector in LDS (the same address in every lane
 // of the walker: a broadcast); w: column j of the set's [n][stride] matrix.
@@ -3088,11 +3097,15 @@ __device__ __forceinline__ void policy_unit2(const float *x, const float *__rest
 // lanes run the layers: the others load no weight, make no Philox call and store nothing, so their actions in the slice
 // stay the held ones, which is what their muscle lanes get back.  NZ and NM are then both given and each is in force
 // iff its first pointer is set (wave-uniform): one HOLD instance serves the four forms, with the arithmetic of each.
-template <bool IN3D, int WS = 4, class NZ = KNoReset, class NM = KNoReset, bool HOLD = false>
+// DP = KDeep (wg_rollout_deep): a second hidden layer between the two, lane q taking units q, q + M, ... of H2 two at a
+// time over the walker's first hidden vector, ReLU into a second LDS region, and the output layer over that.
+template <bool IN3D, int WS = 4, class NZ = KNoReset, class NM = KNoReset, bool HOLD = false, class DP = KNoReset>
 __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &kp, const KPolicy &pol, const LeanGeo &lg,
                                              char *smem, char *sl, const LeanTile &t, const float *p3, const float *v3,
                                              const LeanPolOut &ps, float x, float *act_dst, const NZ &nz = NZ{},
-                                             int s = 0, const NM &nm = NM{}, unsigned long long db = ~0ull) {
+                                             int s = 0, const NM &nm = NM{}, unsigned long long db = ~0ull,
+                                             const DP &dp = DP{}) {
+    constexpr bool DEEP = std::is_same<DP, KDeep>::value;
     const int M = b.M, D = pol.D, H = pol.H, C = pol.C;
     // the lanes that run the layers: the tile's mass lanes, under a hold those of the deciding walkers
     const bool run = HOLD ? (t.is_mass && ((db >> ((t.wl * M) & 63)) & 1ull) != 0ull) : t.is_mass;
@@ -3141,12 +3154,37 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
         xin = hid + t.wl * H;
         n = H;
     }
+    int w2_at = D * H;   // the output matrix in the staged weights
+    if constexpr (DEEP) {   // (H > 0: the host refuses a middle layer without a first one)
+        const int H2 = dp.H2;
+        float *hid2 = reinterpret_cast<float *>(sl + dp.off_h2);
+        if (run) {
+            for (int j = t.q; j < H2; j += 2 * M) {
+                const bool two = j + M < H2;
+                const int d = two ? M : 0;
+                const float *bp = dp.bm ? dp.bm + (size_t)gset * (size_t)H2 + j : nullptr;
+                const float bias0 = bp ? bp[0] : 0.f, bias1 = bp ? bp[d] : 0.f;
+                float z0, z1;
+                if (pol.off_wts >= 0)
+                    policy_unit2(xin, reinterpret_cast<const float *>(smem + pol.off_wts) + D * H + j, H, H2, d, bias0, bias1,
+                                 z0, z1);
+                else
+                    policy_unit2(xin, dp.wm + (size_t)gset * (size_t)H * (size_t)H2 + j, H, H2, d, bias0, bias1, z0, z1);
+                hid2[t.wl * H2 + j] = (z0 > 0.f) ? z0 : 0.f;   // (a NaN becomes +0)
+                if (two) hid2[t.wl * H2 + j + M] = (z1 > 0.f) ? z1 : 0.f;
+            }
+        }
+        wave_sync();
+        xin = hid2 + t.wl * H2;
+        n = H2;
+        w2_at = D * H + H * H2;
+    }
     if (run) {
         const float lim = pol.act_limit;
         for (int j = t.q; j < C; j += M) {
             const float bias = pol.b2 ? pol.b2[(size_t)gset * (size_t)C + j] : 0.f;
             const float y = pol.off_wts >= 0
-                                ? policy_unit(xin, reinterpret_cast<const float *>(smem + pol.off_wts) + D * H + j, n, C,
+                                ? policy_unit(xin, reinterpret_cast<const float *>(smem + pol.off_wts) + w2_at + j, n, C,
                                               bias)
                                 : policy_unit(xin, pol.w2 + (size_t)gset * (size_t)n * (size_t)C + j, n, C, bias);
             float u = y;
@@ -3189,7 +3227,10 @@ __device__ __forceinline__ float lean_policy(const wg_batch &b, const KParams &k
 // lanes store every step's action_out row from their registers.  The running hold reward is one more LDS word per
 // walker, kept by lane q == 0.  Instantiated with NZ and ON both set: the noise and the normaliser are in force iff
 // their pointers are, so 40 instances serve the four forms of either mode (see DESIGN 9i for the cost).
-template <bool IN3D, int NE, bool E8, bool AR = false, bool NZ = false, bool ON = false, bool HOLD = false>
+// DEEP (wg_rollout_deep): the policy's second hidden layer (lean_policy), on the HOLD family only: 40 more instances
+// serve every form of either mode, with or without a hold.
+template <bool IN3D, int NE, bool E8, bool AR = false, bool NZ = false, bool ON = false, bool HOLD = false,
+          bool DEEP = false>
 // (register budget: one wave per SIMD fewer than walker_rollout_lean.  The LDS slice with the rows already holds the
 // canonical walker to 4 waves per SIMD, the NE 8 shapes to 2, and the latency-bound NE 1 batches run one)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3 : 4))) void walker_rollout_policy(
@@ -3198,16 +3239,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
     typename std::conditional<AR, wg_episode_stats, KNoReset>::type st,
     typename std::conditional<NZ, KNoise, KNoReset>::type nz,
     typename std::conditional<ON, KObsNorm, KNoReset>::type nm,
-    typename std::conditional<HOLD, KHold, KNoReset>::type hd) {
+    typename std::conditional<HOLD, KHold, KNoReset>::type hd,
+    typename std::conditional<DEEP, KDeep, KNoReset>::type dp) {
     static_assert(!HOLD || (NZ && ON), "the HOLD instances carry the noise and the normaliser as runtime options");
+    static_assert(!DEEP || HOLD, "the DEEP instances are HOLD instances");
     constexpr int WS = AR ? 8 : 4;   // LDS words per walker
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int tile = blockIdx.x * lg.wpb + wv;
     if (pol.off_wts >= 0) {   // a shared policy: its weights into the workgroup's LDS once, by every wave of it
         float *sw = reinterpret_cast<float *>(smem + pol.off_wts);
-        const int n1 = pol.D * pol.H, n2 = (pol.H > 0 ? pol.H : pol.D) * pol.C;
+        int n1 = pol.D * pol.H, n2 = (pol.H > 0 ? pol.H : pol.D) * pol.C;
         for (int i = threadIdx.x; i < n1; i += 64 * lg.wpb) sw[i] = pol.w1[i];
+        if constexpr (DEEP) {   // w1 | wm | w2, w2 over H2 inputs
+            const int nm_ = pol.H * dp.H2;
+            for (int i = threadIdx.x; i < nm_; i += 64 * lg.wpb) sw[n1 + i] = dp.wm[i];
+            n1 += nm_;
+            n2 = dp.H2 * pol.C;
+        }
         for (int i = threadIdx.x; i < n2; i += 64 * lg.wpb) sw[n1 + i] = pol.w2[i];
         __syncthreads();      // (the only workgroup barrier: the waves run on their own from here)
     }
@@ -3275,9 +3324,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NE >= 8 ? 3
         unsigned long long db = ~0ull;   // (HOLD) lane q == 0 of every walker that decides at this step
         if constexpr (HOLD) {
             db = __ballot(ts.is_mass && ts.q == 0 && (uint32_t)L.wsteps % (uint32_t)hd.every == 0u);
-            if (db != 0ull)   // wave-uniform
-                L.a = lean_policy<IN3D, WS, KNoise, KObsNorm, true>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x,
-                                                                    nullptr, nz, s, nm, db);
+            if (db != 0ull) {   // wave-uniform
+                if constexpr (DEEP)
+                    L.a = lean_policy<IN3D, WS, KNoise, KObsNorm, true, KDeep>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps,
+                                                                               L.x, nullptr, nz, s, nm, db, dp);
+                else
+                    L.a = lean_policy<IN3D, WS, KNoise, KObsNorm, true>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x,
+                                                                        nullptr, nz, s, nm, db);
+            }
             if (act_dst && ts.acts)   // the action applied, deciding or held
                 act_dst[(size_t)(uint32_t)(ts.w0 + ts.mu_wl) * (size_t)pol.C + ts.mu_ua] = L.a;
         } else if constexpr (ON) L.a = lean_policy<IN3D, WS>(b, kp, pol, lg, smem, sl, ts, L.p3, L.v3, ps, L.x, act_dst, nz, s, nm);
@@ -3801,6 +3855,13 @@ int wg_rollout_held(const wg_batch *b, const wg_params *p, const wg_policy *pol,
                     const wg_episode_stats *st, int32_t n_steps, hipStream_t stream) {
     return rollout_policy(b, p, pol, o, n_steps, stream, p && p->auto_reset != 0, st, nz != nullptr, nz, nm != nullptr, nm,
                           true, hold);
+}
+int wg_rollout_deep(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_policy_mid *mid,
+                    const wg_obs_norm *nm, const wg_action_noise *nz, const wg_action_hold *hold, const wg_outputs *o,
+                    const wg_episode_stats *st, int32_t n_steps, hipStream_t stream) {
+    const wg_action_hold every1{1, nullptr, nullptr, 0, nullptr, 0};   // (no hold: every walker decides at every step)
+    return rollout_policy(b, p, pol, o, n_steps, stream, p && p->auto_reset != 0, st, nz != nullptr, nz, nm != nullptr, nm,
+                          true, hold ? hold : &every1, true, mid);
 }
 
 int wg_run_ranges(const wg_range *ranges, int32_t n, const wg_params *p, const float *action, int32_t action_cols,

@@ -424,11 +424,14 @@ bool host_overlap(const HostSpan &a, const HostSpan &c) {
 // `nm`.
 // held (wg_rollout_held): the mode and the form by p->auto_reset, nz and nm as above, the HOLD instances (which carry the
 // noise and the normaliser as runtime options), the checks of `hold`, and one more word per walker in the slice.
+// deep (wg_rollout_deep): held with the middle layer of `mid`: the DEEP instances, the checks of `mid`, hidden2 more words
+// per walker in the slice (the second hidden vector), and the middle matrix among a shared policy's staged weights.
 int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, const wg_outputs *o, int32_t n_steps,
                    hipStream_t stream, bool episodes = false, const wg_episode_stats *st = nullptr,
                    bool stochastic = false, const wg_action_noise *nz = nullptr, bool normalized = false,
-                   const wg_obs_norm *nm = nullptr, bool held = false, const wg_action_hold *hold = nullptr) {
-    const char *fn = held ? "wg_rollout_held" : normalized ? "wg_rollout_normalized"
+                   const wg_obs_norm *nm = nullptr, bool held = false, const wg_action_hold *hold = nullptr,
+                   bool deep = false, const wg_policy_mid *mid = nullptr) {
+    const char *fn = deep ? "wg_rollout_deep" : held ? "wg_rollout_held" : normalized ? "wg_rollout_normalized"
                      : stochastic ? "wg_rollout_stochastic" : episodes ? "wg_rollout_episodes" : "wg_rollout_policy";
     int rc = validate(b);
     if (rc) return rc;
@@ -441,6 +444,13 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
     if (pol->hidden < 0 || pol->hidden > 256)
         return wg_fail(WG_EINVAL, "%s: hidden %d outside 0..256", fn, pol->hidden);
     if (pol->hidden > 0 && !pol->w1) return wg_fail(WG_EINVAL, "%s: hidden %d with a null w1", fn, pol->hidden);
+    if (deep) {
+        if (!mid) return wg_fail(WG_EINVAL, "%s: null middle layer", fn);
+        if (mid->hidden2 < 1 || mid->hidden2 > 256)
+            return wg_fail(WG_EINVAL, "%s: hidden2 %d outside 1..256", fn, mid->hidden2);
+        if (!mid->wm) return wg_fail(WG_EINVAL, "%s: null wm", fn);
+        if (pol->hidden == 0) return wg_fail(WG_EINVAL, "%s: a middle layer needs hidden > 0", fn);
+    }
     if (pol->act_dim < 1 || pol->act_dim > b->A)
         return wg_fail(WG_EINVAL, "%s: act_dim %d outside 1..A = %d", fn, pol->act_dim, b->A);
     if (pol->obs_dim != obs_row_len(b, p))
@@ -555,6 +565,11 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
                    hold->hold_reward_out_step, hold->every, lg.slice};
         lg.slice += align16(lg.wpw * 4);
     }
+    KDeep kd{};
+    if (deep) {   // hidden2 more floats per walker: the second hidden vector
+        kd = KDeep{mid->wm, mid->bm, mid->hidden2, lg.slice};
+        lg.slice += align16(lg.wpw * mid->hidden2 * 4);
+    }
     int lds = lg.wpb * lg.slice;
     if (lds > 80 * 1024) return wg_fail(WG_ERANGE, "%s: workgroup needs %d B of LDS (> 80 KiB)", fn, lds);
     // a shared policy's weights staged in LDS where that costs no resident wave: as many workgroups per CU (160 KiB of
@@ -562,7 +577,8 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
     // price of occupancy the canonical batch ran 90.6 us per step with H = 32 against 73.8 through L2; the one-wave
     // workgroups of a small batch keep their occupancy and run 7.96 against 9.03: profiles/r08_policy_rollout_ab.json.)
     // WG_POLICY_STAGE (read on every call, like WG_LEAN): 0 never, 2 whenever the workgroup stays within 80 KiB
-    const int wbytes = 4 * (kpol.D * kpol.H + (kpol.H > 0 ? kpol.H : kpol.D) * kpol.C);
+    const int wbytes = deep ? 4 * (kpol.D * kpol.H + kpol.H * kd.H2 + kd.H2 * kpol.C)
+                            : 4 * (kpol.D * kpol.H + (kpol.H > 0 ? kpol.H : kpol.D) * kpol.C);
     const int ne = lean_passes(lg, b);
     const int cap = std::max(1, (ne > 4 ? 12 : 16) / lg.wpb);
     const int stage = env_int("WG_POLICY_STAGE", 1);
@@ -584,15 +600,22 @@ int rollout_policy(const wg_batch *b, const wg_params *p, const wg_policy *pol, 
         constexpr int NE = decltype(n)::value;
         auto go = [&](auto kernel, const auto &reset, const auto &stats, const auto &noise, const auto &norm) {
             hipLaunchKernelGGL(kernel, grid, block, lds, stream, *b, kp, kpol, kout(out), n_steps, lg, reset, stats, noise,
-                               norm, KNoReset{});
+                               norm, KNoReset{}, KNoReset{});
         };
-        if (held) {   // (kn with a null sigma, kon with a null mean: that option is off)
+        if (deep) {   // (held, with the middle layer)
+            if (episodes)
+                hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8, true, true, true, true, true>), grid, block, lds,
+                                   stream, *b, kp, kpol, kout(out), n_steps, lg, ar, *st, kn, kon, kh, kd);
+            else
+                hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8, false, true, true, true, true>), grid, block, lds,
+                                   stream, *b, kp, kpol, kout(out), n_steps, lg, KNoReset{}, KNoReset{}, kn, kon, kh, kd);
+        } else if (held) {   // (kn with a null sigma, kon with a null mean: that option is off)
             if (episodes)
                 hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8, true, true, true, true>), grid, block, lds, stream, *b,
-                                   kp, kpol, kout(out), n_steps, lg, ar, *st, kn, kon, kh);
+                                   kp, kpol, kout(out), n_steps, lg, ar, *st, kn, kon, kh, KNoReset{});
             else
                 hipLaunchKernelGGL((walker_rollout_policy<D3, NE, E8, false, true, true, true>), grid, block, lds, stream,
-                                   *b, kp, kpol, kout(out), n_steps, lg, KNoReset{}, KNoReset{}, kn, kon, kh);
+                                   *b, kp, kpol, kout(out), n_steps, lg, KNoReset{}, KNoReset{}, kn, kon, kh, KNoReset{});
         } else if (normalized) {
             if (stochastic) {
                 if (episodes) go(walker_rollout_policy<D3, NE, E8, true, true, true>, ar, *st, kn, kon);

@@ -198,6 +198,10 @@ class EvolutionStrategy:
                  act_limit: float = 1.0, theta0=None, obs_norm=None):
         import torch
         from .policy import MLPPolicy
+        if isinstance(hidden, (tuple, list)) or getattr(hidden, "ndim", 0):
+            # wg_es's theta has the segments w1, b1, w2, b2: a second hidden layer (MLPPolicy(wm=...)) has no place in it
+            raise ValueError(f"hidden {hidden!r}: evolution strategies take at most one hidden layer (an int); a deep "
+                             "MLPPolicy trains through walker_gym_amd.pg")
         self.env = env
         N, D = int(env.N), int(env.obs_dim)
         H, Cc = int(hidden), int(env.batch.A if act_dim is None else act_dim)

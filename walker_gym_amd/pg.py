@@ -76,8 +76,8 @@ def stochastic_forward_numpy(policy, obs_rows, sigma, seed: int, t: int, walker_
     x = np.ascontiguousarray(obs_rows, dtype=np.float32)
     n = x.shape[0]
     inf = policy.__class__(policy.w2, policy.b2, policy.w1, policy.b1, act_limit=float("inf"),
-                           obs_norm=getattr(policy, "obs_norm", None))
-    y = inf.forward_numpy(x, first_walker, n_walkers_total)            # the chain value: no clip at L = inf
+                           obs_norm=getattr(policy, "obs_norm", None), **_mid_of(policy))
+    y = inf.forward_numpy(x, first_walker, n_walkers_total)           # the chain value: no clip at L = inf
     sets = policy._sets(n, first_walker, n_walkers_total)
     sg = np.asarray(sigma.detach().cpu().numpy() if hasattr(sigma, "detach") else sigma, dtype=np.float32)
     sg = np.broadcast_to(sg, (policy.G, policy.C)) if sg.ndim < 2 else sg
@@ -154,6 +154,11 @@ def gae_held_numpy(hold_reward, value, next_value, decided, term=None, cut=None,
     return adv, ret
 
 
+def _mid_of(policy) -> dict:
+    """The middle layer of a deep policy as MLPPolicy's keyword arguments (empty for a shallow one)."""
+    return dict(wm=policy.wm, bm=policy.bm) if getattr(policy, "H2", 0) else {}
+
+
 def _sets_of(policy, N: int):
     if policy.G > 1 and N % policy.G != 0:
         raise ValueError(f"{N} walkers do not divide into {policy.G} parameter sets")
@@ -175,7 +180,7 @@ def policy_rows_numpy(policy, x, mask=None):
     x, on, _ = _rows_arrays(policy, x, mask)
     T, N, _ = x.shape
     inf = policy.__class__(policy.w2, policy.b2, policy.w1, policy.b1, act_limit=float("inf"),
-                           obs_norm=getattr(policy, "obs_norm", None))
+                           obs_norm=getattr(policy, "obs_norm", None), **_mid_of(policy))
     y = np.zeros((T, N, policy.C), np.float32)
     for t in range(T):
         y[t] = np.where(on[t][:, None], inf.forward_numpy(x[t], 0, N), np.float32(0.0))
@@ -185,7 +190,8 @@ def policy_rows_numpy(policy, x, mask=None):
 def policy_grad_numpy(policy, x, dy, mask=None, chunk_rows: int = 256):
     """wg_policy_backward on the host: float32 chains, float64 sums, in the contract's order (see the module's
     docstring).  x [T, N, D], dy [T, N, C], mask [T, N] or None.  Returns (g_w1, g_b1, g_w2, g_b2), float32 arrays
-    shaped like the policy's tensors ([G, D, H], [G, H], [G, n2, C], [G, C]), None for what the policy does not have."""
+    shaped like the policy's tensors ([G, D, H], [G, H], [G, n2, C], [G, C]), None for what the policy does not have.
+    A deep policy (H2 > 0) returns six: (g_w1, g_b1, g_wm, g_bm, g_w2, g_b2), wg_policy_backward_deep's."""
     x, on, sets = _rows_arrays(policy, x, mask)
     if getattr(policy, "obs_norm", None) is not None:
         x = policy.obs_norm.normalize_numpy(x)      # the layers and both outer products see xn
@@ -199,10 +205,29 @@ def policy_grad_numpy(policy, x, dy, mask=None, chunk_rows: int = 256):
         raise ValueError("chunk_rows < 1")
     host = lambda t: None if t is None else t.detach().cpu().numpy()
     w1, b1, w2, b2 = host(policy.w1), host(policy.b1), host(policy.w2), host(policy.b2)
+    H2 = getattr(policy, "H2", 0)
+    wm, bm = (host(policy.wm), host(policy.bm)) if H2 else (None, None)
     n, zero = N // G, np.float32(0.0)
     with np.errstate(all="ignore"):
         inp, dh = x, None
-        if H:
+        if H2:
+            z1 = np.zeros((T, N, H), np.float32) if b1 is None else np.broadcast_to(b1[sets], (T, N, H)).copy()
+            for i in range(D):
+                z1 = z1 + x[:, :, i:i + 1] * w1[sets, i][None]       # RN32 of the product, then RN32 of the sum
+            h1 = np.where(z1 > 0, z1, zero).astype(np.float32)
+            z2 = np.zeros((T, N, H2), np.float32) if bm is None else np.broadcast_to(bm[sets], (T, N, H2)).copy()
+            for j in range(H):
+                z2 = z2 + h1[:, :, j:j + 1] * wm[sets, j][None]
+            inp = np.where(z2 > 0, z2, zero).astype(np.float32)
+            d = np.zeros((T, N, H2), np.float32)
+            for c in range(Cc):
+                d = d + dy[:, :, c:c + 1] * w2[sets, :, c][None]
+            dh2 = np.where(z2 > 0, d, zero).astype(np.float32)
+            d = np.zeros((T, N, H), np.float32)
+            for k in range(H2):
+                d = d + dh2[:, :, k:k + 1] * wm[sets, :, k][None]
+            dh = np.where(z1 > 0, d, zero).astype(np.float32)
+        elif H:
             z = np.zeros((T, N, H), np.float32) if b1 is None else np.broadcast_to(b1[sets], (T, N, H)).copy()
             for i in range(D):
                 z = z + x[:, :, i:i + 1] * w1[sets, i][None]         # RN32 of the product, then RN32 of the sum
@@ -235,6 +260,10 @@ def policy_grad_numpy(policy, x, dy, mask=None, chunk_rows: int = 256):
         if H:
             g1 = ordered(x, dh, b1 is not None)
             g_w1, g_b1 = np.ascontiguousarray(g1[:, :D]), (None if b1 is None else np.ascontiguousarray(g1[:, D]))
+        if H2:
+            gm = ordered(h1, dh2, bm is not None)
+            g_wm, g_bm = np.ascontiguousarray(gm[:, :H]), (None if bm is None else np.ascontiguousarray(gm[:, H]))
+            return g_w1, g_b1, g_wm, g_bm, g_w2, g_b2
     return g_w1, g_b1, g_w2, g_b2
 
 
@@ -304,7 +333,11 @@ def policy_rows_forward(policy, obs, mask=None, y_out=None):
             raise ValueError(f"policy_rows_forward: y_out must be float32 {(T, N, Cc)} with only its step dimension strided")
     stream = torch.cuda.current_stream(dv).cuda_stream
     nm, L = _obs_norm_of(policy, "policy_rows_forward"), _lib.load()
-    if nm is None:
+    if getattr(policy, "H2", 0):
+        _lib.check(L.wg_policy_forward_deep(pol, policy.mid_struct(), None if nm is None else nm.struct(), rows,
+                                            _lib.ptr(y), y.stride(0) if T > 1 else N * Cc, stream),
+                   "wg_policy_forward_deep")
+    elif nm is None:
         _lib.check(L.wg_policy_forward(pol, rows, _lib.ptr(y), y.stride(0) if T > 1 else N * Cc, stream),
                    "wg_policy_forward")
     else:
@@ -324,19 +357,24 @@ def _rows_function():
 
     class PolicyRows(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, policy, obs, mask, chunk_rows, w1, b1, w2, b2):
+        def forward(ctx, policy, obs, mask, chunk_rows, w1, b1, w2, b2, wm=None, bm=None):
             ctx.policy, ctx.chunk_rows = policy, chunk_rows
             ctx.save_for_backward(obs, mask)
             return policy_rows_forward(policy, obs, mask)
 
         @staticmethod
         def backward(ctx, dy):
-            need = ctx.needs_input_grad[4:8]
+            need = ctx.needs_input_grad[4:10]
             if not any(need):
-                return (None,) * 8
+                return (None,) * 10
             obs, mask = ctx.saved_tensors
-            grads = policy_rows_backward(ctx.policy, obs, dy.to(torch.float32).contiguous(), mask, ctx.chunk_rows, need)
-            return (None, None, None, None, *grads)
+            dy = dy.to(torch.float32).contiguous()
+            if ctx.policy.H2:   # (the inputs are w1, b1, w2, b2, wm, bm; the deep call's order is w1, b1, wm, bm, w2, b2)
+                want = (need[0], need[1], need[4], need[5], need[2], need[3])
+                g = policy_rows_backward(ctx.policy, obs, dy, mask, ctx.chunk_rows, want)
+                return (None, None, None, None, g[0], g[1], g[4], g[5], g[2], g[3])
+            grads = policy_rows_backward(ctx.policy, obs, dy, mask, ctx.chunk_rows, need[:4])
+            return (None, None, None, None, *grads, None, None)
 
     _ROWS_FN = PolicyRows
     return PolicyRows
@@ -350,17 +388,19 @@ def policy_rows(policy, obs, mask=None, chunk_rows: Optional[int] = None):
     [R]): rows with 0 are skipped (they may hold anything, NaN included); their y is zero and they add nothing to any
     gradient: a minibatch is a row mask.
 
-    Differentiable with respect to policy.w1 / b1 / w2 / b2, whichever require grad (MLPPolicy keeps the tensors it was
-    given by identity: make them nn.Parameters or leaves with requires_grad); what the autograd engine does not need is
-    not computed.  There is NO gradient with respect to obs: its grad stays None.  The backward's sums are ordered
+    Differentiable with respect to policy.w1 / b1 / w2 / b2 (and wm / bm of a deep policy), whichever require grad
+    (MLPPolicy keeps the tensors it was given by identity: make them nn.Parameters or leaves with requires_grad); what
+    the autograd engine does not need is not computed.  There is NO gradient with respect to obs: its grad stays None.  The backward's sums are ordered
     (module docstring), chunk_rows rows per float64 partial sum, default max(256, ceil(T * n / 512)); two calls give
     identical bits.  The float64 workspace is allocated per call.  ValueError for what the library refuses."""
-    return _rows_function().apply(policy, obs, mask, chunk_rows, policy.w1, policy.b1, policy.w2, policy.b2)
+    return _rows_function().apply(policy, obs, mask, chunk_rows, policy.w1, policy.b1, policy.w2, policy.b2,
+                                  getattr(policy, "wm", None), getattr(policy, "bm", None))
 
 
 def policy_rows_backward(policy, obs, dy, mask=None, chunk_rows: Optional[int] = None, want=(True, True, True, True)):
     """wg_policy_backward called directly: (g_w1, g_b1, g_w2, g_b2) of dy [T, N, C] (or [R, C]) on the rows of obs, None
-    where `want` is False or the policy has no such tensor.  What policy_rows' autograd backward runs."""
+    where `want` is False or the policy has no such tensor.  What policy_rows' autograd backward runs.  A deep policy
+    (H2 > 0) gives six, (g_w1, g_b1, g_wm, g_bm, g_w2, g_b2), and takes a `want` of six (the default: all)."""
     import torch
     pol, rows, T, N, o3, m3, flat = _rows_struct(policy, obs, mask, "policy_rows_backward")
     dv = obs.device
@@ -371,16 +411,27 @@ def policy_rows_backward(policy, obs, dy, mask=None, chunk_rows: Optional[int] =
         raise ValueError(f"policy_rows_backward: dy must be {(T, N, policy.C)} with only its step dimension strided")
     chunk = default_chunk_rows(T, N // policy.G) if chunk_rows is None else int(chunk_rows)
     L = _lib.load()
-    count = L.wg_policy_backward_workspace(pol, rows, chunk)
-    _lib.check(count, "wg_policy_backward_workspace")
+    deep = bool(getattr(policy, "H2", 0))
+    mid = policy.mid_struct() if deep else None
+    if deep:
+        count = L.wg_policy_backward_deep_workspace(pol, mid, rows, chunk)
+        _lib.check(count, "wg_policy_backward_deep_workspace")
+        tensors = (policy.w1, policy.b1, policy.wm, policy.bm, policy.w2, policy.b2)
+        want = tuple(want) if len(tuple(want)) == 6 else (True,) * 6
+    else:
+        count = L.wg_policy_backward_workspace(pol, rows, chunk)
+        _lib.check(count, "wg_policy_backward_workspace")
+        tensors = (policy.w1, policy.b1, policy.w2, policy.b2)
     ws = torch.empty(int(count), dtype=torch.float64, device=dv)
-    grads = [torch.empty_like(t) if (k and t is not None) else None
-             for t, k in zip((policy.w1, policy.b1, policy.w2, policy.b2), want)]
+    grads = [torch.empty_like(t) if (k and t is not None) else None for t, k in zip(tensors, want)]
     p = _lib.ptr
     nm = _obs_norm_of(policy, "policy_rows_backward")
     tail = (p(d3), d3.stride(0) if T > 1 else N * policy.C, chunk, p(ws), *(p(g) for g in grads),
             torch.cuda.current_stream(dv).cuda_stream)
-    if nm is None:
+    if deep:
+        _lib.check(L.wg_policy_backward_deep(pol, mid, None if nm is None else nm.struct(), rows, *tail),
+                   "wg_policy_backward_deep")
+    elif nm is None:
         _lib.check(L.wg_policy_backward(pol, rows, *tail), "wg_policy_backward")
     else:
         _lib.check(L.wg_policy_backward_normalized(pol, nm.struct(), rows, *tail), "wg_policy_backward_normalized")

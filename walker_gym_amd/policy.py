@@ -7,6 +7,8 @@ The arithmetic is the contract, float32 with separately rounded multiply and add
   hidden:  h = (z > 0) ? z : +0.0                       (a NaN becomes 0)
   output:  a = (y < -L) ? -L : ((y > L) ? L : y)        (L = act_limit > 0, inf allowed; a NaN passes through)
 Weights are input-major (y = x @ w): w1 [G, D, H], b1 [G, H] (only with a hidden layer), w2 [G, H or D, C], b2 [G, C].
+A deep policy has a second hidden layer between the two (wg_policy_mid): wm [G, H, H2], bm [G, H2], and w2 [G, H2, C];
+its units and its ReLU are the ones above.
 With obs_norm (a walker_gym_amd.normalize.ObsNorm, wg_obs_norm in the header) the layers run on the normalised row
   input:   v = RN32(RN32(x[i] - mean[i]) * scale[i]);  xn[i] = (v < -clip) ? -clip : ((v > clip) ? clip : v)
 in all three and in the kernels; mean / scale [D] are shared by every parameter set and read at every call.
@@ -75,14 +77,15 @@ class _BoundPolicy:
 
 
 class MLPPolicy:
-    """The policy of the module's docstring over w2 [G, H or D, C], b2 [G, C], w1 [G, D, H], b1 [G, H].
+    """The policy of the module's docstring over w2 [G, H or D, C], b2 [G, C], w1 [G, D, H], b1 [G, H], and with a
+    second hidden layer wm [G, H, H2], bm [G, H2] (w2 is then [G, H2, C]; .H2 is 0 without one).
 
     A tensor that is already contiguous and of full rank ([G, ..]) is kept by identity: an nn.Parameter (or any leaf
     that requires grad) handed in stays that object in .w1 / .b1 / .w2 / .b2.  walker_gym_amd.pg.policy_rows
     differentiates with respect to exactly those, so an optimizer over the same parameters updates the policy the
     rollout kernel reads, with no copy in between."""
 
-    def __init__(self, w2, b2=None, w1=None, b1=None, act_limit: float = 1.0, obs_norm=None):
+    def __init__(self, w2, b2=None, w1=None, b1=None, act_limit: float = 1.0, obs_norm=None, wm=None, bm=None):
         w2 = _as_tensor(w2, "w2")
         if w2.dim() == 2:
             w2 = w2[None]
@@ -91,6 +94,10 @@ class MLPPolicy:
         G, n2, Cc = w2.shape
         if w1 is None and b1 is not None:
             raise ValueError("b1 without w1")
+        if wm is None and bm is not None:
+            raise ValueError("bm without wm")
+        if wm is not None and w1 is None:
+            raise ValueError("wm without w1 (a middle layer needs a first hidden layer)")
 
         def bias(b, name, width):
             if b is None:
@@ -110,12 +117,27 @@ class MLPPolicy:
                 raise ValueError(f"w1 must be [G, D, H] (or 2-D for G = 1), got {tuple(w1.shape)}")
             if w1.shape[0] != G:
                 raise ValueError(f"w1 has {w1.shape[0]} parameter sets, w2 has {G}")
-            if w1.shape[2] != n2:
+            if wm is None and w1.shape[2] != n2:
                 raise ValueError(f"w1 has {w1.shape[2]} hidden units, w2 takes {n2} inputs")
-        b1 = bias(b1, "b1", n2)
+        if wm is not None:
+            wm = _as_tensor(wm, "wm")
+            if wm.dim() == 2:
+                wm = wm[None]
+            if wm.dim() != 3 or min(wm.shape) < 1:
+                raise ValueError(f"wm must be [G, H, H2] (or 2-D for G = 1), got {tuple(wm.shape)}")
+            if wm.shape[0] != G:
+                raise ValueError(f"wm has {wm.shape[0]} parameter sets, w2 has {G}")
+            if wm.shape[1] != w1.shape[2]:
+                raise ValueError(f"w1 has {w1.shape[2]} hidden units, wm takes {wm.shape[1]} inputs")
+            if wm.shape[2] != n2:
+                raise ValueError(f"wm has {wm.shape[2]} hidden units, w2 takes {n2} inputs")
+            if wm.shape[2] > 256:
+                raise ValueError(f"wm has {wm.shape[2]} hidden units, at most 256")
+        b1 = bias(b1, "b1", n2 if wm is None else int(wm.shape[1]))
+        bm = bias(bm, "bm", n2)
         b2 = bias(b2, "b2", Cc)
         dev = w2.device
-        for name, t in (("b2", b2), ("w1", w1), ("b1", b1)):
+        for name, t in (("b2", b2), ("w1", w1), ("b1", b1), ("wm", wm), ("bm", bm)):
             if t is not None and t.device != dev:
                 raise ValueError(f"{name} is on {t.device}, w2 is on {dev}")
         L = float(act_limit)
@@ -123,10 +145,13 @@ class MLPPolicy:
             raise ValueError(f"act_limit must be > 0 (inf allowed), got {act_limit!r}")
         self.w1 = None if w1 is None else w1.contiguous()
         self.b1 = None if b1 is None else b1.contiguous()
+        self.wm = None if wm is None else wm.contiguous()
+        self.bm = None if bm is None else bm.contiguous()
         self.w2, self.b2 = w2.contiguous(), None if b2 is None else b2.contiguous()
         self.act_limit = float(np.float32(L))
         self.G, self.C = int(G), int(Cc)
-        self.H = 0 if w1 is None else int(n2)
+        self.H = 0 if w1 is None else int(w1.shape[2])
+        self.H2 = 0 if wm is None else int(n2)    # the second hidden layer's width; 0: none
         self.D = int(n2) if w1 is None else int(w1.shape[1])
         # walker_gym_amd.normalize.ObsNorm, kept by identity: its mean / scale are updated in place.  Every evaluator
         # runs the layers on xn = clip((x - mean) * scale); None: the plain policy
@@ -146,10 +171,14 @@ class MLPPolicy:
                              w2=p(self.w2), b2=p(self.b2), act_limit=self.act_limit, action_out=p(action_out),
                              action_out_step=n_walkers * self.C, return_out=None, length_out=None)
 
+    def mid_struct(self) -> "_lib.WgPolicyMid":
+        """wg_policy_mid of a deep policy (H2 > 0): what the *_deep entries take beside struct()."""
+        return _lib.WgPolicyMid(hidden2=self.H2, wm=_lib.ptr(self.wm), bm=_lib.ptr(self.bm))
+
     def to(self, device) -> "MLPPolicy":
         mv = lambda t: None if t is None else t.to(device)
         return MLPPolicy(mv(self.w2), mv(self.b2), mv(self.w1), mv(self.b1), self.act_limit,
-                         None if self.obs_norm is None else self.obs_norm.to(device))
+                         None if self.obs_norm is None else self.obs_norm.to(device), mv(self.wm), mv(self.bm))
 
     def _sets(self, n: int, first_walker: int, n_total: Optional[int]):
         """The parameter set of each of n rows starting at walker first_walker of n_total (numpy int64), or None for
@@ -190,6 +219,9 @@ class MLPPolicy:
             if self.H:
                 z = layer(x, host(self.w1), host(self.b1))
                 x = np.where(z > 0, z, np.float32(0.0)).astype(np.float32)
+            if self.H2:
+                z = layer(x, host(self.wm), host(self.bm))
+                x = np.where(z > 0, z, np.float32(0.0)).astype(np.float32)
             y = layer(x, host(self.w2), host(self.b2))
             L = np.float32(self.act_limit)
             return np.where(y < -L, -L, np.where(y > L, L, y)).astype(np.float32)
@@ -217,6 +249,9 @@ class MLPPolicy:
         x = rows if self.obs_norm is None else self.obs_norm.normalize_torch(rows)
         if self.H:
             z = layer(x, self.w1, self.b1)
+            x = torch.where(z > 0, z, torch.zeros_like(z))
+        if self.H2:
+            z = layer(x, self.wm, self.bm)
             x = torch.where(z > 0, z, torch.zeros_like(z))
         y = layer(x, self.w2, self.b2)
         L = torch.full_like(y, self.act_limit)
