@@ -7,7 +7,8 @@ process:
   (c) the same generation as the torch composition a user writes today: a torch.randn [G/2, K] noise matrix kept for
       the update, broadcast adds into the four [G, ...] weight tensors, the rollout, a double argsort, d @ eps
 
-Rows: Balance-v0 x 4,096 and canonical x 65,536, H = 0 and 32, `--steps` steps per rollout.  Every timed call restores
+Rows: Balance-v0 x 4,096 and canonical x 65,536, H = 0 and 32, and the deep 32 x 32 policy (hidden2 = 32: the six-segment
+theta and the wg_es_*_deep entries; --deep-only runs these two rows alone), `--steps` steps per rollout.  Every timed call restores
 the same start state inside the clock (the same copy in all three paths), runs between two device synchronisations, and
 follows three warm-up calls of every path; the paths are timed in turn `--reps` times (interleaved, so clock and thermal
 drift fall on all alike).  Per row and path: median, min, max ms per call and max / min.
@@ -17,6 +18,7 @@ computed from the shapes, integer issue and store bandwidth, and which of them b
 and of (c) above what is allocated before the call (the policy sets, theta, the env).
 
     python scripts/es_generation_ab.py [--steps 200] [--reps 5] [--out profiles/r10_es_generation_ab.json]
+    python scripts/es_generation_ab.py --deep-only --out profiles/r17_es_deep_generation_ab.json
 """
 import argparse
 import ctypes as C
@@ -40,7 +42,8 @@ from walker_gym_amd.walker import balance_spec             # noqa: E402
 # of es_perturb on its K >= 256 path whose element lies in the first segment, as nearly all do (111: the ten Philox
 # rounds, the segment test and the 64-bit addresses; one value per thread), and the inner loop of es_update_partial (80:
 # the rounds that depend only on k are hoisted out of it).  Each is taken at full rate, 4 cycles per wave64 instruction
-# on a SIMD, the 32-bit multiplies included: at a quarter of it both kernels would run far above their bounds.
+# on a SIMD, the 32-bit multiplies included: at a quarter of it both kernels would run far above their bounds.  The deep
+# rows use es_perturb's count for es_perturb_deep (not recounted: the first segment's path has the same steps).
 VALU = {"perturb": 111, "update": 80}
 SIMDS, CLOCK_HZ, HBM_BPS = 1024, 2.4e9, 6.3e12
 
@@ -64,15 +67,15 @@ def kernel_ms(fn, n=20):
     return e0.elapsed_time(e1) / n
 
 
-def row(name, spec, params, H, steps, reps):
+def row(name, spec, params, H, steps, reps, H2=0):
     env = BatchedPhysicsEnv(spec, **params)
     N, D, A, dev = env.N, env.obs_dim, env.batch.A, env.device
     s = 0.002 if H else 0.0005
-    tr = EvolutionStrategy(env, hidden=H, population=N, sigma=s, lr=1e-5, seed=1)
+    tr = EvolutionStrategy(env, hidden=H, population=N, sigma=s, lr=1e-5, seed=1, hidden2=H2)
     G, K, n_pairs, pol = tr.G, tr.K, tr.n_pairs, tr.policy
     start = tr._state0
     theta_c = torch.zeros(K, device=dev)
-    segs = [(t, t[0].numel()) for t in (pol.w1, pol.b1, pol.w2, pol.b2) if t is not None]
+    segs = [(t, t[0].numel()) for t in (pol.w1, pol.b1, pol.wm, pol.bm, pol.w2, pol.b2) if t is not None]
     c_G = 1.0 / (2 * (G - 1))
 
     def a_rollout():
@@ -86,7 +89,7 @@ def row(name, spec, params, H, steps, reps):
         env.batch.load_state_dict(start)
         eps = torch.randn((n_pairs, K), device=dev)
         o = 0
-        for t, n in segs:   # broadcast adds into the four [G, ...] tensors
+        for t, n in segs:   # broadcast adds into the four (deep: six) [G, ...] tensors
             v = t.view(n_pairs, 2, n)
             d = s * eps[:, o:o + n]
             v[:, 0] = theta_c[o:o + n] + d
@@ -141,15 +144,27 @@ def row(name, spec, params, H, steps, reps):
     es = tr._struct()
     L, stream = _lib.load(), env._stream()
     p = lambda t: C.c_void_p(t.data_ptr())
-    t_perturb = kernel_ms(lambda: L.wg_es_perturb(C.byref(es), 0, n_pairs, stream))
-    t_update = kernel_ms(lambda: L.wg_es_update(C.byref(es), 0, n_pairs, p(util), 1.0, 0.0, p(tr._work), p(tr._grad), None,
-                                                stream))
+    if H2:
+        mid = _lib.WgEsMid(hidden2=H2, wm=p(pol.wm), bm=p(pol.bm))
+        t_perturb = kernel_ms(lambda: L.wg_es_perturb_deep(C.byref(es), C.byref(mid), 0, n_pairs, stream))
+        t_update = kernel_ms(lambda: L.wg_es_update_deep(C.byref(es), C.byref(mid), 0, n_pairs, p(util), 1.0, 0.0,
+                                                         p(tr._work), p(tr._grad), None, stream))
+    else:
+        t_perturb = kernel_ms(lambda: L.wg_es_perturb(C.byref(es), 0, n_pairs, stream))
+        t_update = kernel_ms(lambda: L.wg_es_update(C.byref(es), 0, n_pairs, p(util), 1.0, 0.0, p(tr._work), p(tr._grad),
+                                                    None, stream))
+    if H2:   # the per-parameter-sigma perturb of the same shape
+        sg = torch.full((K,), s, device=dev)
+        t_diag = kernel_ms(lambda: L.wg_es_perturb_diag_deep(C.byref(es), C.byref(mid), p(sg), 0, n_pairs, stream))
     kern = {}
     for kname, t in (("perturb", t_perturb), ("update", t_update)):
         b = bounds(kname, n_pairs, K)
-        kern["wg_es_" + kname] = dict(b, ms=t, bound_over_measured=b["bound_ms"] / t)
+        kern["wg_es_" + kname + ("_deep" if H2 else "")] = dict(b, ms=t, bound_over_measured=b["bound_ms"] / t)
+    if H2:
+        b = bounds("perturb", n_pairs, K)
+        kern["wg_es_perturb_diag_deep"] = dict(b, ms=t_diag, bound_over_measured=b["bound_ms"] / t_diag)
     med = lambda k: stat[k]["median"]
-    return {"row": name, "N": N, "G": G, "D": D, "H": H, "C": A, "K": K, "steps": steps, "ms_per_call": stat,
+    return {"row": name, "N": N, "G": G, "D": D, "H": H, "H2": H2, "C": A, "K": K, "steps": steps, "ms_per_call": stat,
             "kernels": kern, "peak_bytes_above_policy_sets": mem,
             "b_allocation_model_bytes": K * (-(-G // 512)) * 8 + G,
             "noise_matrix_bytes": n_pairs * K * 4, "policy_set_bytes": G * K * 4,
@@ -165,12 +180,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--deep-only", action="store_true")
     a = ap.parse_args()
     bal, can = balance_spec(4096), canonical_walkers(65536, seed=0)
     rows = []
-    for H in (0, 32):
+    for H in (() if a.deep_only else (0, 32)):
         rows.append(row(f"balance4096-H{H}", bal, dict(in3d=0), H, a.steps, a.reps))
         rows.append(row(f"canonical65536-H{H}", can, dict(in3d=1), H, a.steps, a.reps))
+    rows.append(row("balance4096-H32x32", bal, dict(in3d=0), 32, a.steps, a.reps, H2=32))
+    rows.append(row("canonical65536-H32x32", can, dict(in3d=1), 32, a.steps, a.reps, H2=32))
     res = {"rows": rows, "device": torch.cuda.get_device_name(0), "reps": a.reps,
            "method": "one process, three warm-up calls of every path, then the paths timed in turn reps times; ms per call = "
                      "wall time of a whole call between two synchronisations, the restore of the start state included "

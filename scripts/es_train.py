@@ -23,6 +23,10 @@ changes nothing).  The rows are then of order one, so --sigma and --lr default t
 --act-every K: the candidates and the mean policy decide every K steps and hold their action between
 (generation_step(act_every=K): the deterministic rollout_held).
     python scripts/es_train.py --act-every 4 --out profiles/r15_es_act_every4_balance_curve.json
+
+--hidden2 H2: a deep policy, --hidden -> H2 units (the trainers' hidden2=: theta's six segments, the wg_es_*_deep
+entries); --hidden defaults to H2 then.
+    python scripts/es_train.py --hidden2 32 --out profiles/r17_es_deep_balance_curve.json
 """
 import argparse
 import json
@@ -45,6 +49,7 @@ def main():
     ap.add_argument("--walkers", type=int, default=1024)
     ap.add_argument("--population", type=int, default=1024)
     ap.add_argument("--hidden", type=int, default=0)
+    ap.add_argument("--hidden2", type=int, default=0)
     ap.add_argument("--generations", type=int, default=30)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--sigma", type=float, default=None)
@@ -57,6 +62,8 @@ def main():
     a = ap.parse_args()
     a.sigma = (0.05 if a.obs_norm else 0.001) if a.sigma is None else a.sigma
     a.lr = (0.05 if a.obs_norm else 1e-4) if a.lr is None else a.lr
+    if a.hidden2 and not a.hidden:
+        a.hidden = a.hidden2
     env = BatchedPhysicsEnv(balance_spec(a.walkers), in3d=0)
     nm = rows = mask = None
     if a.obs_norm:
@@ -66,10 +73,10 @@ def main():
         mask[:, ::64] = 1
     if a.adaptive:
         tr = AdaptiveEvolutionStrategy(env, hidden=a.hidden, population=a.population, sigma=a.sigma,
-                                       lr=a.lr / a.sigma ** 2, seed=a.seed, obs_norm=nm)
+                                       lr=a.lr / a.sigma ** 2, seed=a.seed, obs_norm=nm, hidden2=a.hidden2)
     else:
         tr = EvolutionStrategy(env, hidden=a.hidden, population=a.population, sigma=a.sigma, lr=a.lr, seed=a.seed,
-                               obs_norm=nm)
+                               obs_norm=nm, hidden2=a.hidden2)
     start = env.batch.state_dict()
     curve = []
     t0 = time.perf_counter()
@@ -96,7 +103,7 @@ def main():
                              obs_norm_scale_max=float(nm.scale.max()))
         print(json.dumps(curve[-1]), flush=True)
     torch.cuda.synchronize()
-    res = {"env": "Balance-v0", "walkers": env.N, "population": tr.G, "hidden": tr.H, "K": tr.K, "steps": a.steps,
+    res = {"env": "Balance-v0", "walkers": env.N, "population": tr.G, "hidden": tr.H, "hidden2": tr.H2, "K": tr.K, "steps": a.steps,
            "trainer": type(tr).__name__, "obs_norm": bool(a.obs_norm), "act_every": a.act_every, "sigma": a.sigma if a.adaptive else tr.sigma, "lr": tr.lr, "seed": tr.seed, "seconds": time.perf_counter() - t0,
            "device": torch.cuda.get_device_name(0), "curve": curve}
     if a.out:

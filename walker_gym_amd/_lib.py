@@ -93,6 +93,12 @@ class WgEsDiagStep(C.Structure):
                 ("sigma_max", C.c_float)]
 
 
+class WgEsMid(C.Structure):
+    """wg_es_mid: the middle layer of a deep candidate set (the wg_es_*_deep entries; theta's segments: w1, b1, wm, bm,
+    w2, b2)."""
+    _fields_ = [("hidden2", C.c_int32), ("wm", _vp), ("bm", _vp)]
+
+
 class WgActionNoise(C.Structure):
     """wg_action_noise: the seeded exploration noise of wg_rollout_stochastic and its optional per-step outputs."""
     _fields_ = [("seed", C.c_uint64), ("step_base", C.c_uint32), ("walker_base", C.c_uint32), ("sigma", _vp),
@@ -130,7 +136,8 @@ EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_r
            "wg_rollout_stochastic", "wg_gae", "wg_policy_forward", "wg_policy_backward_workspace", "wg_policy_backward",
            "wg_es_perturb_diag", "wg_es_update_diag", "wg_rollout_normalized", "wg_policy_forward_normalized",
            "wg_policy_backward_normalized", "wg_obs_moments_workspace", "wg_obs_moments", "wg_rollout_held", "wg_gae_held",
-           "wg_rollout_deep", "wg_policy_forward_deep", "wg_policy_backward_deep_workspace", "wg_policy_backward_deep")
+           "wg_rollout_deep", "wg_policy_forward_deep", "wg_policy_backward_deep_workspace", "wg_policy_backward_deep",
+           "wg_es_perturb_deep", "wg_es_update_deep", "wg_es_perturb_diag_deep", "wg_es_update_diag_deep")
 
 _lib = None
 _lock = threading.Lock()
@@ -200,6 +207,11 @@ def load(path: str | None = None):
         L.wg_es_perturb_diag.argtypes = [C.POINTER(WgEs), _vp, C.c_int32, C.c_int32, _vp]
         L.wg_es_update_diag.argtypes = [C.POINTER(WgEs), _vp, C.c_int32, C.c_int32, _vp, C.POINTER(WgEsDiagStep), _vp,
                                         _vp, _vp, _vp, _vp, _vp]
+        mid = C.POINTER(WgEsMid)   # the _deep twins: wg_es_mid after es, then the shallow entry's arguments
+        L.wg_es_perturb_deep.argtypes = [C.POINTER(WgEs), mid] + L.wg_es_perturb.argtypes[1:]
+        L.wg_es_update_deep.argtypes = [C.POINTER(WgEs), mid] + L.wg_es_update.argtypes[1:]
+        L.wg_es_perturb_diag_deep.argtypes = [C.POINTER(WgEs), mid] + L.wg_es_perturb_diag.argtypes[1:]
+        L.wg_es_update_diag_deep.argtypes = [C.POINTER(WgEs), mid] + L.wg_es_update_diag.argtypes[1:]
         L.wg_step_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,
                                      C.POINTER(_vp)]
         L.wg_run_ranges.argtypes = [C.POINTER(WgRange), C.c_int32, C.POINTER(WgParams), _vp, C.c_int32, C.c_int32,

@@ -18,6 +18,9 @@
 //                      tile's in pair order, lanes 0..31 the chain of the mean and lanes 32..63 the chain of sigma
 //   es_diag_partial_thread  one thread per (chunk, k) walking both chains; the same bits (chosen for large launches)
 //   es_diag_tail       one thread per k: both chunk-ordered sums, the scales, the division, the two steps, the clamp
+// and for a policy with a second hidden layer (wg_es_mid: theta's six segments w1, b1, wm, bm, w2, b2):
+//   es_perturb_deep, es_perturb_diag_deep  es_perturb's rows and lanes; es_deep_slot resolves the six segments for both
+// The deep update entries launch the update kernels above: those depend on the layout through K alone.
 // The summation order is the contract (no atomics).  Every element offset is 64-bit.
 
 #include <hip/hip_runtime.h>
@@ -283,10 +286,90 @@ __global__ __launch_bounds__(ES_THREADS) void es_diag_tail(const double *__restr
     }
 }
 
-// The checks that every call here shares (scalar_sigma: also es->sigma, which the _diag calls do not read); fills the
-// layout and K.
-int es_check(const wg_es *es, int32_t first_pair, int32_t n_pairs, const char *who, EsLayout *lay, int64_t *K,
-             bool scalar_sigma = true) {
+// ------------------------------------------------------------------------------------------- a second hidden layer
+// The six segments of a deep theta in order (element counts, 0 for an absent one) and the candidate tensors.
+struct EsDeepLayout {
+    int32_t n_w1, n_b1, n_wm, n_bm, n_w2, n_b2;
+    float *w1, *b1, *wm, *bm, *w2, *b2;
+};
+
+// A thread of the deep perturb kernels: its parameter k, its pair j and the address of element k in set 2j (set 2j + 1
+// is *stride elements on).  es_perturb's mapping (rows of ppb pairs, blocks of 256 values of k); false for a thread
+// beyond the launch's pairs or parameters.  A segment of no elements never takes an element: off >= 0 is not < 0, so
+// the chain moves on with off unchanged.  The last branch is b2's: k < K leaves nothing else.
+__device__ __forceinline__ bool es_deep_slot(const EsDeepLayout &lay, int32_t K, int32_t ppb, int32_t first_pair,
+                                             int32_t n_pairs, int32_t *k_out, int32_t *j_out, float **p_out,
+                                             int64_t *stride_out) {
+    int32_t pl = 0, k;
+    if (ppb > 1) {
+        pl = (int32_t)threadIdx.x / K;
+        k = (int32_t)threadIdx.x - pl * K;
+        if (pl >= ppb) return false;
+    } else {
+        k = (int32_t)(blockIdx.y * ES_THREADS + threadIdx.x);
+        if (k >= K) return false;
+    }
+    const int32_t jl = (int32_t)blockIdx.x * ppb + pl;   // < n_pairs + ppb <= 2^30 + 256
+    if (jl >= n_pairs) return false;
+    float *dst;
+    int64_t stride;
+    int32_t off = k;
+    if (off < lay.n_w1) {
+        dst = lay.w1; stride = lay.n_w1;
+    } else if ((off -= lay.n_w1) < lay.n_b1) {
+        dst = lay.b1; stride = lay.n_b1;
+    } else if ((off -= lay.n_b1) < lay.n_wm) {
+        dst = lay.wm; stride = lay.n_wm;
+    } else if ((off -= lay.n_wm) < lay.n_bm) {
+        dst = lay.bm; stride = lay.n_bm;
+    } else if ((off -= lay.n_bm) < lay.n_w2) {
+        dst = lay.w2; stride = lay.n_w2;
+    } else {
+        off -= lay.n_w2;
+        dst = lay.b2; stride = lay.n_b2;
+    }
+    const int32_t j = first_pair + jl;
+    *k_out = k;
+    *j_out = j;
+    *p_out = dst + off + 2 * (int64_t)j * stride;   // 64-bit: wm's set stride is up to 65,536 elements
+    *stride_out = stride;
+    return true;
+}
+
+// es_perturb over the six-segment theta: set 2j gets RN32(theta[k] + d), set 2j + 1 RN32(theta[k] - d), d = RN32(sigma *
+// eps(seed, generation, j, k)) with k the index in the deep theta.
+__global__ __launch_bounds__(ES_THREADS) void es_perturb_deep(EsDeepLayout lay, const float *__restrict__ theta, int32_t K,
+                                                              int32_t ppb, uint32_t k0, uint32_t k1, uint32_t generation,
+                                                              float sigma, int32_t first_pair, int32_t n_pairs) {
+    int32_t k, j;
+    float *p;
+    int64_t stride;
+    if (!es_deep_slot(lay, K, ppb, first_pair, n_pairs, &k, &j, &p, &stride)) return;
+    const float th = theta[k];
+    const float d = __fmul_rn(sigma, wg_eps<WG_ES_TAG>(k0, k1, generation, (uint32_t)j, (uint32_t)k));
+    p[0] = __fadd_rn(th, d);
+    p[stride] = __fsub_rn(th, d);
+}
+
+// The same with d = RN32(sigma[k] * eps), sigma [K] in the deep theta's order.
+__global__ __launch_bounds__(ES_THREADS) void es_perturb_diag_deep(EsDeepLayout lay, const float *__restrict__ theta,
+                                                                   const float *__restrict__ sigma, int32_t K,
+                                                                   int32_t ppb, uint32_t k0, uint32_t k1,
+                                                                   uint32_t generation, int32_t first_pair,
+                                                                   int32_t n_pairs) {
+    int32_t k, j;
+    float *p;
+    int64_t stride;
+    if (!es_deep_slot(lay, K, ppb, first_pair, n_pairs, &k, &j, &p, &stride)) return;
+    const float th = theta[k];
+    const float d = __fmul_rn(sigma[k], wg_eps<WG_ES_TAG>(k0, k1, generation, (uint32_t)j, (uint32_t)k));
+    p[0] = __fadd_rn(th, d);
+    p[stride] = __fsub_rn(th, d);
+}
+
+// The checks that every call here shares, in the order the header lists them (scalar_sigma: also es->sigma, which
+// the _diag calls do not read); everything but the parameter count, which depends on the layout.
+int es_check_head(const wg_es *es, int32_t first_pair, int32_t n_pairs, const char *who, bool scalar_sigma) {
     if (!es) return wg_fail(WG_EINVAL, "%s: null es", who);
     if (!es->theta) return wg_fail(WG_EINVAL, "%s: null theta", who);
     if (es->obs_dim < 1) return wg_fail(WG_EINVAL, "%s: obs_dim %d < 1", who, es->obs_dim);
@@ -302,6 +385,13 @@ int es_check(const wg_es *es, int32_t first_pair, int32_t n_pairs, const char *w
         return wg_fail(WG_EINVAL, "%s: pairs %d .. %lld outside 0 .. %d", who, first_pair,
                     (long long)first_pair + n_pairs, es->n_sets / 2);
     if (scalar_sigma && (!std::isfinite(es->sigma) || !(es->sigma > 0.0f))) return wg_fail(WG_EINVAL, "%s: sigma must be finite and > 0", who);
+    return 0;
+}
+
+// The four-segment entries: the shared checks, then the layout and K.
+int es_check(const wg_es *es, int32_t first_pair, int32_t n_pairs, const char *who, EsLayout *lay, int64_t *K,
+             bool scalar_sigma = true) {
+    if (const int rc = es_check_head(es, first_pair, n_pairs, who, scalar_sigma)) return rc;
     const int64_t H = es->hidden, D = es->obs_dim, C = es->act_dim;
     const int64_t n_w1 = D * H, n_b1 = es->b1 ? H : 0, n_w2 = (H > 0 ? H : D) * C, n_b2 = es->b2 ? C : 0;
     *K = n_w1 + n_b1 + n_w2 + n_b2;
@@ -311,35 +401,35 @@ int es_check(const wg_es *es, int32_t first_pair, int32_t n_pairs, const char *w
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int wg_es_perturb(const wg_es *es, int32_t first_pair, int32_t n_pairs, hipStream_t stream) {
-    EsLayout lay;
-    int64_t K64;
-    if (const int rc = es_check(es, first_pair, n_pairs, "wg_es_perturb", &lay, &K64)) return rc;
-    const int32_t K = (int32_t)K64;
-    const int32_t ppb = K >= ES_THREADS ? 1 : ES_THREADS / K;
-    const int32_t rows = (n_pairs + ppb - 1) / ppb;
-    const dim3 grid(rows, ppb > 1 ? 1 : (K + ES_THREADS - 1) / ES_THREADS);
-    es_perturb<<<grid, ES_THREADS, 0, stream>>>(lay, es->theta, K, ppb, (uint32_t)(es->seed & 0xffffffffu),
-                                               (uint32_t)(es->seed >> 32), es->generation, es->sigma, first_pair,
-                                               n_pairs);
-    return wg_launched("wg_es_perturb: launch");
+// The _deep entries: the shared checks in front, then the middle layer's, then K over the six segments.
+int es_check_deep(const wg_es *es, const wg_es_mid *mid, int32_t first_pair, int32_t n_pairs, const char *who,
+                  EsDeepLayout *lay, int64_t *K, bool scalar_sigma = true) {
+    if (const int rc = es_check_head(es, first_pair, n_pairs, who, scalar_sigma)) return rc;
+    if (!mid) return wg_fail(WG_EINVAL, "%s: null mid", who);
+    if (mid->hidden2 < 1 || mid->hidden2 > 256)
+        return wg_fail(WG_EINVAL, "%s: hidden2 %d outside 1..256", who, mid->hidden2);
+    if (es->hidden == 0) return wg_fail(WG_EINVAL, "%s: a middle layer without a first hidden layer (hidden 0)", who);
+    if (!mid->wm) return wg_fail(WG_EINVAL, "%s: null wm", who);
+    const int64_t H = es->hidden, H2 = mid->hidden2, D = es->obs_dim, C = es->act_dim;
+    const int64_t n_w1 = D * H, n_b1 = es->b1 ? H : 0, n_wm = H * H2, n_bm = mid->bm ? H2 : 0, n_w2 = H2 * C,
+                  n_b2 = es->b2 ? C : 0;
+    *K = n_w1 + n_b1 + n_wm + n_bm + n_w2 + n_b2;
+    if (*K > ES_MAX_K) return wg_fail(WG_EINVAL, "%s: %lld parameters (at most 2^23)", who, (long long)*K);
+    lay->n_w1 = (int32_t)n_w1; lay->n_b1 = (int32_t)n_b1; lay->n_wm = (int32_t)n_wm; lay->n_bm = (int32_t)n_bm;
+    lay->n_w2 = (int32_t)n_w2; lay->n_b2 = (int32_t)n_b2;
+    lay->w1 = es->w1; lay->b1 = es->b1; lay->wm = mid->wm; lay->bm = mid->bm; lay->w2 = es->w2; lay->b2 = es->b2;
+    return 0;
 }
 
-int wg_es_update(const wg_es *es, int32_t first_pair, int32_t n_pairs, const float *util, double scale, float lr,
-                 double *workspace, float *grad, float *theta_out, hipStream_t stream) {
-    EsLayout lay;
-    int64_t K64;
-    if (const int rc = es_check(es, first_pair, n_pairs, "wg_es_update", &lay, &K64)) return rc;
-    if (!util) return wg_fail(WG_EINVAL, "wg_es_update: null util");
-    if (!workspace) return wg_fail(WG_EINVAL, "wg_es_update: null workspace");
-    if (!std::isfinite(scale)) return wg_fail(WG_EINVAL, "wg_es_update: scale is not finite");
-    if (!std::isfinite(lr)) return wg_fail(WG_EINVAL, "wg_es_update: lr is not finite");
-    if (!grad && !theta_out) return wg_fail(WG_EINVAL, "wg_es_update: grad and theta_out are both null");
-    const int32_t K = (int32_t)K64;
+// What follows the layout's checks in wg_es_update and wg_es_update_deep: the call's own refusals and the two launches
+// (the kernels know the layout through K alone).
+int es_update_run(const char *who, const wg_es *es, int32_t K, int32_t first_pair, int32_t n_pairs, const float *util,
+                  double scale, float lr, double *workspace, float *grad, float *theta_out, hipStream_t stream) {
+    if (!util) return wg_fail(WG_EINVAL, "%s: null util", who);
+    if (!workspace) return wg_fail(WG_EINVAL, "%s: null workspace", who);
+    if (!std::isfinite(scale)) return wg_fail(WG_EINVAL, "%s: scale is not finite", who);
+    if (!std::isfinite(lr)) return wg_fail(WG_EINVAL, "%s: lr is not finite", who);
+    if (!grad && !theta_out) return wg_fail(WG_EINVAL, "%s: grad and theta_out are both null", who);
     const int32_t n_chunks = (n_pairs + ES_CHUNK - 1) / ES_CHUNK, kb = (K + ES_THREADS - 1) / ES_THREADS;
     es_update_partial<<<dim3(n_chunks, kb), ES_THREADS, 0, stream>>>(
         util, workspace, K, (uint32_t)(es->seed & 0xffffffffu), (uint32_t)(es->seed >> 32), es->generation, first_pair,
@@ -349,27 +439,10 @@ int wg_es_update(const wg_es *es, int32_t first_pair, int32_t n_pairs, const flo
     return wg_launched("wg_es_update (tail): launch");
 }
 
-int wg_es_perturb_diag(const wg_es *es, const float *sigma, int32_t first_pair, int32_t n_pairs, hipStream_t stream) {
-    EsLayout lay;
-    int64_t K64;
-    if (const int rc = es_check(es, first_pair, n_pairs, "wg_es_perturb_diag", &lay, &K64, false)) return rc;
-    if (!sigma) return wg_fail(WG_EINVAL, "wg_es_perturb_diag: null sigma vector");
-    const int32_t K = (int32_t)K64;
-    const int32_t ppb = K >= ES_THREADS ? 1 : ES_THREADS / K;
-    const int32_t rows = (n_pairs + ppb - 1) / ppb;
-    const dim3 grid(rows, ppb > 1 ? 1 : (K + ES_THREADS - 1) / ES_THREADS);
-    es_perturb_diag<<<grid, ES_THREADS, 0, stream>>>(lay, es->theta, sigma, K, ppb, (uint32_t)(es->seed & 0xffffffffu),
-                                                    (uint32_t)(es->seed >> 32), es->generation, first_pair, n_pairs);
-    return wg_launched("wg_es_perturb_diag: launch");
-}
-
-int wg_es_update_diag(const wg_es *es, const float *sigma, int32_t first_pair, int32_t n_pairs, const float *util,
-                      const wg_es_diag_step *step, double *workspace, float *g_theta, float *theta_out, float *g_sigma,
-                      float *sigma_out, hipStream_t stream) {
-    static const char *const who = "wg_es_update_diag";
-    EsLayout lay;
-    int64_t K64;
-    if (const int rc = es_check(es, first_pair, n_pairs, who, &lay, &K64, false)) return rc;
+// The same for wg_es_update_diag and wg_es_update_diag_deep.
+int es_update_diag_run(const char *who, const wg_es *es, int32_t K, const float *sigma, int32_t first_pair,
+                       int32_t n_pairs, const float *util, const wg_es_diag_step *step, double *workspace,
+                       float *g_theta, float *theta_out, float *g_sigma, float *sigma_out, hipStream_t stream) {
     if (!sigma) return wg_fail(WG_EINVAL, "%s: null sigma vector", who);
     if (!util) return wg_fail(WG_EINVAL, "%s: null util", who);
     if (!step) return wg_fail(WG_EINVAL, "%s: null step", who);
@@ -385,7 +458,6 @@ int wg_es_update_diag(const wg_es *es, const float *sigma, int32_t first_pair, i
         return wg_fail(WG_EINVAL, "%s: sigma_min must be finite and > 0", who);
     if (!(step->sigma_max >= step->sigma_min)) return wg_fail(WG_EINVAL, "%s: sigma_max below sigma_min (or NaN)", who);
     if (!g_theta && !theta_out && !g_sigma && !sigma_out) return wg_fail(WG_EINVAL, "%s: all four outputs are null", who);
-    const int32_t K = (int32_t)K64;
     const int32_t n_chunks = (n_pairs + ES_CHUNK - 1) / ES_CHUNK;
     const uint32_t k0 = (uint32_t)(es->seed & 0xffffffffu), k1 = (uint32_t)(es->seed >> 32);
     const int32_t tblocks = (K + ES_THREADS - 1) / ES_THREADS;
@@ -403,6 +475,110 @@ int wg_es_update_diag(const wg_es *es, const float *sigma, int32_t first_pair, i
                                                                               theta_out, g_sigma, sigma_out, K,
                                                                               n_chunks, *step);
     return wg_launched("wg_es_update_diag (tail): launch");
+}
+
+// The grid of the perturb kernels: rows of ppb pairs by blocks of 256 parameters.
+dim3 es_perturb_grid(int32_t K, int32_t n_pairs, int32_t *ppb) {
+    *ppb = K >= ES_THREADS ? 1 : ES_THREADS / K;
+    return dim3((n_pairs + *ppb - 1) / *ppb, *ppb > 1 ? 1 : (K + ES_THREADS - 1) / ES_THREADS);
+}
+
+}  // namespace
+
+extern "C" {
+
+int wg_es_perturb(const wg_es *es, int32_t first_pair, int32_t n_pairs, hipStream_t stream) {
+    EsLayout lay;
+    int64_t K64;
+    if (const int rc = es_check(es, first_pair, n_pairs, "wg_es_perturb", &lay, &K64)) return rc;
+    const int32_t K = (int32_t)K64;
+    int32_t ppb;
+    const dim3 grid = es_perturb_grid(K, n_pairs, &ppb);
+    es_perturb<<<grid, ES_THREADS, 0, stream>>>(lay, es->theta, K, ppb, (uint32_t)(es->seed & 0xffffffffu),
+                                               (uint32_t)(es->seed >> 32), es->generation, es->sigma, first_pair,
+                                               n_pairs);
+    return wg_launched("wg_es_perturb: launch");
+}
+
+int wg_es_update(const wg_es *es, int32_t first_pair, int32_t n_pairs, const float *util, double scale, float lr,
+                 double *workspace, float *grad, float *theta_out, hipStream_t stream) {
+    EsLayout lay;
+    int64_t K64;
+    if (const int rc = es_check(es, first_pair, n_pairs, "wg_es_update", &lay, &K64)) return rc;
+    return es_update_run("wg_es_update", es, (int32_t)K64, first_pair, n_pairs, util, scale, lr, workspace, grad,
+                         theta_out, stream);
+}
+
+int wg_es_perturb_diag(const wg_es *es, const float *sigma, int32_t first_pair, int32_t n_pairs, hipStream_t stream) {
+    EsLayout lay;
+    int64_t K64;
+    if (const int rc = es_check(es, first_pair, n_pairs, "wg_es_perturb_diag", &lay, &K64, false)) return rc;
+    if (!sigma) return wg_fail(WG_EINVAL, "wg_es_perturb_diag: null sigma vector");
+    const int32_t K = (int32_t)K64;
+    int32_t ppb;
+    const dim3 grid = es_perturb_grid(K, n_pairs, &ppb);
+    es_perturb_diag<<<grid, ES_THREADS, 0, stream>>>(lay, es->theta, sigma, K, ppb, (uint32_t)(es->seed & 0xffffffffu),
+                                                    (uint32_t)(es->seed >> 32), es->generation, first_pair, n_pairs);
+    return wg_launched("wg_es_perturb_diag: launch");
+}
+
+int wg_es_update_diag(const wg_es *es, const float *sigma, int32_t first_pair, int32_t n_pairs, const float *util,
+                      const wg_es_diag_step *step, double *workspace, float *g_theta, float *theta_out, float *g_sigma,
+                      float *sigma_out, hipStream_t stream) {
+    EsLayout lay;
+    int64_t K64;
+    if (const int rc = es_check(es, first_pair, n_pairs, "wg_es_update_diag", &lay, &K64, false)) return rc;
+    return es_update_diag_run("wg_es_update_diag", es, (int32_t)K64, sigma, first_pair, n_pairs, util, step, workspace,
+                              g_theta, theta_out, g_sigma, sigma_out, stream);
+}
+
+int wg_es_perturb_deep(const wg_es *es, const wg_es_mid *mid, int32_t first_pair, int32_t n_pairs, hipStream_t stream) {
+    EsDeepLayout lay;
+    int64_t K64;
+    if (const int rc = es_check_deep(es, mid, first_pair, n_pairs, "wg_es_perturb_deep", &lay, &K64)) return rc;
+    const int32_t K = (int32_t)K64;
+    int32_t ppb;
+    const dim3 grid = es_perturb_grid(K, n_pairs, &ppb);
+    es_perturb_deep<<<grid, ES_THREADS, 0, stream>>>(lay, es->theta, K, ppb, (uint32_t)(es->seed & 0xffffffffu),
+                                                    (uint32_t)(es->seed >> 32), es->generation, es->sigma, first_pair,
+                                                    n_pairs);
+    return wg_launched("wg_es_perturb_deep: launch");
+}
+
+int wg_es_update_deep(const wg_es *es, const wg_es_mid *mid, int32_t first_pair, int32_t n_pairs, const float *util,
+                      double scale, float lr, double *workspace, float *grad, float *theta_out, hipStream_t stream) {
+    EsDeepLayout lay;
+    int64_t K64;
+    if (const int rc = es_check_deep(es, mid, first_pair, n_pairs, "wg_es_update_deep", &lay, &K64)) return rc;
+    return es_update_run("wg_es_update_deep", es, (int32_t)K64, first_pair, n_pairs, util, scale, lr, workspace, grad,
+                         theta_out, stream);
+}
+
+int wg_es_perturb_diag_deep(const wg_es *es, const wg_es_mid *mid, const float *sigma, int32_t first_pair,
+                            int32_t n_pairs, hipStream_t stream) {
+    EsDeepLayout lay;
+    int64_t K64;
+    if (const int rc = es_check_deep(es, mid, first_pair, n_pairs, "wg_es_perturb_diag_deep", &lay, &K64, false))
+        return rc;
+    if (!sigma) return wg_fail(WG_EINVAL, "wg_es_perturb_diag_deep: null sigma vector");
+    const int32_t K = (int32_t)K64;
+    int32_t ppb;
+    const dim3 grid = es_perturb_grid(K, n_pairs, &ppb);
+    es_perturb_diag_deep<<<grid, ES_THREADS, 0, stream>>>(lay, es->theta, sigma, K, ppb,
+                                                         (uint32_t)(es->seed & 0xffffffffu), (uint32_t)(es->seed >> 32),
+                                                         es->generation, first_pair, n_pairs);
+    return wg_launched("wg_es_perturb_diag_deep: launch");
+}
+
+int wg_es_update_diag_deep(const wg_es *es, const wg_es_mid *mid, const float *sigma, int32_t first_pair,
+                           int32_t n_pairs, const float *util, const wg_es_diag_step *step, double *workspace,
+                           float *g_theta, float *theta_out, float *g_sigma, float *sigma_out, hipStream_t stream) {
+    EsDeepLayout lay;
+    int64_t K64;
+    if (const int rc = es_check_deep(es, mid, first_pair, n_pairs, "wg_es_update_diag_deep", &lay, &K64, false))
+        return rc;
+    return es_update_diag_run("wg_es_update_diag_deep", es, (int32_t)K64, sigma, first_pair, n_pairs, util, step,
+                              workspace, g_theta, theta_out, g_sigma, sigma_out, stream);
 }
 
 }  // extern "C"

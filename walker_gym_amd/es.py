@@ -12,6 +12,11 @@ theta +- RN32(sigma * eps_j) (antithetic pairs).  The update is the centred-rank
   grad[k] = scale * sum_j (util[2j] - util[2j+1]) * eps_j[k],   scale = 1 / (2 * n_pairs * sigma),
 summed in float64 in a fixed order (chunks of 256 pairs), then theta += lr * grad in float32.
 
+With hidden2 > 0 both trainers hold a deep MLPPolicy (a second hidden layer, wg_es_mid) and call the _deep entries;
+theta then has six segments: w1 (D*H1), b1 (H1), wm (H1*H2, element (j, k) at j*H2 + k), bm (H2), w2 (H2*C), b2 (C), the
+order of pg's gradient segments for a deep policy.  The noise, the antithetic rule and both updates are unchanged: they
+see the layout through K alone.
+
 AdaptiveEvolutionStrategy over wg_es_perturb_diag / wg_es_update_diag keeps one sigma per parameter (a float32 [K]
 device vector) and adapts it from the same samples (PGPE with symmetric sampling): with d = RN32(sigma[k] * eps),
   g_theta[k] = scale_theta * sum_j (util[2j] - util[2j+1]) * d_j[k]
@@ -67,7 +72,9 @@ def es_noise_numpy(seed: int, generation: int, first_pair: int, n_pairs: int, K:
 
 def es_perturb_numpy(theta, sigma, seed: int, generation: int, first_pair: int, n_pairs: int) -> np.ndarray:
     """The candidates of pairs [first_pair, first_pair + n_pairs) as flat vectors: float32 [2 * n_pairs, K], row 2i the
-    `+` member of pair first_pair + i, row 2i + 1 its `-` member."""
+    `+` member of pair first_pair + i, row 2i + 1 its `-` member.  Any K and any segment layout: the noise is a function
+    of (pair, k) alone, so this restates wg_es_perturb_deep on a six-segment theta as it stands (split_theta(...,
+    H2=...) cuts the rows)."""
     theta = np.ascontiguousarray(theta, dtype=np.float32)
     d = np.float32(sigma) * es_noise_numpy(seed, generation, first_pair, n_pairs, theta.shape[0])
     out = np.empty((2 * n_pairs, theta.shape[0]), np.float32)
@@ -88,7 +95,8 @@ def es_utilities_numpy(fitness) -> np.ndarray:
 
 
 def es_update_numpy(theta, util, seed: int, generation: int, first_pair: int, n_pairs: int, scale: float, lr):
-    """wg_es_update's arithmetic: (grad, theta_out), float32 [K] each.  util is indexed by set ([G])."""
+    """wg_es_update's arithmetic: (grad, theta_out), float32 [K] each.  util is indexed by set ([G]).  Any K: it is
+    wg_es_update_deep's arithmetic on a six-segment theta too (the update never looks at the segments)."""
     theta = np.ascontiguousarray(theta, dtype=np.float32)
     util = np.ascontiguousarray(util, dtype=np.float32)
     K = theta.shape[0]
@@ -108,7 +116,8 @@ def es_update_numpy(theta, util, seed: int, generation: int, first_pair: int, n_
 
 
 def es_perturb_diag_numpy(theta, sigma_vec, seed: int, generation: int, first_pair: int, n_pairs: int) -> np.ndarray:
-    """wg_es_perturb_diag's candidates, laid out as es_perturb_numpy's: d = RN32(sigma_vec[k] * eps)."""
+    """wg_es_perturb_diag's candidates, laid out as es_perturb_numpy's: d = RN32(sigma_vec[k] * eps).  Any K and layout
+    (wg_es_perturb_diag_deep's too), as es_perturb_numpy."""
     theta = np.ascontiguousarray(theta, dtype=np.float32)
     sigma_vec = np.ascontiguousarray(sigma_vec, dtype=np.float32)
     if sigma_vec.shape != theta.shape:
@@ -130,7 +139,7 @@ def diag_step(base=0.0, scale_theta=1.0, scale_sigma=1.0, lr_theta=0.0, lr_sigma
 
 def es_update_diag_numpy(theta, sigma_vec, util, seed: int, generation: int, first_pair: int, n_pairs: int, step):
     """wg_es_update_diag's arithmetic: (g_theta, theta_out, g_sigma, sigma_out), float32 [K] each.  util is indexed by
-    set ([G]); step holds wg_es_diag_step's fields (a dict, see diag_step)."""
+    set ([G]); step holds wg_es_diag_step's fields (a dict, see diag_step).  Any K: wg_es_update_diag_deep's too."""
     f32, f64 = np.float32, np.float64
     theta = np.ascontiguousarray(theta, dtype=f32)
     sg = np.ascontiguousarray(sigma_vec, dtype=f32)
@@ -166,17 +175,28 @@ def es_update_diag_numpy(theta, sigma_vec, util, seed: int, generation: int, fir
         return g_theta, theta_out, g_sigma, sigma_out
 
 
-def param_count(D: int, H: int, Cc: int, biases: bool) -> int:
+def param_count(D: int, H: int, Cc: int, biases: bool, H2: int = 0) -> int:
+    """K of a D -> H -> C policy (H = 0: linear), or with H2 > 0 of the deep D -> H -> H2 -> C one."""
+    if H2:
+        if not H:
+            raise ValueError("H2 > 0 needs H > 0 (a middle layer follows a first hidden layer)")
+        return D * H + H * H2 + H2 * Cc + ((H + H2 + Cc) if biases else 0)
     return (D * H + (H if biases else 0) if H else 0) + (H if H else D) * Cc + (Cc if biases else 0)
 
 
-def split_theta(flat, D: int, H: int, Cc: int, biases: bool) -> dict:
+def split_theta(flat, D: int, H: int, Cc: int, biases: bool, H2: int = 0) -> dict:
     """Views of the segments of flat [..., K] as {'w1': [..., D, H], 'b1': [..., H], 'w2': [..., n2, C], 'b2': [..., C]}
-    (None for an absent one); works on numpy arrays and torch tensors."""
+    (None for an absent one); with H2 > 0 also 'wm': [..., H, H2] and 'bm': [..., H2] between b1 and w2, and n2 = H2.
+    Works on numpy arrays and torch tensors."""
+    if H2 and not H:
+        raise ValueError("H2 > 0 needs H > 0 (a middle layer follows a first hidden layer)")
     lead, o, out = tuple(flat.shape[:-1]), 0, {}
-    n2 = H if H else D
-    for name, shape, there in (("w1", (D, H), H > 0), ("b1", (H,), H > 0 and biases), ("w2", (n2, Cc), True),
-                               ("b2", (Cc,), biases)):
+    n2 = H2 if H2 else (H if H else D)
+    segs = [("w1", (D, H), H > 0), ("b1", (H,), H > 0 and biases)]
+    if H2:
+        segs += [("wm", (H, H2), True), ("bm", (H2,), biases)]
+    segs += [("w2", (n2, Cc), True), ("b2", (Cc,), biases)]
+    for name, shape, there in segs:
         n = int(np.prod(shape)) if there else 0
         out[name] = flat[..., o:o + n].reshape(lead + shape) if there else None
         o += n
@@ -185,26 +205,44 @@ def split_theta(flat, D: int, H: int, Cc: int, biases: bool) -> dict:
     return out
 
 
+def theta_from_policy(policy, set_index: int = 0) -> np.ndarray:
+    """The flat float32 [K] host vector of parameter set `set_index` of an MLPPolicy, shallow or deep, in theta's
+    segment order: what `theta0=` takes to start a trainer from a policy trained elsewhere (walker_gym_amd.pg).  The
+    trainers know one switch, biases=True or False, for all layers: a policy with some biases present and others
+    absent is refused (all of b1 / bm / b2 that its shape has, or none of them)."""
+    g = int(set_index)
+    if not 0 <= g < policy.G:
+        raise ValueError(f"set_index {set_index} outside 0..{policy.G - 1}")
+    names = (["w1", "b1"] if policy.H else []) + (["wm", "bm"] if policy.H2 else []) + ["w2", "b2"]
+    have = [getattr(policy, n) is not None for n in names if n.startswith("b")]
+    if any(have) and not all(have):
+        raise ValueError("theta_from_policy: biases partly present ("
+                         + ", ".join(n for n in names if n.startswith("b") and getattr(policy, n) is not None)
+                         + " set); the trainers take biases=True (every layer) or biases=False (none)")
+    parts = [getattr(policy, n)[g].detach().cpu().numpy().reshape(-1) for n in names if getattr(policy, n) is not None]
+    return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+
+
 # ---------------------------------------------------------------------------------------------------- the trainer
 class EvolutionStrategy:
     """Antithetic evolution strategies with centred-rank utilities over an MLPPolicy of `population` parameter sets on
     env's device.  ask() -> MLPPolicy of the generation's candidates; tell(fitness) -> the update; generation_step() a
     whole generation from the state captured at construction.  obs_norm (walker_gym_amd.normalize.ObsNorm): the
     observation normaliser every candidate and mean_policy() evaluate; the caller updates it (generation_step's obs_out
-    records the rows), the trainer carries it in its state_dict."""
+    records the rows), the trainer carries it in its state_dict.  hidden2 > 0: a deep policy, hidden -> hidden2 units
+    (wm / bm in the MLPPolicy, theta's six segments, the wg_es_*_deep entries); everything else is the same."""
 
     def __init__(self, env, hidden: int = 0, act_dim: Optional[int] = None, biases: bool = True,
                  population: Optional[int] = None, sigma: float = 0.05, lr: float = 0.05, seed: int = 0,
-                 act_limit: float = 1.0, theta0=None, obs_norm=None):
+                 act_limit: float = 1.0, theta0=None, obs_norm=None, hidden2: int = 0):
         import torch
         from .policy import MLPPolicy
         if isinstance(hidden, (tuple, list)) or getattr(hidden, "ndim", 0):
-            # wg_es's theta has the segments w1, b1, w2, b2: a second hidden layer (MLPPolicy(wm=...)) has no place in it
-            raise ValueError(f"hidden {hidden!r}: evolution strategies take at most one hidden layer (an int); a deep "
-                             "MLPPolicy trains through walker_gym_amd.pg")
+            raise ValueError(f"hidden {hidden!r}: `hidden` is the width of one hidden layer (an int); the second hidden "
+                             "layer of a deep policy is hidden2=")
         self.env = env
         N, D = int(env.N), int(env.obs_dim)
-        H, Cc = int(hidden), int(env.batch.A if act_dim is None else act_dim)
+        H, Cc, H2 = int(hidden), int(env.batch.A if act_dim is None else act_dim), int(hidden2)
         G = N if population is None else int(population)
         if G < 2 or G % 2:
             raise ValueError(f"population {G} must be even and >= 2 (antithetic pairs)")
@@ -212,6 +250,10 @@ class EvolutionStrategy:
             raise ValueError(f"population {G} does not divide N = {N}")
         if not 0 <= H <= 256:
             raise ValueError(f"hidden {H} outside 0..256")
+        if not 0 <= H2 <= 256:
+            raise ValueError(f"hidden2 {H2} outside 0..256")
+        if H2 and not H:
+            raise ValueError(f"hidden2 {H2} with hidden 0: a second hidden layer follows a first")
         if Cc < 1:
             raise ValueError(f"act_dim {Cc} < 1")
         if not (np.isfinite(sigma) and sigma > 0):
@@ -220,8 +262,8 @@ class EvolutionStrategy:
             raise ValueError(f"lr must be finite, got {lr!r}")
         if not 0 <= int(seed) < 1 << 64:
             raise ValueError("seed is a uint64")
-        self.D, self.H, self.C, self.G, self.biases = D, H, Cc, G, bool(biases)
-        self.K = param_count(D, H, Cc, self.biases)
+        self.D, self.H, self.H2, self.C, self.G, self.biases = D, H, H2, Cc, G, bool(biases)
+        self.K = param_count(D, H, Cc, self.biases, H2)
         self.sigma, self.lr, self.seed, self.generation = float(np.float32(sigma)), float(np.float32(lr)), int(seed), 0
         dv = env.device
         if theta0 is None:
@@ -233,14 +275,16 @@ class EvolutionStrategy:
                 raise ValueError(f"theta0 has shape {tuple(t0.shape)}, expected ({self.K},)")
             self.theta = t0.to(dv).contiguous()
         # the candidates (allocated once, rewritten by every ask()), behind one MLPPolicy
-        n2 = H if H else D
+        n2 = H2 if H2 else (H if H else D)
         e = lambda *s: torch.empty(s, dtype=torch.float32, device=dv)
         w1 = e(G, D, H) if H else None
         b1 = e(G, H) if H and self.biases else None
         b2 = e(G, Cc) if self.biases else None
         # obs_norm (walker_gym_amd.normalize.ObsNorm, shared by every candidate and by mean_policy(); its owner updates it)
         self.obs_norm = obs_norm
-        self.policy = MLPPolicy(e(G, n2, Cc), b2, w1, b1, act_limit=act_limit, obs_norm=obs_norm)
+        wm = e(G, H, H2) if H2 else None
+        bm = e(G, H2) if H2 and self.biases else None
+        self.policy = MLPPolicy(e(G, n2, Cc), b2, w1, b1, act_limit=act_limit, obs_norm=obs_norm, wm=wm, bm=bm)
         self.act_limit = self.policy.act_limit
         self.n_pairs = G // 2
         self._work = torch.empty((-(-self.n_pairs // CHUNK), self.K), dtype=torch.float64, device=dv)
@@ -248,6 +292,13 @@ class EvolutionStrategy:
         self._state0 = env.batch.state_dict()
 
     # -------------------------------------------------------------------------------------------- the two kernels
+    def _call(self, name: str, es, *args) -> None:
+        """The entry `name` on (es, args), or with a deep policy its _deep twin on (es, mid, args)."""
+        if self.H2:
+            mid = _lib.WgEsMid(hidden2=self.H2, wm=_lib.ptr(self.policy.wm), bm=_lib.ptr(self.policy.bm))
+            name, args = name + "_deep", (C.byref(mid),) + args
+        _lib.check(getattr(_lib.load(), name)(C.byref(es), *args), name)
+
     def _struct(self) -> _lib.WgEs:
         p, pol = _lib.ptr, self.policy
         return _lib.WgEs(n_sets=self.G, obs_dim=self.D, hidden=self.H, act_dim=self.C, seed=self.seed,
@@ -255,10 +306,9 @@ class EvolutionStrategy:
                          w2=p(pol.w2), b2=p(pol.b2))
 
     def ask(self):
-        """Write the generation's candidates (wg_es_perturb over every pair) and return their MLPPolicy (the same
-        object every time: its tensors are rewritten in place)."""
-        es = self._struct()
-        _lib.check(_lib.load().wg_es_perturb(C.byref(es), 0, self.n_pairs, self.env._stream()), "wg_es_perturb")
+        """Write the generation's candidates (wg_es_perturb, or wg_es_perturb_deep, over every pair) and return their
+        MLPPolicy (the same object every time: its tensors are rewritten in place)."""
+        self._call("wg_es_perturb", self._struct(), 0, self.n_pairs, self.env._stream())
         return self.policy
 
     def utilities(self, fitness):
@@ -281,8 +331,8 @@ class EvolutionStrategy:
         es = self._struct()
         scale = 1.0 / (2.0 * self.n_pairs * self.sigma)
         p = _lib.ptr
-        _lib.check(_lib.load().wg_es_update(C.byref(es), 0, self.n_pairs, p(util), scale, self.lr, p(self._work),
-                                            p(self._grad), p(self.theta), self.env._stream()), "wg_es_update")
+        self._call("wg_es_update", es, 0, self.n_pairs, p(util), scale, self.lr, p(self._work), p(self._grad),
+                   p(self.theta), self.env._stream())
         self.generation += 1
         return {"grad": self._grad.clone()}
 
@@ -326,10 +376,11 @@ class EvolutionStrategy:
                 "fitness_min": torch.where(nan, torch.full_like(fit, float("inf")), fit).min()}
 
     def mean_policy(self):
-        """The G = 1 policy of theta (a copy)."""
+        """The G = 1 policy of theta (a copy); deep with hidden2 > 0."""
         from .policy import MLPPolicy
-        seg = split_theta(self.theta.clone(), self.D, self.H, self.C, self.biases)
-        return MLPPolicy(seg["w2"], seg["b2"], seg["w1"], seg["b1"], act_limit=self.act_limit, obs_norm=self.obs_norm)
+        seg = split_theta(self.theta.clone(), self.D, self.H, self.C, self.biases, self.H2)
+        return MLPPolicy(seg["w2"], seg["b2"], seg["w1"], seg["b1"], act_limit=self.act_limit, obs_norm=self.obs_norm,
+                         wm=seg.get("wm"), bm=seg.get("bm"))
 
     def state_dict(self) -> dict:
         sd = {"theta": self.theta.detach().cpu().clone(), "seed": self.seed, "generation": self.generation,
@@ -359,7 +410,7 @@ class AdaptiveEvolutionStrategy(EvolutionStrategy):
     def __init__(self, env, hidden: int = 0, act_dim: Optional[int] = None, biases: bool = True,
                  population: Optional[int] = None, sigma=0.05, lr: float = 0.05, seed: int = 0,
                  act_limit: float = 1.0, theta0=None, sigma_lr: float = 0.1, sigma_max_change: float = 0.2,
-                 sigma_min: float = 1e-8, sigma_max: float = float("inf"), obs_norm=None):
+                 sigma_min: float = 1e-8, sigma_max: float = float("inf"), obs_norm=None, hidden2: int = 0):
         import torch
         s0 = np.asarray(sigma.detach().cpu() if hasattr(sigma, "detach") else sigma, dtype=np.float32)
         if s0.ndim > 1:
@@ -374,7 +425,7 @@ class AdaptiveEvolutionStrategy(EvolutionStrategy):
             raise ValueError(f"need 0 < sigma_min <= sigma_max, got {sigma_min!r}, {sigma_max!r}")
         super().__init__(env, hidden=hidden, act_dim=act_dim, biases=biases, population=population,
                          sigma=float(s0.reshape(-1)[0]), lr=lr, seed=seed, act_limit=act_limit, theta0=theta0,
-                         obs_norm=obs_norm)
+                         obs_norm=obs_norm, hidden2=hidden2)
         if s0.ndim == 1 and s0.shape[0] != self.K:
             raise ValueError(f"sigma has {s0.shape[0]} entries, expected a scalar or ({self.K},)")
         self.sigma = 0.0                 # wg_es's scalar: the _diag calls do not read it
@@ -395,10 +446,9 @@ class AdaptiveEvolutionStrategy(EvolutionStrategy):
                          sigma_max=self.sigma_max)
 
     def ask(self):
-        """Write the generation's candidates (wg_es_perturb_diag over every pair) and return their MLPPolicy."""
-        es = self._struct()
-        _lib.check(_lib.load().wg_es_perturb_diag(C.byref(es), _lib.ptr(self.sigma_vec), 0, self.n_pairs,
-                                                  self.env._stream()), "wg_es_perturb_diag")
+        """Write the generation's candidates (wg_es_perturb_diag, or wg_es_perturb_diag_deep, over every pair) and
+        return their MLPPolicy."""
+        self._call("wg_es_perturb_diag", self._struct(), _lib.ptr(self.sigma_vec), 0, self.n_pairs, self.env._stream())
         return self.policy
 
     def tell(self, fitness) -> dict:
@@ -406,9 +456,8 @@ class AdaptiveEvolutionStrategy(EvolutionStrategy):
         Returns {'grad': [K] f32, 'grad_sigma': [K] f32}, the two estimates the steps were taken along."""
         util = self.utilities(fitness).contiguous()
         es, st, p = self._struct(), _lib.WgEsDiagStep(**self.step_fields()), _lib.ptr
-        _lib.check(_lib.load().wg_es_update_diag(C.byref(es), p(self.sigma_vec), 0, self.n_pairs, p(util), C.byref(st),
-                                                 p(self._work), p(self._grad), p(self.theta), p(self._grad_sigma),
-                                                 p(self.sigma_vec), self.env._stream()), "wg_es_update_diag")
+        self._call("wg_es_update_diag", es, p(self.sigma_vec), 0, self.n_pairs, p(util), C.byref(st), p(self._work),
+                   p(self._grad), p(self.theta), p(self._grad_sigma), p(self.sigma_vec), self.env._stream())
         self.generation += 1
         self._told = {"grad": self._grad.clone(), "grad_sigma": self._grad_sigma.clone()}
         return self._told
