@@ -28,6 +28,13 @@ row's return is the hold's summed reward plus the discounted value at the next d
 wg_rollout_deep, pg.policy_rows through wg_policy_forward_deep / wg_policy_backward_deep); the 64 x 64 or 32 x 32 actor of
 the PPO baselines is --hidden 64 --hidden2 64.  The middle matrix starts at 1 / sqrt(hidden).
     python scripts/ppo_train.py --hidden 64 --hidden2 64
+
+--fused-loss: the density, the ratio, the clip, the minimum, the masking and their backward in one kernel call
+(pg.ppo_surrogate: wg_ppo_surrogate, its exponential the library's own wg_expf) instead of the torch composition below:
+old_lp comes from pg.log_prob_rows, the minibatch loss from pg.ppo_surrogate on pg.policy_rows' mean and the critic's
+values.  The first-pass ratio is still exactly 1 (exp(+0) = 1 in wg_expf).  Off by default: without the flag the script
+runs as before.
+    python scripts/ppo_train.py --fused-loss --out profiles/r30_ppo_fused_loss_balance_curve.json
 """
 import argparse
 import json
@@ -65,6 +72,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--obs-norm", action="store_true")
     ap.add_argument("--act-every", type=int, default=1)
+    ap.add_argument("--fused-loss", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.manual_seed(a.seed)
@@ -109,7 +117,10 @@ def main():
         adv_n = torch.where(ok, (adv - adv[ok].mean()) / (adv[ok].std() + 1e-8), torch.zeros_like(adv))
         ret_0 = torch.where(ok, ret, torch.zeros_like(ret))
         with torch.no_grad():   # the old policy's density: the same function on the same rows, before any update
-            old_lp = log_prob(pg.policy_rows(pol, obs, ok), u)
+            if a.fused_loss:
+                old_lp = pg.log_prob_rows(pg.policy_rows(pol, obs, ok), u, sigma.reshape(-1), log_sigma.detach(), ok)
+            else:
+                old_lp = log_prob(pg.policy_rows(pol, obs, ok), u)
             first_ratio_dev = None
         T = obs.shape[0]
         for _ in range(a.epochs):
@@ -118,6 +129,18 @@ def main():
                 mask = ok & (part == m)           # the minibatch: a row mask (skipped rows are neither read nor summed)
                 cnt = mask.sum().clamp(min=1)
                 mean = pg.policy_rows(pol, obs, mask)
+                if a.fused_loss:
+                    value = value_fn(torch.where(mask[..., None], obs, torch.zeros_like(obs)))
+                    loss, info = pg.ppo_surrogate(mean, u, log_sigma, old_lp, adv_n, mask, a.clip, value=value, ret=ret_0)
+                    if first_ratio_dev is None:   # exactly 0: exp(+0) = 1 in the library's own exponential
+                        ratio = pg.expf(torch.where(mask, info["logp"] - old_lp, torch.zeros_like(old_lp)))
+                        first_ratio_dev = float((ratio[mask] - 1).abs().max())
+                    v_loss = info["value_loss"].to(torch.float32)
+                    opt.zero_grad(set_to_none=True)
+                    loss.backward()
+                    torch.nn.utils.clip_grad_norm_([*actor, log_sigma, *critic.parameters()], 0.5)
+                    opt.step()
+                    continue
                 lp = torch.where(mask, log_prob(mean, torch.where(mask[..., None], u, torch.zeros_like(u))), old_lp)
                 ratio = (lp - old_lp).exp()
                 if first_ratio_dev is None:       # exactly 0: the trained function is the function the kernel ran
@@ -147,7 +170,8 @@ def main():
     torch.cuda.synchronize()
     res = {"env": "Balance-v0", "walkers": N, "hidden": H, "hidden2": H2, "steps": a.steps, "iterations": a.iterations,
            "epochs": a.epochs, "minibatches": a.minibatches, "lr": a.lr, "clip": a.clip, "gamma": a.gamma,
-           "lam": a.lam, "max_steps": a.max_steps, "seed": a.seed, "obs_norm": bool(a.obs_norm), "act_every": a.act_every, "seconds": time.perf_counter() - t0,
+           "lam": a.lam, "max_steps": a.max_steps, "seed": a.seed, "obs_norm": bool(a.obs_norm), "act_every": a.act_every,
+           "fused_loss": bool(a.fused_loss), "seconds": time.perf_counter() - t0,
            "device": torch.cuda.get_device_name(0), "curve": curve}
     if a.out:
         with open(a.out, "w") as f:

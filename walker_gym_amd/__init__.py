@@ -16,7 +16,9 @@ statistics on the device (wg_obs_moments) and the normaliser MLPPolicy(obs_norm=
 (wg_rollout_normalized, wg_policy_forward_normalized / wg_policy_backward_normalized); BatchedPhysicsEnv.rollout_held,
 the resident closed loop with an action hold (decide every k steps: wg_rollout_held), and pg.gae_held on its decision
 grid (wg_gae_held); MLPPolicy(wm=..., bm=...), a second hidden layer in the rollouts and the row kernels (wg_rollout_deep,
-wg_policy_forward_deep / wg_policy_backward_deep).
+wg_policy_forward_deep / wg_policy_backward_deep); pg.expf, the library's own pinned exponential (wg_expf), and
+pg.log_prob_rows / pg.ppo_surrogate, the Gaussian density and the clipped PPO surrogate with its gradients in one kernel
+call (wg_ppo_surrogate).
 Importing the package needs no GPU; stepping does (no CPU fallback).
 """
 from .engine import Config, DingPoint, Point, to_data  # noqa: F401
@@ -56,6 +58,10 @@ def __getattr__(name):
         from . import batched_env
         return batched_env.BatchedPhysicsEnv.rollout_held
     if name in ("gae_held", "gae_held_numpy", "hold_decide_numpy"):   # pg's GAE on the hold's decision grid
+        import importlib
+        return getattr(importlib.import_module(".pg", __name__), name)
+    if name in ("expf", "expf_numpy", "log_prob_rows", "ppo_surrogate", "ppo_surrogate_numpy"):
+        # pg's pinned exponential (wg_expf) and the fused clipped surrogate over recorded rows (wg_ppo_surrogate)
         import importlib
         return getattr(importlib.import_module(".pg", __name__), name)
     if name in ("PhysicsEnv", "make_env"):

@@ -127,6 +127,13 @@ class WgPolicyMid(C.Structure):
     _fields_ = [("hidden2", C.c_int32), ("wm", _vp), ("bm", _vp)]
 
 
+class WgPpoRows(C.Structure):
+    """wg_ppo_rows: the recorded means and raw actions of wg_ppo_surrogate, and the density's sigma / log_sigma."""
+    _fields_ = [("y", _vp), ("y_step", C.c_int64), ("u", _vp), ("u_step", C.c_int64), ("sigma", _vp), ("log_sigma", _vp),
+                ("mask", _vp), ("mask_step", C.c_int64), ("n_steps", C.c_int32), ("N", C.c_int32), ("n_sets", C.c_int32),
+                ("act_dim", C.c_int32)]
+
+
 POLICY_GRAD_MAX_K = 16384   # WG_POLICY_GRAD_MAX_K
 
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
@@ -137,7 +144,8 @@ EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_r
            "wg_es_perturb_diag", "wg_es_update_diag", "wg_rollout_normalized", "wg_policy_forward_normalized",
            "wg_policy_backward_normalized", "wg_obs_moments_workspace", "wg_obs_moments", "wg_rollout_held", "wg_gae_held",
            "wg_rollout_deep", "wg_policy_forward_deep", "wg_policy_backward_deep_workspace", "wg_policy_backward_deep",
-           "wg_es_perturb_deep", "wg_es_update_deep", "wg_es_perturb_diag_deep", "wg_es_update_diag_deep")
+           "wg_es_perturb_deep", "wg_es_update_deep", "wg_es_perturb_diag_deep", "wg_es_update_diag_deep", "wg_expf",
+           "wg_ppo_surrogate_workspace", "wg_ppo_surrogate")
 
 _lib = None
 _lock = threading.Lock()
@@ -202,6 +210,10 @@ def load(path: str | None = None):
         L.wg_obs_moments_workspace.argtypes = [C.POINTER(WgPolicyRows), C.c_int32, C.c_int32]
         L.wg_obs_moments.argtypes = [C.POINTER(WgPolicyRows), C.c_int32, C.c_float, C.c_int32, _vp, _vp, C.c_double,
                                      _vp, _vp, _vp]
+        L.wg_expf.argtypes = [_vp, C.c_int64, _vp, _vp]
+        L.wg_ppo_surrogate_workspace.argtypes = [C.POINTER(WgPpoRows), C.c_int32]
+        L.wg_ppo_surrogate.argtypes = [C.POINTER(WgPpoRows), _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_float, C.c_int32,
+                                       _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]
         L.wg_es_perturb.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp]
         L.wg_es_update.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp, C.c_double, C.c_float, _vp, _vp, _vp, _vp]
         L.wg_es_perturb_diag.argtypes = [C.POINTER(WgEs), _vp, C.c_int32, C.c_int32, _vp]
@@ -236,6 +248,7 @@ def load(path: str | None = None):
         L.wg_policy_backward_workspace.restype = C.c_int64
         L.wg_policy_backward_deep_workspace.restype = C.c_int64
         L.wg_obs_moments_workspace.restype = C.c_int64
+        L.wg_ppo_surrogate_workspace.restype = C.c_int64
         v = L.wg_abi_version()
         if v != ABI_VERSION:
             raise WalkerHipError(f"{p}: ABI version {v}, expected {ABI_VERSION}")

@@ -38,6 +38,15 @@
 //                        OM_NC columns a pass; wider rows walk the chunk again for the next columns).
 //   obs_moments_tail     one workgroup: a thread per column adds the chunks in order into the caller's state, then
 //                        derives mean and scale.
+//
+// and wg_expf / wg_ppo_surrogate: the pinned exponential (wg_expf.h) and the clipped surrogate over recorded rows.
+//
+//   ppo_logp_rows     the density mode: a thread per row, the Gaussian log-density summed over c ascending.
+//   ppo_rows_partial  a workgroup owns one (set, chunk): a thread per row of a tile (16-byte loads of y / u and stores of
+//                     dy where act_dim % 4 == 0 and the addresses allow) computes the density, the ratio through
+//                     wg_expf_scalar, the clip and the row's dy, and leaves its terms in LDS; then thread j < act_dim + 5
+//                     adds the tile's rows in ascending rho, one float64 chain per element.
+//   ppo_rows_tail     one workgroup: the chunks' partials added in order, then the sets' statistics.
 
 #include <hip/hip_runtime.h>
 
@@ -48,6 +57,7 @@
 
 #include "walker_hip.h"
 #include "walker_internal.h"   // wg_fail, wg_launched: the refusals here go to the library's one error message
+#include "wg_expf.h"           // wg_expf_scalar: the pinned exponential of wg_expf and of the surrogate's ratio
 
 namespace {
 
@@ -791,6 +801,189 @@ __global__ __launch_bounds__(PR_THREADS) void obs_moments_tail(const double *__r
     }
 }
 
+// ------------------------------------------------------------------------------------------------ PPO surrogate
+constexpr int PPO_STATS = 5;   // rows, surrogate, log-ratio, clipped, value error: the elements behind the act_dim sums
+
+struct PpoArgs {
+    const float *y, *u, *sigma, *log_sigma;
+    const uint8_t *mask;
+    const float *old_logp, *adv, *value, *ret, *scale;
+    float *logp_out, *dy, *dvalue;
+    int64_t y_step, u_step, mask_step, row_step, dy_step;
+    int32_t n_steps, N, n;          // n = N / n_sets walkers per set
+    int32_t C, Cs, TR, chunk_rows;  // Cs = C | 1, the LDS row length (odd: the rows of a wave fall on distinct banks)
+    float lo, hi;                   // RN32(1 - clip_eps), RN32(1 + clip_eps)
+};
+
+// The row's log-density, c ascending; with zs, z[c] is left in zs[c].  V4: act_dim % 4 == 0 and rows on 16-byte addresses.
+template <bool V4>
+__device__ __forceinline__ float ppo_logp(const float *__restrict__ yr, const float *__restrict__ ur,
+                                          const float *__restrict__ sg, const float *__restrict__ ls, int C, float *zs) {
+    const float K0 = __builtin_bit_cast(float, 0x3F6B3F8Eu);   // RN32(0.5 * ln(2 pi))
+    float logp = 0.0f;
+    auto unit = [&](int c, float y, float u) {
+        const float z = __fdiv_rn(__fsub_rn(u, y), sg[c]);
+        const float l = __fsub_rn(__fsub_rn(__fmul_rn(-0.5f, __fmul_rn(z, z)), ls[c]), K0);
+        logp = __fadd_rn(logp, l);
+        if (zs) zs[c] = z;
+    };
+    if (V4) {
+        for (int c = 0; c < C; c += 4) {
+            const float4 vy = *reinterpret_cast<const float4 *>(yr + c), vu = *reinterpret_cast<const float4 *>(ur + c);
+            unit(c, vy.x, vu.x); unit(c + 1, vy.y, vu.y); unit(c + 2, vy.z, vu.z); unit(c + 3, vy.w, vu.w);
+        }
+    } else {
+        for (int c = 0; c < C; c++) unit(c, yr[c], ur[c]);
+    }
+    return logp;
+}
+
+// wg_ppo_surrogate's density mode: a thread per row of the whole batch.
+template <bool V4>
+__global__ __launch_bounds__(PR_THREADS) void ppo_logp_rows(PpoArgs a, int64_t rows) {
+    const int64_t idx = (int64_t)blockIdx.x * PR_THREADS + threadIdx.x;
+    if (idx >= rows) return;
+    const int64_t t = idx / a.N, w = idx - t * a.N;
+    if (a.mask && a.mask[t * a.mask_step + w] == 0) return;   // (per lane: a skipped row is not loaded)
+    const int64_t g = w / a.n;
+    a.logp_out[t * a.row_step + w] = ppo_logp<V4>(a.y + t * a.y_step + w * a.C, a.u + t * a.u_step + w * a.C,
+                                                  a.sigma + g * a.C, a.log_sigma + g * a.C, a.C, nullptr);
+}
+
+// Element j of a row's terms added to P: j < C the log-sigma term (an exact product: one float64 fma), then the five
+// statistics.  f: bit 0 the row is unskipped, bit 1 it was clipped.
+__device__ __forceinline__ double ppo_add(double P, int j, int C, int f, float wr, float qm1, float surr, float d,
+                                          float ev) {
+    if (j < C) return fma((double)wr, (double)qm1, P);
+    switch (j - C) {
+        case 0: return __dadd_rn(P, 1.0);
+        case 1: return __dadd_rn(P, (double)surr);
+        case 2: return __dadd_rn(P, (double)d);
+        case 3: return __dadd_rn(P, (f & 2) ? 1.0 : 0.0);
+        default: return fma((double)ev, (double)ev, P);
+    }
+}
+
+// A workgroup owns one (set, chunk) and walks its rows in order, TR at a time: thread r takes row base + r (density,
+// ratio, clip, dy; its z row, then q - 1, in LDS), then thread j < act_dim + 5 adds the tile's rows in ascending rho, one
+// float64 chain per element (act_dim > 251: threads 0..4 carry a second chain, element 256 + j).
+// LDS, in floats: zs[TR][Cs] wr[TR] surr[TR] d[TR] ev[TR] flag[TR]
+template <bool V4>
+__global__ __launch_bounds__(PR_THREADS) void ppo_rows_partial(PpoArgs a, int64_t n_chunks, double *__restrict__ ws) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *zs = lds, *wrs = zs + a.TR * a.Cs, *surrs = wrs + a.TR, *dls = surrs + a.TR, *evs = dls + a.TR;
+    int *flag = reinterpret_cast<int *>(evs + a.TR);
+    const int g = (int)(blockIdx.x / n_chunks);
+    const int64_t k = blockIdx.x - (int64_t)g * n_chunks;
+    const int64_t lo = k * a.chunk_rows, set_rows = (int64_t)a.n_steps * a.n;
+    const int64_t hi = set_rows - lo < a.chunk_rows ? set_rows : lo + a.chunk_rows;
+    const float *sg = a.sigma + (int64_t)g * a.C, *ls = a.log_sigma + (int64_t)g * a.C;
+    const float sc0 = a.scale[0], sc1 = a.value ? a.scale[1] : 0.0f;
+    const int C = a.C, J = C + PPO_STATS, r = (int)threadIdx.x, j2 = r + PR_THREADS;
+    double P = 0.0, P2 = 0.0;
+    for (int64_t base = lo; base < hi; base += a.TR) {
+        if (r < a.TR) {
+            const int64_t rho = base + r;
+            bool on = rho < hi;
+            int64_t t = 0, w = 0;
+            if (on) {
+                t = rho / a.n;
+                w = (int64_t)g * a.n + (rho - t * a.n);
+                on = !a.mask || a.mask[t * a.mask_step + w] != 0;   // (per lane: a skipped row is not loaded)
+            }
+            int f = 0;
+            if (on) {
+                const int64_t at = t * a.row_step + w;
+                float *z = zs + r * a.Cs;
+                const float logp = ppo_logp<V4>(a.y + t * a.y_step + w * C, a.u + t * a.u_step + w * C, sg, ls, C, z);
+                if (a.logp_out) a.logp_out[at] = logp;
+                const float d = __fsub_rn(logp, a.old_logp[at]);
+                const float rr = wg_expf_scalar(d), A = a.adv[at];
+                const float s1 = __fmul_rn(rr, A);
+                const float rc = (rr < a.lo) ? a.lo : ((rr > a.hi) ? a.hi : rr);
+                const float s2 = __fmul_rn(rc, A);
+                const bool take = s1 <= s2;                          // (a NaN compares false)
+                const float wr = __fmul_rn(sc0, take ? s1 : 0.0f);
+                float ev = 0.0f;
+                if (a.value) {
+                    ev = __fsub_rn(a.value[at], a.ret[at]);
+                    if (a.dvalue) a.dvalue[at] = __fmul_rn(sc1, ev);
+                }
+                float *dr = a.dy ? a.dy + t * a.dy_step + w * C : nullptr;
+                if (V4) {
+                    for (int c = 0; c < C; c += 4) {
+                        float4 v;
+                        v.x = __fmul_rn(wr, __fdiv_rn(z[c], sg[c]));
+                        v.y = __fmul_rn(wr, __fdiv_rn(z[c + 1], sg[c + 1]));
+                        v.z = __fmul_rn(wr, __fdiv_rn(z[c + 2], sg[c + 2]));
+                        v.w = __fmul_rn(wr, __fdiv_rn(z[c + 3], sg[c + 3]));
+                        if (dr) *reinterpret_cast<float4 *>(dr + c) = v;
+#pragma unroll
+                        for (int i = 0; i < 4; i++) z[c + i] = __fsub_rn(__fmul_rn(z[c + i], z[c + i]), 1.0f);
+                    }
+                } else {
+                    for (int c = 0; c < C; c++) {
+                        const float zc = z[c];
+                        if (dr) dr[c] = __fmul_rn(wr, __fdiv_rn(zc, sg[c]));
+                        z[c] = __fsub_rn(__fmul_rn(zc, zc), 1.0f);
+                    }
+                }
+                wrs[r] = wr;
+                surrs[r] = take ? s1 : s2;
+                dls[r] = d;
+                evs[r] = ev;
+                f = 1 | (rc != rr ? 2 : 0);
+            }
+            flag[r] = f;
+        }
+        __syncthreads();
+        if (r < J) {
+            for (int q = 0; q < a.TR; q++) {
+                const int f = flag[q];
+                if (!(f & 1)) continue;
+                P = ppo_add(P, r, C, f, wrs[q], zs[q * a.Cs + (r < C ? r : 0)], surrs[q], dls[q], evs[q]);
+                if (j2 < J) P2 = ppo_add(P2, j2, C, f, wrs[q], 0.0f, surrs[q], dls[q], evs[q]);   // (j2 >= 256 >= C)
+            }
+        }
+        __syncthreads();
+    }
+    double *out = ws + ((int64_t)g * n_chunks + k) * J;
+    if (r < J) out[r] = P;
+    if (j2 < J) out[j2] = P2;
+}
+
+// One workgroup: S_g[j], the chunks' partials added in order; g_log_sigma[g][c] = RN32(S_g[c]); stats[j], the sets'
+// S_g[act_dim + j] added in order.
+__global__ __launch_bounds__(PR_THREADS) void ppo_rows_tail(const double *__restrict__ ws, int64_t n_chunks, int32_t G,
+                                                            int32_t C, float *__restrict__ g_log_sigma,
+                                                            double *__restrict__ stats) {
+    const int J = C + PPO_STATS;
+    if (g_log_sigma)
+        for (int64_t i = threadIdx.x; i < (int64_t)G * C; i += PR_THREADS) {
+            const int64_t g = i / C;
+            const double *p = ws + g * n_chunks * J + (i - g * C);
+            double S = 0.0;
+            for (int64_t k = 0; k < n_chunks; k++) S = __dadd_rn(S, p[k * J]);
+            g_log_sigma[i] = (float)S;
+        }
+    if (stats && threadIdx.x < PPO_STATS) {
+        double st = 0.0;
+        for (int64_t g = 0; g < G; g++) {
+            const double *p = ws + g * n_chunks * J + C + threadIdx.x;
+            double S = 0.0;
+            for (int64_t k = 0; k < n_chunks; k++) S = __dadd_rn(S, p[k * J]);
+            st = __dadd_rn(st, S);
+        }
+        stats[threadIdx.x] = st;
+    }
+}
+
+// wg_expf: a thread per element, the grid striding past 2^31 elements.
+__global__ __launch_bounds__(PR_THREADS) void expf_rows(const float *x, int64_t n, float *out) {
+    for (int64_t i = (int64_t)blockIdx.x * PR_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * PR_THREADS)
+        out[i] = wg_expf_scalar(x[i]);
+}
+
 // [p, p + bytes) of an array of `elem`-byte elements, [n_steps][N] with `stride` elements between steps
 struct Span {
     uintptr_t lo, hi;
@@ -1184,9 +1377,141 @@ int om_check(const wg_policy_rows *rows, int32_t obs_dim, int32_t chunk_rows, co
     return 0;
 }
 
+// What wg_ppo_surrogate_workspace and wg_ppo_surrogate check alike, in the header's order; fills the rows' part of the
+// kernel's arguments and the chunk count.
+int ppo_check(const wg_ppo_rows *rows, int32_t chunk_rows, const char *who, PpoArgs *a, int64_t *n_chunks) {
+    if (!rows) return wg_fail(WG_EINVAL, "%s: null rows", who);
+    if (!rows->y) return wg_fail(WG_EINVAL, "%s: null y", who);
+    if (!rows->u) return wg_fail(WG_EINVAL, "%s: null u", who);
+    if (!rows->sigma) return wg_fail(WG_EINVAL, "%s: null sigma", who);
+    if (!rows->log_sigma) return wg_fail(WG_EINVAL, "%s: null log_sigma", who);
+    if (rows->act_dim < 1 || rows->act_dim > 256)
+        return wg_fail(WG_EINVAL, "%s: act_dim %d outside 1..256", who, rows->act_dim);
+    if (rows->n_steps < 1) return wg_fail(WG_EINVAL, "%s: n_steps %d < 1", who, rows->n_steps);
+    if (rows->N < 1) return wg_fail(WG_EINVAL, "%s: N %d < 1", who, rows->N);
+    if (rows->n_sets < 1 || rows->N % rows->n_sets != 0)
+        return wg_fail(WG_EINVAL, "%s: n_sets %d does not divide N = %d", who, rows->n_sets, rows->N);
+    const int64_t NC = (int64_t)rows->N * rows->act_dim;
+    if (NC > INT32_MAX) return wg_fail(WG_ERANGE, "%s: a step's rows pass 2^31 elements", who);
+    if (rows->y_step < NC)
+        return wg_fail(WG_EINVAL, "%s: y_step %lld < N * act_dim = %lld", who, (long long)rows->y_step, (long long)NC);
+    if (rows->u_step < NC)
+        return wg_fail(WG_EINVAL, "%s: u_step %lld < N * act_dim = %lld", who, (long long)rows->u_step, (long long)NC);
+    if (rows->mask && rows->mask_step < rows->N)
+        return wg_fail(WG_EINVAL, "%s: mask_step %lld < N = %d", who, (long long)rows->mask_step, rows->N);
+    if (chunk_rows < 1) return wg_fail(WG_EINVAL, "%s: chunk_rows %d < 1", who, chunk_rows);
+    *a = PpoArgs{};
+    a->y = rows->y; a->u = rows->u; a->sigma = rows->sigma; a->log_sigma = rows->log_sigma; a->mask = rows->mask;
+    a->y_step = rows->y_step; a->u_step = rows->u_step; a->mask_step = rows->mask ? rows->mask_step : 0;
+    a->n_steps = rows->n_steps; a->N = rows->N; a->n = rows->N / rows->n_sets;
+    a->C = rows->act_dim; a->Cs = rows->act_dim | 1; a->chunk_rows = chunk_rows;
+    const int row = 4 * (a->Cs + PPO_STATS);
+    a->TR = PR_LDS / row < PR_THREADS ? PR_LDS / row : PR_THREADS;
+    *n_chunks = ((int64_t)a->n_steps * a->n + chunk_rows - 1) / chunk_rows;
+    if (*n_chunks * rows->n_sets > INT32_MAX)
+        return wg_fail(WG_ERANGE, "%s: %lld chunks in %d sets pass 2^31 workgroups", who, (long long)*n_chunks,
+                       rows->n_sets);
+    return 0;
+}
+
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
 }  // namespace
 
 extern "C" {
+
+int wg_expf(const float *x, int64_t n, float *out, hipStream_t stream) {
+    if (!x) return wg_fail(WG_EINVAL, "wg_expf: null x");
+    if (!out) return wg_fail(WG_EINVAL, "wg_expf: null out");
+    if (n < 1) return wg_fail(WG_EINVAL, "wg_expf: n %lld < 1", (long long)n);
+    if (x != out && overlap(span_of(x, 1, n, 0, 4), span_of(out, 1, n, 0, 4)))
+        return wg_fail(WG_EINVAL, "wg_expf: out overlaps x without being x");
+    const int64_t blocks = (n + PR_THREADS - 1) / PR_THREADS;
+    expf_rows<<<(unsigned)(blocks < (1 << 20) ? blocks : (1 << 20)), PR_THREADS, 0, stream>>>(x, n, out);
+    return wg_launched("wg_expf: launch");
+}
+
+int64_t wg_ppo_surrogate_workspace(const wg_ppo_rows *rows, int32_t chunk_rows) {
+    PpoArgs a;
+    int64_t n_chunks;
+    if (const int rc = ppo_check(rows, chunk_rows, "wg_ppo_surrogate_workspace", &a, &n_chunks)) return rc;
+    return (int64_t)rows->n_sets * n_chunks * (a.C + PPO_STATS);
+}
+
+int wg_ppo_surrogate(const wg_ppo_rows *rows, const float *old_logp, const float *adv, int64_t row_step,
+                     const float *value, const float *ret, const float *scale, float clip_eps, int32_t chunk_rows,
+                     double *workspace, float *logp_out, float *dy, int64_t dy_step, float *dvalue, float *g_log_sigma,
+                     double *stats, hipStream_t stream) {
+    const char *who = "wg_ppo_surrogate";
+    PpoArgs a;
+    int64_t n_chunks;
+    if (const int rc = ppo_check(rows, chunk_rows, who, &a, &n_chunks)) return rc;
+    if (row_step < a.N) return wg_fail(WG_EINVAL, "%s: row_step %lld < N = %d", who, (long long)row_step, a.N);
+    const int64_t NC = (int64_t)a.N * a.C;
+    if (dy && dy_step < NC)
+        return wg_fail(WG_EINVAL, "%s: dy_step %lld < N * act_dim = %lld", who, (long long)dy_step, (long long)NC);
+    const bool density = old_logp == nullptr;
+    if (density) {
+        if (adv || value || ret || scale || dy || dvalue || g_log_sigma || stats || workspace)
+            return wg_fail(WG_EINVAL, "%s: without old_logp (the density alone) only logp_out may be set", who);
+        if (!logp_out) return wg_fail(WG_EINVAL, "%s: without old_logp (the density alone) logp_out is required", who);
+    } else {
+        if (!adv) return wg_fail(WG_EINVAL, "%s: null adv", who);
+        if (!scale) return wg_fail(WG_EINVAL, "%s: null scale", who);
+        if (!workspace) return wg_fail(WG_EINVAL, "%s: null workspace", who);
+    }
+    if ((value == nullptr) != (ret == nullptr)) return wg_fail(WG_EINVAL, "%s: value and ret go together", who);
+    if (dvalue && !value) return wg_fail(WG_EINVAL, "%s: dvalue without value", who);
+    if (!(clip_eps >= 0.f) || !std::isfinite(clip_eps))
+        return wg_fail(WG_EINVAL, "%s: clip_eps must be finite and >= 0", who);
+    if (!logp_out && !dy && !dvalue && !g_log_sigma && !stats)
+        return wg_fail(WG_EINVAL, "%s: every output pointer is null", who);
+    const int64_t G = rows->n_sets, J = a.C + PPO_STATS;
+    PrBuf in[10], out[6];
+    int n_in = 0, n_out = 0;
+    in[n_in++] = {"y", a.y, span_of(a.y, a.n_steps, NC, a.y_step, 4)};
+    in[n_in++] = {"u", a.u, span_of(a.u, a.n_steps, NC, a.u_step, 4)};
+    in[n_in++] = {"sigma", a.sigma, span_of(a.sigma, 1, G * a.C, 0, 4)};
+    in[n_in++] = {"log_sigma", a.log_sigma, span_of(a.log_sigma, 1, G * a.C, 0, 4)};
+    if (a.mask) in[n_in++] = {"mask", a.mask, span_of(a.mask, a.n_steps, a.N, a.mask_step, 1)};
+    if (old_logp) in[n_in++] = {"old_logp", old_logp, span_of(old_logp, a.n_steps, a.N, row_step, 4)};
+    if (adv) in[n_in++] = {"adv", adv, span_of(adv, a.n_steps, a.N, row_step, 4)};
+    if (value) in[n_in++] = {"value", value, span_of(value, a.n_steps, a.N, row_step, 4)};
+    if (ret) in[n_in++] = {"ret", ret, span_of(ret, a.n_steps, a.N, row_step, 4)};
+    if (scale) in[n_in++] = {"scale", scale, span_of(scale, 1, 2, 0, 4)};
+    if (workspace) out[n_out++] = {"workspace", workspace, span_of(workspace, 1, G * n_chunks * J, 0, 8)};
+    if (logp_out) out[n_out++] = {"logp_out", logp_out, span_of(logp_out, a.n_steps, a.N, row_step, 4)};
+    if (dy) out[n_out++] = {"dy", dy, span_of(dy, a.n_steps, NC, dy_step, 4)};
+    if (dvalue) out[n_out++] = {"dvalue", dvalue, span_of(dvalue, a.n_steps, a.N, row_step, 4)};
+    if (g_log_sigma) out[n_out++] = {"g_log_sigma", g_log_sigma, span_of(g_log_sigma, 1, G * a.C, 0, 4)};
+    if (stats) out[n_out++] = {"stats", stats, span_of(stats, 1, PPO_STATS, 0, 8)};
+    for (int o = 0; o < n_out; o++) {
+        for (int i = 0; i < n_in; i++)
+            if (overlap(out[o].s, in[i].s)) return wg_fail(WG_EINVAL, "%s: %s aliases %s", who, out[o].name, in[i].name);
+        for (int p = 0; p < o; p++)
+            if (overlap(out[o].s, out[p].s)) return wg_fail(WG_EINVAL, "%s: %s aliases %s", who, out[o].name, out[p].name);
+    }
+    a.old_logp = old_logp; a.adv = adv; a.value = value; a.ret = ret; a.scale = scale;
+    a.logp_out = logp_out; a.dy = dy; a.dvalue = dvalue; a.row_step = row_step; a.dy_step = dy ? dy_step : 0;
+    a.lo = 1.0f - clip_eps; a.hi = 1.0f + clip_eps;   // one float32 operation each (-ffp-contract=off)
+    const bool v4 = a.C % 4 == 0 && a.y_step % 4 == 0 && a.u_step % 4 == 0 && a.dy_step % 4 == 0 && aligned16(a.y) &&
+                    aligned16(a.u) && aligned16(dy);
+    if (density) {
+        const int64_t n_rows = (int64_t)a.n_steps * a.N, blocks = (n_rows + PR_THREADS - 1) / PR_THREADS;
+        if (blocks > INT32_MAX) return wg_fail(WG_ERANGE, "%s: %lld rows pass 2^31 workgroups", who, (long long)n_rows);
+        if (v4) ppo_logp_rows<true><<<(unsigned)blocks, PR_THREADS, 0, stream>>>(a, n_rows);
+        else ppo_logp_rows<false><<<(unsigned)blocks, PR_THREADS, 0, stream>>>(a, n_rows);
+        return wg_launched("wg_ppo_surrogate (density): launch");
+    }
+    const size_t lds = (size_t)a.TR * 4 * (a.Cs + PPO_STATS);
+    const dim3 grid((unsigned)(n_chunks * G));
+    if (v4) ppo_rows_partial<true><<<grid, PR_THREADS, lds, stream>>>(a, n_chunks, workspace);
+    else ppo_rows_partial<false><<<grid, PR_THREADS, lds, stream>>>(a, n_chunks, workspace);
+    if (const int rc = wg_launched("wg_ppo_surrogate (partial sums): launch")) return rc;
+    if (!g_log_sigma && !stats) return 0;
+    ppo_rows_tail<<<1, PR_THREADS, 0, stream>>>(workspace, n_chunks, (int32_t)G, a.C, g_log_sigma, stats);
+    return wg_launched("wg_ppo_surrogate (tail): launch");
+}
 
 int wg_gae(const float *reward, const float *value, const float *next_value, const uint8_t *term, const uint8_t *cut,
            int32_t n_steps, int32_t N, int64_t step_stride, float gamma, float lam, float *adv, float *ret,

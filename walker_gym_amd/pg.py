@@ -36,9 +36,23 @@ policy_rows_numpy and policy_grad_numpy restate both on the host, bit for bit.  
 obs.  A policy that carries an obs_norm (walker_gym_amd.normalize) is evaluated on the normalised rows xn in all of
 these (wg_policy_forward_normalized / wg_policy_backward_normalized): xn[i] takes x[i]'s place as the left factor, and
 there is no gradient with respect to mean or scale.
+
+The surrogate.  expf is the library's own exponential (wg_expf: float64, every operation rounded by itself, one rounding
+to float32; expf_numpy restates it).  log_prob_rows is the Gaussian log-density of the recorded raw actions around
+policy_rows' mean, and ppo_surrogate the clipped surrogate of a minibatch with its gradients with respect to that mean,
+log_sigma and the critic's values, one kernel call (wg_ppo_surrogate; ppo_surrogate_numpy restates it).  Per unskipped
+row, float32, every operation rounded by itself, c ascending from logp = +0.0:
+  z[c] = RN32(RN32(u[c] - y[c]) / sigma[c]);  q[c] = RN32(z[c] * z[c])
+  logp = RN32(logp + RN32(RN32(RN32(-0.5 * q[c]) - log_sigma[c]) - K0)),   K0 = RN32(0.5 ln 2 pi)
+  d = RN32(logp - old_logp);  r = expf(d);  s1 = RN32(r * A);  s2 = RN32(clip(r, lo, hi) * A);  take = s1 <= s2
+  wr = RN32(scale[0] * (take ? s1 : +0.0));   dy[c] = RN32(wr * RN32(z[c] / sigma[c]))
+  ev = RN32(value - ret);   dvalue = RN32(scale[1] * ev)
+and per set, in policy_grad_numpy's chunks and order, float64 sums of wr * RN32(q[c] - 1) (exact products) into
+g_log_sigma and of five statistics (rows, surrogate, log-ratio, clipped, squared value error) into stats.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import numpy as np
@@ -597,3 +611,288 @@ def collect(envs, policy, sigma, n_steps: int, seed: int, step_base: int = 0, va
                reset=reset, final_obs=buf["final_obs_out"], action=buf["action_out"], raw_action=buf["raw_action_out"],
                eps=buf["eps_out"], value=value, next_value=next_value, term=term, cut=reset, adv=adv, ret=ret)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- the fused surrogate
+# wg_expf (include/walker_hip.h; csrc/wg_expf.h): the library's own exponential, and wg_ppo_surrogate, the clipped
+# surrogate over recorded rows.  expf_numpy / ppo_surrogate_numpy restate both contracts on the host, bit for bit;
+# expf / log_prob_rows / ppo_surrogate are the device calls.
+EXPF_LOG2E = float.fromhex("0x1.71547652b82fep+0")
+EXPF_LN2_HI = float.fromhex("0x1.62e42fee00000p-1")
+EXPF_LN2_LO = float.fromhex("0x1.a39ef35793c76p-33")
+EXPF_C = tuple(1.0 / math.factorial(n) for n in range(14))   # RN64(1 / n!): n! is exact in float64 up to 13!
+LOGP_K0 = np.array([0x3F6B3F8E], np.uint32).view(np.float32)[0]   # RN32(0.5 * ln(2 pi))
+PPO_STATS = ("rows", "surrogate", "log_ratio", "clipped", "value_error")
+
+
+def expf_numpy(x):
+    """wg_expf on the host: float32 in, float32 out, every float64 operation rounded by itself (numpy never fuses)."""
+    x = np.asarray(x, dtype=np.float32)
+    nan = np.isnan(x)
+    xd = np.clip(np.where(nan, np.float32(0.0), x).astype(np.float64), -150.0, 150.0)
+    k = np.rint(xd * np.float64(EXPF_LOG2E))
+    r = (xd - k * np.float64(EXPF_LN2_HI)) - k * np.float64(EXPF_LN2_LO)
+    p = np.full_like(xd, EXPF_C[13])
+    for n in range(12, -1, -1):
+        p = p * r + np.float64(EXPF_C[n])
+    with np.errstate(over="ignore", under="ignore"):
+        out = np.ldexp(p, k.astype(np.int32)).astype(np.float32)
+    return np.where(nan, x, out)
+
+
+def ppo_surrogate_numpy(y, u, sigma, log_sigma, old_logp=None, adv=None, mask=None, clip_eps: float = 0.2, scale=None,
+                        value=None, ret=None, chunk_rows: int = 256):
+    """wg_ppo_surrogate on the host.  y, u [T, N, C]; sigma, log_sigma [G, C] (or [C]); old_logp, adv, value, ret, mask
+    [T, N].  old_logp None: the density mode, {'logp'} alone.  Otherwise scale = (actor, value coefficient) and the
+    result holds 'logp', 'dy', 'dvalue' (None without value), 'g_log_sigma' [G, C] and 'stats' float64 [5] (PPO_STATS).
+    Skipped rows of logp / dy / dvalue are zero here (the kernel leaves them as they were)."""
+    f32 = np.float32
+    y = np.ascontiguousarray(y, dtype=f32)
+    u = np.ascontiguousarray(u, dtype=f32)
+    if y.ndim != 3 or u.shape != y.shape:
+        raise ValueError(f"y and u must be [T, N, C] alike, got {y.shape} and {u.shape}")
+    T, N, Cc = y.shape
+    sg = np.asarray(sigma, dtype=f32).reshape(-1, Cc)
+    ls = np.asarray(log_sigma, dtype=f32).reshape(-1, Cc)
+    G = sg.shape[0]
+    if ls.shape != sg.shape or N % G != 0:
+        raise ValueError(f"sigma {sg.shape} / log_sigma {ls.shape} must be [G, {Cc}] alike with G dividing N = {N}")
+    n = N // G
+    sets = np.arange(N) // n
+    on = np.ones((T, N), bool) if mask is None else np.asarray(mask).reshape(T, N) != 0
+    zero = f32(0.0)
+    with np.errstate(all="ignore"):
+        # (skipped rows may hold anything: they are computed on zeros and dropped)
+        ym, um = np.where(on[..., None], y, zero), np.where(on[..., None], u, zero)
+        z = (um - ym) / sg[sets][None]
+        q = z * z
+        l = (f32(-0.5) * q - ls[sets][None]) - LOGP_K0
+        logp = np.zeros((T, N), f32)
+        for c in range(Cc):
+            logp = logp + l[:, :, c]
+        out = {"logp": np.where(on, logp, zero)}
+        if old_logp is None:
+            return out
+        if adv is None or scale is None:
+            raise ValueError("the loss mode needs adv and scale")
+        if (value is None) != (ret is None):
+            raise ValueError("value and ret go together")
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 1:
+            raise ValueError("chunk_rows < 1")
+        sc = np.asarray(scale, dtype=f32).reshape(-1)
+        lo, hi = f32(1.0) - f32(clip_eps), f32(1.0) + f32(clip_eps)
+        d = logp - np.where(on, np.asarray(old_logp, dtype=f32).reshape(T, N), zero)
+        r = expf_numpy(d)
+        A = np.where(on, np.asarray(adv, dtype=f32).reshape(T, N), zero)
+        s1 = r * A
+        rc = np.where(r < lo, lo, np.where(r > hi, hi, r)).astype(f32)
+        s2 = rc * A
+        take = s1 <= s2
+        surr = np.where(take, s1, s2)
+        wr = sc[0] * np.where(take, s1, zero)
+        out["dy"] = np.where(on[..., None], wr[..., None] * (z / sg[sets][None]), zero)
+        qm1 = q - f32(1.0)
+        ev = np.zeros((T, N), f32)
+        out["dvalue"] = None
+        if value is not None:
+            ev = np.where(on, np.asarray(value, dtype=f32).reshape(T, N) - np.asarray(ret, dtype=f32).reshape(T, N), zero)
+            out["dvalue"] = np.where(on, sc[1] * ev, zero)
+        f64 = np.float64
+        terms = np.concatenate([wr.astype(f64)[..., None] * qm1.astype(f64), np.ones((T, N, 1)), surr.astype(f64)[..., None],
+                                d.astype(f64)[..., None], (rc != r).astype(f64)[..., None],
+                                (ev.astype(f64) * ev.astype(f64))[..., None]], axis=2).reshape(T, G, n, Cc + 5)
+        v = on.reshape(T, G, n)
+        S, P = np.zeros((G, Cc + 5)), np.zeros((G, Cc + 5))
+        for rho in range(T * n):
+            if rho and rho % chunk_rows == 0:
+                S, P = S + P, np.zeros_like(P)
+            t, i = divmod(rho, n)
+            P = np.where(v[t, :, i, None], P + terms[t, :, i], P)
+        S = S + P
+        out["g_log_sigma"] = S[:, :Cc].astype(f32)
+        stats = np.zeros(5)
+        for g in range(G):
+            stats = stats + S[g, Cc:]
+        out["stats"] = stats
+    return out
+
+
+def _vec(t, who, name, dv, n=None):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dv or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous float32 tensor on {dv}")
+    if n is not None and t.numel() != n:
+        raise ValueError(f"{who}: {name} has {t.numel()} elements, expected {n}")
+    return t
+
+
+def expf(x, out=None):
+    """wg_expf on a contiguous float32 device tensor: the library's exponential, elementwise (out may be x)."""
+    import torch
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("expf: x must be a float32 device tensor")
+    x = _vec(x, "expf", "x", x.device)
+    out = torch.empty_like(x) if out is None else _vec(out, "expf", "out", x.device, x.numel())
+    if x.numel() == 0:
+        return out
+    _lib.check(_lib.load().wg_expf(_lib.ptr(x), x.numel(), _lib.ptr(out), torch.cuda.current_stream(x.device).cuda_stream),
+               "wg_expf")
+    return out
+
+
+def _ppo_rows(mean, raw_action, sigma, log_sigma, mask, who):
+    """(wg_ppo_rows, T, N, G, C, flat, what must stay alive) of mean / raw_action [T, N, C] or [R, C]."""
+    import torch
+    if not isinstance(mean, torch.Tensor) or mean.dim() not in (2, 3) or mean.dtype != torch.float32 or not mean.is_cuda:
+        raise ValueError(f"{who}: mean must be a float32 device tensor [T, N, C] or [R, C]")
+    Cc = int(mean.shape[-1])
+    rows_y, T, N, y3, m3, flat = _rows_of(Cc, mean.device, mean, mask, who)
+    if not isinstance(raw_action, torch.Tensor) or raw_action.shape != mean.shape or raw_action.dtype != torch.float32:
+        raise ValueError(f"{who}: raw_action must be float32 {tuple(mean.shape)}")
+    rows_u, _, _, u3, _, _ = _rows_of(Cc, mean.device, raw_action, None, who)
+    ls = _vec(log_sigma, who, "log_sigma", mean.device)
+    sg = _vec(sigma, who, "sigma", mean.device, ls.numel())
+    if ls.dim() not in (1, 2) or ls.shape[-1] != Cc:
+        raise ValueError(f"{who}: log_sigma must be [{Cc}] or [G, {Cc}], got {tuple(ls.shape)}")
+    G = 1 if ls.dim() == 1 else int(ls.shape[0])
+    rows = _lib.WgPpoRows(y=rows_y.x, y_step=rows_y.x_step, u=rows_u.x, u_step=rows_u.x_step, sigma=_lib.ptr(sg),
+                          log_sigma=_lib.ptr(ls), mask=rows_y.mask, mask_step=rows_y.mask_step, n_steps=T, N=N, n_sets=G,
+                          act_dim=Cc)
+    return rows, T, N, G, Cc, flat, (y3, u3, m3, sg, ls)
+
+
+def log_prob_rows(mean, raw_action, sigma, log_sigma, mask=None):
+    """wg_ppo_surrogate's density mode: the Gaussian log-density of raw_action around mean, summed over the action
+    units in ascending order: float32 [T, N] (or [R]); zero on the rows mask skips.  sigma and log_sigma are [C] or
+    [G, C] device tensors; the kernel computes neither from the other.  No gradient."""
+    import torch
+    rows, T, N, G, Cc, flat, keep = _ppo_rows(mean, raw_action, sigma, log_sigma, mask, "log_prob_rows")
+    dv = mean.device
+    logp = (torch.empty if mask is None else torch.zeros)((T, N), dtype=torch.float32, device=dv)
+    _lib.check(_lib.load().wg_ppo_surrogate(rows, None, None, N, None, None, None, 0.0, 1, None, _lib.ptr(logp), None, 0,
+                                            None, None, None, torch.cuda.current_stream(dv).cuda_stream),
+               "wg_ppo_surrogate")
+    return logp[0] if flat else logp
+
+
+def ppo_surrogate_rows(mean, raw_action, sigma, log_sigma, old_logp, adv, scale, mask=None, clip: float = 0.2, value=None,
+                       ret=None, chunk_rows: Optional[int] = None, want=("logp", "dy", "dvalue", "g_log_sigma", "stats"),
+                       dy_out=None):
+    """wg_ppo_surrogate's loss mode called directly (no autograd): a dict of the outputs named in `want` ('dvalue' only
+    with value).  scale: float32 [2] device tensor.  old_logp / adv / value / ret: contiguous float32 [T, N] (or [R]).
+    dy_out: where dy is written (float32 [T, N, C], only its step dimension strided; skipped rows are left as they
+    were); otherwise the skipped rows of dy, dvalue and logp are zero."""
+    import torch
+    who = "ppo_surrogate"
+    rows, T, N, G, Cc, flat, keep = _ppo_rows(mean, raw_action, sigma, log_sigma, mask, who)
+    dv = mean.device
+    per_row = lambda t, name: None if t is None else _vec(t, who, name, dv, T * N)
+    old_logp, adv = per_row(old_logp, "old_logp"), per_row(adv, "adv")
+    value, ret = per_row(value, "value"), per_row(ret, "ret")
+    if old_logp is None or adv is None:
+        raise ValueError(f"{who}: old_logp and adv are required")
+    scale = _vec(scale, who, "scale", dv, 2)
+    chunk = default_chunk_rows(T, N // G) if chunk_rows is None else int(chunk_rows)
+    L = _lib.load()
+    count = _lib.check(L.wg_ppo_surrogate_workspace(rows, chunk), "wg_ppo_surrogate_workspace")
+    ws = torch.empty(int(count), dtype=torch.float64, device=dv)
+    new = torch.empty if mask is None else torch.zeros
+    out = {}
+    if "logp" in want:
+        out["logp"] = new((T, N), dtype=torch.float32, device=dv)
+    dy3 = None
+    if dy_out is not None:
+        dy3 = dy_out[None] if dy_out.dim() == 2 else dy_out
+        if (dy3.dtype != torch.float32 or dy3.device != dv or tuple(dy3.shape) != (T, N, Cc) or dy3.stride(2) != 1
+                or dy3.stride(1) != Cc):
+            raise ValueError(f"{who}: dy_out must be float32 {(T, N, Cc)} with only its step dimension strided")
+    elif "dy" in want:
+        dy3 = new((T, N, Cc), dtype=torch.float32, device=dv)
+    if dy3 is not None:
+        out["dy"] = dy3
+    if "dvalue" in want and value is not None:
+        out["dvalue"] = new((T, N), dtype=torch.float32, device=dv)
+    if "g_log_sigma" in want:
+        out["g_log_sigma"] = torch.empty((G, Cc), dtype=torch.float32, device=dv)
+    if "stats" in want:
+        out["stats"] = torch.empty(5, dtype=torch.float64, device=dv)
+    p = _lib.ptr
+    _lib.check(L.wg_ppo_surrogate(rows, p(old_logp), p(adv), N, p(value), p(ret), p(scale), float(clip), chunk, p(ws),
+                                  p(out.get("logp")), p(dy3), (dy3.stride(0) if T > 1 else N * Cc) if dy3 is not None else 0,
+                                  p(out.get("dvalue")), p(out.get("g_log_sigma")), p(out.get("stats")),
+                                  torch.cuda.current_stream(dv).cuda_stream), "wg_ppo_surrogate")
+    if flat:
+        for k in ("logp", "dy", "dvalue"):
+            if k in out and (k != "dy" or dy_out is None):
+                out[k] = out[k][0]
+    return out
+
+
+_PPO_FN = None
+
+
+def _ppo_function():
+    global _PPO_FN
+    if _PPO_FN is not None:
+        return _PPO_FN
+    import torch
+
+    class PpoSurrogate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, mean, log_sigma, value, raw_action, old_logp, adv, mask, clip, scale, ret, chunk_rows):
+            sigma = log_sigma.detach().exp()
+            o = ppo_surrogate_rows(mean.detach(), raw_action, sigma, log_sigma.detach(), old_logp, adv, scale, mask, clip,
+                                   None if value is None else value.detach().contiguous(), ret, chunk_rows)
+            stats = o["stats"]
+            loss = (scale[0].double() * stats[1] + 0.5 * scale[1].double() * stats[4]).to(torch.float32)
+            ctx.shapes = (mean.shape, log_sigma.shape, None if value is None else value.shape)
+            ctx.save_for_backward(o["dy"], o["g_log_sigma"], o.get("dvalue"))
+            ctx.mark_non_differentiable(stats, o["logp"])
+            return loss, stats, o["logp"]
+
+        @staticmethod
+        def backward(ctx, g_loss, g_stats, g_logp):
+            dy, g_ls, dvalue = ctx.saved_tensors
+            need, (s_mean, s_ls, s_value) = ctx.needs_input_grad, ctx.shapes
+            g_mean = (dy * g_loss).reshape(s_mean) if need[0] else None
+            g_lsig = (g_ls * g_loss).reshape(s_ls) if need[1] else None
+            g_val = (dvalue * g_loss).reshape(s_value) if (need[2] and dvalue is not None) else None
+            return (g_mean, g_lsig, g_val) + (None,) * 8
+
+    _PPO_FN = PpoSurrogate
+    return PpoSurrogate
+
+
+def ppo_surrogate(mean, raw_action, log_sigma, old_logp, adv, mask=None, clip: float = 0.2, scale=None, value=None,
+                  ret=None, value_scale=None, chunk_rows: Optional[int] = None):
+    """The clipped PPO surrogate of a minibatch in one kernel call (wg_ppo_surrogate), differentiable with respect to
+    mean (pg.policy_rows' output), log_sigma and value: (loss, info).
+
+    mean, raw_action: float32 [T, N, C] (or [R, C]) device tensors, only the step dimension strided; log_sigma [C] or
+    [G, C] (sigma is log_sigma.detach().exp(), what the rollout was given); old_logp (log_prob_rows before the update),
+    adv, and the optional pair value / ret: contiguous [T, N]; mask as in policy_rows (a minibatch is a row mask).
+    loss = scale * sum(min(r A, clip(r) A)) + 0.5 * value_scale * sum((value - ret)^2) over the unskipped rows, a
+    float32 scalar formed on the device from the kernel's float64 sums; scale defaults to -1 / max(count(mask), 1) and
+    value_scale to 1 / max(count(mask), 1), both computed on the device (numbers or 0-d tensors are accepted).  info:
+    'stats' (float64 [5]: PPO_STATS), 'logp' [T, N], 'approx_kl' = -stats[2] / stats[0], 'clip_fraction' =
+    stats[3] / stats[0], 'value_loss' = stats[4] / stats[0], all device tensors.  The backward returns the gradients
+    the forward's kernel call wrote, times the upstream scalar (an upstream of 1 leaves the kernel's bits)."""
+    import torch
+    dv = mean.device
+    T_N = mean.shape[:-1].numel()
+    cnt = None
+    if scale is None or (value is not None and value_scale is None):
+        cnt = (mask.sum() if mask is not None else torch.tensor(T_N, device=dv)).clamp(min=1).to(torch.float32)
+    as_dev = lambda v: v.to(device=dv, dtype=torch.float32).reshape(()) if isinstance(v, torch.Tensor) else \
+        torch.tensor(float(v), dtype=torch.float32, device=dv)
+    s0 = -1.0 / cnt if scale is None else as_dev(scale)
+    s1 = torch.zeros((), dtype=torch.float32, device=dv) if value is None else \
+        (1.0 / cnt if value_scale is None else as_dev(value_scale))
+    sc = torch.stack([s0, s1]).detach().contiguous()
+    loss, stats, logp = _ppo_function().apply(mean, log_sigma, value, raw_action, old_logp, adv, mask, float(clip), sc,
+                                              ret, chunk_rows)
+    rows = stats[0].clamp(min=1.0)
+    info = {"stats": stats, "logp": logp, "approx_kl": -stats[2] / rows, "clip_fraction": stats[3] / rows,
+            "value_loss": stats[4] / rows}
+    return loss, info
