@@ -27,6 +27,11 @@ changes nothing).  The rows are then of order one, so --sigma and --lr default t
 --hidden2 H2: a deep policy, --hidden -> H2 units (the trainers' hidden2=: theta's six segments, the wg_es_*_deep
 entries); --hidden defaults to H2 then.
     python scripts/es_train.py --hidden2 32 --out profiles/r17_es_deep_balance_curve.json
+
+--adam: theta is stepped by the device optimiser (EvolutionStrategy(optimizer="adam"): wg_adam_step along the same
+estimate, lr = --lr, the class's betas, no clip) instead of theta += lr * grad.  Adam's step is of the order of lr per
+parameter whatever the estimate's scale, so --lr means another thing there; nothing is tuned.  Not with --adaptive.
+    python scripts/es_train.py --adam --lr 1e-3 --out profiles/r31_es_adam_balance_curve.json
 """
 import argparse
 import json
@@ -58,8 +63,11 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--act-every", type=int, default=1)
+    ap.add_argument("--adam", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.adam and a.adaptive:
+        ap.error("--adam is the scalar trainer's option (the adaptive theta step is inside wg_es_update_diag)")
     a.sigma = (0.05 if a.obs_norm else 0.001) if a.sigma is None else a.sigma
     a.lr = (0.05 if a.obs_norm else 1e-4) if a.lr is None else a.lr
     if a.hidden2 and not a.hidden:
@@ -76,7 +84,7 @@ def main():
                                        lr=a.lr / a.sigma ** 2, seed=a.seed, obs_norm=nm, hidden2=a.hidden2)
     else:
         tr = EvolutionStrategy(env, hidden=a.hidden, population=a.population, sigma=a.sigma, lr=a.lr, seed=a.seed,
-                               obs_norm=nm, hidden2=a.hidden2)
+                               obs_norm=nm, hidden2=a.hidden2, optimizer="adam" if a.adam else None)
     start = env.batch.state_dict()
     curve = []
     t0 = time.perf_counter()
@@ -104,7 +112,7 @@ def main():
         print(json.dumps(curve[-1]), flush=True)
     torch.cuda.synchronize()
     res = {"env": "Balance-v0", "walkers": env.N, "population": tr.G, "hidden": tr.H, "hidden2": tr.H2, "K": tr.K, "steps": a.steps,
-           "trainer": type(tr).__name__, "obs_norm": bool(a.obs_norm), "act_every": a.act_every, "sigma": a.sigma if a.adaptive else tr.sigma, "lr": tr.lr, "seed": tr.seed, "seconds": time.perf_counter() - t0,
+           "trainer": type(tr).__name__, "obs_norm": bool(a.obs_norm), "act_every": a.act_every, "adam": bool(a.adam), "sigma": a.sigma if a.adaptive else tr.sigma, "lr": tr.lr, "seed": tr.seed, "seconds": time.perf_counter() - t0,
            "device": torch.cuda.get_device_name(0), "curve": curve}
     if a.out:
         with open(a.out, "w") as f:

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Resource usage (VGPRs, SGPR spills, scratch, occupancy) of every kernel in walker_hip.hip, es_hip.hip and pg_hip.hip:
+"""Resource usage (VGPRs, SGPR spills, scratch, occupancy) of every kernel in walker_hip.hip, es_hip.hip, pg_hip.hip and
+opt_hip.hip:
     python scripts/kres.py [extra hipcc flags, e.g. -DWG_LEAN_SOA=0]"""
 import os
 import re
@@ -8,7 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rows, cur = {}, None
-for unit in ("walker_hip.hip", "es_hip.hip", "pg_hip.hip"):
+for unit in ("walker_hip.hip", "es_hip.hip", "pg_hip.hip", "opt_hip.hip"):
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
            "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero", "-mllvm",
            "-amdgpu-kernarg-preload-count=10", "--cuda-device-only", "-c",

@@ -35,6 +35,13 @@ old_lp comes from pg.log_prob_rows, the minibatch loss from pg.ppo_surrogate on 
 values.  The first-pass ratio is still exactly 1 (exp(+0) = 1 in wg_expf).  Off by default: without the flag the script
 runs as before.
     python scripts/ppo_train.py --fused-loss --out profiles/r30_ppo_fused_loss_balance_curve.json
+
+--device-adam: the update's last part on the device too: walker_gym_amd.optim.Adam (wg_adam_step: the global-norm clip
+at max_norm = 0.5 and the Adam step over the actor's tensors, log_sigma and the critic's torch parameters as ordinary
+segments, one call) instead of clip_grad_norm_ + torch.optim.Adam, and pg.normalize_advantages (the masked mean and
+1 / sqrt(var + eps) from wg_obs_moments' ordered sums; the population variance, where adv[ok].std() is the sample's)
+instead of the boolean-indexed mean / std.  Off by default: without the flag the script runs as before.
+    python scripts/ppo_train.py --fused-loss --device-adam --out profiles/r31_ppo_device_adam_balance_curve.json
 """
 import argparse
 import json
@@ -47,7 +54,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from walker_gym_amd import pg                              # noqa: E402
+from walker_gym_amd import optim, pg                       # noqa: E402
 from walker_gym_amd.batched_env import BatchedPhysicsEnv   # noqa: E402
 from walker_gym_amd.normalize import ObsNorm               # noqa: E402
 from walker_gym_amd.policy import MLPPolicy                # noqa: E402
@@ -73,6 +80,7 @@ def main():
     ap.add_argument("--obs-norm", action="store_true")
     ap.add_argument("--act-every", type=int, default=1)
     ap.add_argument("--fused-loss", action="store_true")
+    ap.add_argument("--device-adam", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.manual_seed(a.seed)
@@ -92,7 +100,14 @@ def main():
     actor = [t for t in (w1, b1, wm, bm, w2, b2) if t is not None]
     log_sigma = torch.nn.Parameter(torch.full((A,), math.log(a.sigma), device=dev))
     critic = torch.nn.Sequential(torch.nn.Linear(D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to(dev)
-    opt = torch.optim.Adam([*actor, log_sigma, *critic.parameters()], lr=a.lr)
+    trained = [*actor, log_sigma, *critic.parameters()]
+    opt = optim.Adam(trained, lr=a.lr, max_norm=0.5) if a.device_adam else torch.optim.Adam(trained, lr=a.lr)
+
+    def update():   # the gradients are in place: clip their global norm at 0.5, one Adam step
+        if not a.device_adam:
+            torch.nn.utils.clip_grad_norm_(trained, 0.5)
+        opt.step()
+
     obs_scale = 1e-2   # the rows hold accelerations in the thousands: the critic sees them scaled
     if nm is not None:
         value_fn = lambda rows: critic(nm.normalize_torch(rows)).squeeze(-1)
@@ -114,7 +129,10 @@ def main():
         ok = torch.isfinite(adv) & torch.isfinite(ret) & torch.isfinite(obs).all(-1) & torch.isfinite(u).all(-1)
         if a.act_every > 1:
             ok = ok & (batch["decided"] != 0)
-        adv_n = torch.where(ok, (adv - adv[ok].mean()) / (adv[ok].std() + 1e-8), torch.zeros_like(adv))
+        if a.device_adam:
+            adv_n = pg.normalize_advantages(adv, ok)
+        else:
+            adv_n = torch.where(ok, (adv - adv[ok].mean()) / (adv[ok].std() + 1e-8), torch.zeros_like(adv))
         ret_0 = torch.where(ok, ret, torch.zeros_like(ret))
         with torch.no_grad():   # the old policy's density: the same function on the same rows, before any update
             if a.fused_loss:
@@ -138,8 +156,7 @@ def main():
                     v_loss = info["value_loss"].to(torch.float32)
                     opt.zero_grad(set_to_none=True)
                     loss.backward()
-                    torch.nn.utils.clip_grad_norm_([*actor, log_sigma, *critic.parameters()], 0.5)
-                    opt.step()
+                    update()
                     continue
                 lp = torch.where(mask, log_prob(mean, torch.where(mask[..., None], u, torch.zeros_like(u))), old_lp)
                 ratio = (lp - old_lp).exp()
@@ -152,8 +169,7 @@ def main():
                 loss = -(surr * mask).sum() / cnt + 0.5 * v_loss
                 opt.zero_grad(set_to_none=True)
                 loss.backward()
-                torch.nn.utils.clip_grad_norm_([*actor, log_sigma, *critic.parameters()], 0.5)
-                opt.step()
+                update()
         if nm is not None:
             nm.update(obs, ok)
         n_ep = batch["episodes"].sum().clamp(min=1)
@@ -171,7 +187,8 @@ def main():
     res = {"env": "Balance-v0", "walkers": N, "hidden": H, "hidden2": H2, "steps": a.steps, "iterations": a.iterations,
            "epochs": a.epochs, "minibatches": a.minibatches, "lr": a.lr, "clip": a.clip, "gamma": a.gamma,
            "lam": a.lam, "max_steps": a.max_steps, "seed": a.seed, "obs_norm": bool(a.obs_norm), "act_every": a.act_every,
-           "fused_loss": bool(a.fused_loss), "seconds": time.perf_counter() - t0,
+           "fused_loss": bool(a.fused_loss), "device_adam": bool(a.device_adam),
+           "seconds": time.perf_counter() - t0,
            "device": torch.cuda.get_device_name(0), "curve": curve}
     if a.out:
         with open(a.out, "w") as f:

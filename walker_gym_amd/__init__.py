@@ -18,7 +18,9 @@ the resident closed loop with an action hold (decide every k steps: wg_rollout_h
 grid (wg_gae_held); MLPPolicy(wm=..., bm=...), a second hidden layer in the rollouts and the row kernels (wg_rollout_deep,
 wg_policy_forward_deep / wg_policy_backward_deep); pg.expf, the library's own pinned exponential (wg_expf), and
 pg.log_prob_rows / pg.ppo_surrogate, the Gaussian density and the clipped PPO surrogate with its gradients in one kernel
-call (wg_ppo_surrogate).
+call (wg_ppo_surrogate); walker_gym_amd.optim.Adam, a global-norm clip and Adam / AdamW over float32 device tensors in
+one call and in pinned arithmetic (wg_adam_step; adam_step_numpy restates it), EvolutionStrategy(optimizer="adam") on
+top of it, and pg.normalize_advantages (the masked mean and scale from wg_obs_moments' ordered sums).
 Importing the package needs no GPU; stepping does (no CPU fallback).
 """
 from .engine import Config, DingPoint, Point, to_data  # noqa: F401
@@ -64,6 +66,15 @@ def __getattr__(name):
         # pg's pinned exponential (wg_expf) and the fused clipped surrogate over recorded rows (wg_ppo_surrogate)
         import importlib
         return getattr(importlib.import_module(".pg", __name__), name)
+    if name in ("normalize_advantages", "normalize_advantages_numpy"):   # pg's masked advantage normalisation
+        import importlib
+        return getattr(importlib.import_module(".pg", __name__), name)
+    if name == "optim":   # the device optimiser: Adam (wg_adam_step) and its numpy restatement
+        import importlib
+        return importlib.import_module(".optim", __name__)
+    if name in ("Adam", "adam_step_numpy"):
+        import importlib
+        return getattr(importlib.import_module(".optim", __name__), name)
     if name in ("PhysicsEnv", "make_env"):
         from . import optimized_env
         return getattr(optimized_env, name)

@@ -134,7 +134,19 @@ class WgPpoRows(C.Structure):
                 ("act_dim", C.c_int32)]
 
 
+class WgOptSegment(C.Structure):
+    """wg_opt_segment: one tensor of wg_adam_step's table (device pointers; the table itself is host memory)."""
+    _fields_ = [("param", _vp), ("grad", _vp), ("m", _vp), ("v", _vp), ("n", C.c_int64)]
+
+
+class WgAdam(C.Structure):
+    """wg_adam: the hyperparameters of one wg_adam_step call."""
+    _fields_ = [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm")] + \
+               [("maximize", C.c_int32)]
+
+
 POLICY_GRAD_MAX_K = 16384   # WG_POLICY_GRAD_MAX_K
+OPT_MAX_SEGMENTS = 32       # WG_OPT_MAX_SEGMENTS
 
 EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_run_ranges", "wg_rollout", "wg_observe",
            "wg_step_simple", "wg_observe_simple", "wg_reset", "wg_reset_noise", "wg_plan_ragged", "wg_plan_waves",
@@ -145,7 +157,7 @@ EXPORTS = ("wg_abi_version", "wg_last_error", "wg_step", "wg_step_ranges", "wg_r
            "wg_policy_backward_normalized", "wg_obs_moments_workspace", "wg_obs_moments", "wg_rollout_held", "wg_gae_held",
            "wg_rollout_deep", "wg_policy_forward_deep", "wg_policy_backward_deep_workspace", "wg_policy_backward_deep",
            "wg_es_perturb_deep", "wg_es_update_deep", "wg_es_perturb_diag_deep", "wg_es_update_diag_deep", "wg_expf",
-           "wg_ppo_surrogate_workspace", "wg_ppo_surrogate")
+           "wg_ppo_surrogate_workspace", "wg_ppo_surrogate", "wg_adam_workspace", "wg_adam_step")
 
 _lib = None
 _lock = threading.Lock()
@@ -214,6 +226,8 @@ def load(path: str | None = None):
         L.wg_ppo_surrogate_workspace.argtypes = [C.POINTER(WgPpoRows), C.c_int32]
         L.wg_ppo_surrogate.argtypes = [C.POINTER(WgPpoRows), _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_float, C.c_int32,
                                        _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]
+        L.wg_adam_workspace.argtypes = [C.POINTER(WgOptSegment), C.c_int32]
+        L.wg_adam_step.argtypes = [C.POINTER(WgOptSegment), C.c_int32, C.POINTER(WgAdam), _vp, _vp, _vp]
         L.wg_es_perturb.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp]
         L.wg_es_update.argtypes = [C.POINTER(WgEs), C.c_int32, C.c_int32, _vp, C.c_double, C.c_float, _vp, _vp, _vp, _vp]
         L.wg_es_perturb_diag.argtypes = [C.POINTER(WgEs), _vp, C.c_int32, C.c_int32, _vp]
@@ -249,6 +263,7 @@ def load(path: str | None = None):
         L.wg_policy_backward_deep_workspace.restype = C.c_int64
         L.wg_obs_moments_workspace.restype = C.c_int64
         L.wg_ppo_surrogate_workspace.restype = C.c_int64
+        L.wg_adam_workspace.restype = C.c_int64
         v = L.wg_abi_version()
         if v != ABI_VERSION:
             raise WalkerHipError(f"{p}: ABI version {v}, expected {ABI_VERSION}")

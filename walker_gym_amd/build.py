@@ -22,6 +22,7 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "walker_hip.hip")
 ES_SRC = os.path.join(HERE, "csrc", "es_hip.hip")   # wg_es_*: a unit of its own, the same flags, the same library
 PG_SRC = os.path.join(HERE, "csrc", "pg_hip.hip")   # wg_gae: likewise
+OPT_SRC = os.path.join(HERE, "csrc", "opt_hip.hip")  # wg_adam_*: likewise
 HDR = os.path.join(ROOT, "include", "walker_hip.h")
 OUT = os.path.join(HERE, "libwalker_hip.so")
 ARCH = os.environ.get("WALKER_HIP_ARCH", "gfx950")
@@ -43,7 +44,7 @@ def hipcc() -> str:
 
 def command(out: str = OUT) -> list:
     return [hipcc(), f"--offload-arch={ARCH}", *FLAGS, "-I", os.path.join(ROOT, "include"), "-o", out, SRC, ES_SRC,
-            PG_SRC]
+            PG_SRC, OPT_SRC]
 
 
 def needs_build(out: str = OUT) -> bool:

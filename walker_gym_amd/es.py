@@ -17,6 +17,11 @@ theta then has six segments: w1 (D*H1), b1 (H1), wm (H1*H2, element (j, k) at j*
 order of pg's gradient segments for a deep policy.  The noise, the antithetic rule and both updates are unchanged: they
 see the layout through K alone.
 
+EvolutionStrategy(optimizer="adam") takes the same estimate (wg_es_update with no theta_out) and steps theta with the
+device optimiser instead (wg_adam_step over the one segment theta, maximize = 1, lr = the trainer's;
+walker_gym_amd.optim.adam_step_numpy restates it): Adam's moments and an optional global-norm clip, without leaving the
+device.
+
 AdaptiveEvolutionStrategy over wg_es_perturb_diag / wg_es_update_diag keeps one sigma per parameter (a float32 [K]
 device vector) and adapts it from the same samples (PGPE with symmetric sampling): with d = RN32(sigma[k] * eps),
   g_theta[k] = scale_theta * sum_j (util[2j] - util[2j+1]) * d_j[k]
@@ -230,13 +235,18 @@ class EvolutionStrategy:
     whole generation from the state captured at construction.  obs_norm (walker_gym_amd.normalize.ObsNorm): the
     observation normaliser every candidate and mean_policy() evaluate; the caller updates it (generation_step's obs_out
     records the rows), the trainer carries it in its state_dict.  hidden2 > 0: a deep policy, hidden -> hidden2 units
-    (wm / bm in the MLPPolicy, theta's six segments, the wg_es_*_deep entries); everything else is the same."""
+    (wm / bm in the MLPPolicy, theta's six segments, the wg_es_*_deep entries); everything else is the same.
+    optimizer="adam": tell() steps theta with wg_adam_step (betas, adam_eps, max_norm; ascent along the estimate with
+    lr) instead of theta += lr * grad; None is the plain step."""
 
     def __init__(self, env, hidden: int = 0, act_dim: Optional[int] = None, biases: bool = True,
                  population: Optional[int] = None, sigma: float = 0.05, lr: float = 0.05, seed: int = 0,
-                 act_limit: float = 1.0, theta0=None, obs_norm=None, hidden2: int = 0):
+                 act_limit: float = 1.0, theta0=None, obs_norm=None, hidden2: int = 0, optimizer: Optional[str] = None,
+                 betas=(0.9, 0.999), adam_eps: float = 1e-8, max_norm: float = float("inf")):
         import torch
         from .policy import MLPPolicy
+        if optimizer not in (None, "adam"):
+            raise ValueError(f"optimizer {optimizer!r}: None (theta += lr * grad) or 'adam'")
         if isinstance(hidden, (tuple, list)) or getattr(hidden, "ndim", 0):
             raise ValueError(f"hidden {hidden!r}: `hidden` is the width of one hidden layer (an int); the second hidden "
                              "layer of a deep policy is hidden2=")
@@ -290,6 +300,13 @@ class EvolutionStrategy:
         self._work = torch.empty((-(-self.n_pairs // CHUNK), self.K), dtype=torch.float64, device=dv)
         self._grad = torch.empty(self.K, dtype=torch.float32, device=dv)
         self._state0 = env.batch.state_dict()
+        self.optimizer = optimizer
+        if optimizer == "adam":
+            from . import optim
+            self.adam_cfg = optim.adam_config(lr=self.lr, betas=betas, eps=adam_eps, max_norm=max_norm, maximize=True)
+            self._m, self._v = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
+            self._adam_state = torch.zeros(optim.STATE_LEN, dtype=torch.float64, device=dv)
+            self._adam_work = torch.empty(-(-self.K // optim.CHUNK), dtype=torch.float64, device=dv)
 
     # -------------------------------------------------------------------------------------------- the two kernels
     def _call(self, name: str, es, *args) -> None:
@@ -326,11 +343,21 @@ class EvolutionStrategy:
 
     def tell(self, fitness) -> dict:
         """Update theta in place from the candidates' fitness [G] (higher is better; NaN ranks lowest) and move to the
-        next generation.  Returns {'grad': [K] f32, the estimate theta moved along (for a caller's own optimiser)}."""
+        next generation.  Returns {'grad': [K] f32, the estimate theta moved along (for a caller's own optimiser)};
+        with optimizer="adam" also 'grad_norm', the estimate's norm as the step computed it (a 0-d float64 device
+        tensor)."""
         util = self.utilities(fitness).contiguous()
         es = self._struct()
         scale = 1.0 / (2.0 * self.n_pairs * self.sigma)
         p = _lib.ptr
+        if self.optimizer == "adam":
+            from . import optim
+            self._call("wg_es_update", es, 0, self.n_pairs, p(util), scale, self.lr, p(self._work), p(self._grad), None,
+                       self.env._stream())
+            optim.adam_step([self.theta], [self._grad], [self._m], [self._v], self._adam_state,
+                            dict(self.adam_cfg, lr=self.lr), self._adam_work)
+            self.generation += 1
+            return {"grad": self._grad.clone(), "grad_norm": self._adam_state[3].clone()}
         self._call("wg_es_update", es, 0, self.n_pairs, p(util), scale, self.lr, p(self._work), p(self._grad),
                    p(self.theta), self.env._stream())
         self.generation += 1
@@ -370,10 +397,13 @@ class EvolutionStrategy:
         fit = self.fitness_of(res, n_steps)
         out = self.tell(fit)
         nan = torch.isnan(fit)
-        return {"generation": self.generation - 1, "fitness": fit, "grad": out["grad"],
-                "fitness_mean": fit.double().nanmean(),
-                "fitness_max": torch.where(nan, torch.full_like(fit, float("-inf")), fit).max(),
-                "fitness_min": torch.where(nan, torch.full_like(fit, float("inf")), fit).min()}
+        res = {"generation": self.generation - 1, "fitness": fit, "grad": out["grad"],
+               "fitness_mean": fit.double().nanmean(),
+               "fitness_max": torch.where(nan, torch.full_like(fit, float("-inf")), fit).max(),
+               "fitness_min": torch.where(nan, torch.full_like(fit, float("inf")), fit).min()}
+        if "grad_norm" in out:
+            res["grad_norm"] = out["grad_norm"]
+        return res
 
     def mean_policy(self):
         """The G = 1 policy of theta (a copy); deep with hidden2 > 0."""
@@ -387,6 +417,9 @@ class EvolutionStrategy:
               "sigma": self.sigma, "lr": self.lr}
         if self.obs_norm is not None:
             sd["obs_norm"] = self.obs_norm.state_dict()
+        if self.optimizer == "adam":
+            sd.update(m=self._m.detach().cpu().clone(), v=self._v.detach().cpu().clone(),
+                      state=self._adam_state.detach().cpu().clone())
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -399,6 +432,9 @@ class EvolutionStrategy:
         self.sigma, self.lr = float(np.float32(sd["sigma"])), float(np.float32(sd["lr"]))
         if self.obs_norm is not None and "obs_norm" in sd:
             self.obs_norm.load_state_dict(sd["obs_norm"])
+        if self.optimizer == "adam" and "state" in sd:
+            for mine, key in ((self._m, "m"), (self._v, "v"), (self._adam_state, "state")):
+                mine.copy_(torch.as_tensor(sd[key], dtype=mine.dtype).reshape(mine.shape).to(mine.device))
 
 
 class AdaptiveEvolutionStrategy(EvolutionStrategy):
@@ -410,8 +446,11 @@ class AdaptiveEvolutionStrategy(EvolutionStrategy):
     def __init__(self, env, hidden: int = 0, act_dim: Optional[int] = None, biases: bool = True,
                  population: Optional[int] = None, sigma=0.05, lr: float = 0.05, seed: int = 0,
                  act_limit: float = 1.0, theta0=None, sigma_lr: float = 0.1, sigma_max_change: float = 0.2,
-                 sigma_min: float = 1e-8, sigma_max: float = float("inf"), obs_norm=None, hidden2: int = 0):
+                 sigma_min: float = 1e-8, sigma_max: float = float("inf"), obs_norm=None, hidden2: int = 0,
+                 optimizer: Optional[str] = None):
         import torch
+        if optimizer is not None:
+            raise ValueError("AdaptiveEvolutionStrategy takes no optimizer=: its theta step is inside wg_es_update_diag")
         s0 = np.asarray(sigma.detach().cpu() if hasattr(sigma, "detach") else sigma, dtype=np.float32)
         if s0.ndim > 1:
             raise ValueError(f"sigma has shape {s0.shape}: a scalar or a [K] vector")

@@ -49,6 +49,11 @@ row, float32, every operation rounded by itself, c ascending from logp = +0.0:
   ev = RN32(value - ret);   dvalue = RN32(scale[1] * ev)
 and per set, in policy_grad_numpy's chunks and order, float64 sums of wr * RN32(q[c] - 1) (exact products) into
 g_log_sigma and of five statistics (rows, surrogate, log-ratio, clipped, squared value error) into stats.
+
+Advantages.  normalize_advantages(adv, mask) is (adv - mean) * scale on the unmasked rows and zero elsewhere, mean and
+scale = 1 / sqrt(var + eps) taken from one wg_obs_moments call on adv as one column (normalize.py's ordered float64 sums
+over the rows that are unmasked and finite): no gather of the unmasked rows, nothing waits for the device.
+normalize_advantages_numpy restates it.  The step that follows an update's backward is walker_gym_amd.optim.Adam.
 """
 from __future__ import annotations
 
@@ -896,3 +901,51 @@ def ppo_surrogate(mean, raw_action, log_sigma, old_logp, adv, mask=None, clip: f
     info = {"stats": stats, "logp": logp, "approx_kl": -stats[2] / rows, "clip_fraction": stats[3] / rows,
             "value_loss": stats[4] / rows}
     return loss, info
+
+
+# ---------------------------------------------------------------------------------------------------- advantages
+def normalize_advantages_numpy(adv, mask=None, eps: float = 1e-8, chunk_rows: Optional[int] = None):
+    """normalize_advantages on the host: the moments of adv [T, N] (or [R]) over the rows that are unmasked and finite
+    (normalize.obs_moments_numpy with one column and bound = +inf), then float32 (adv - mean) * scale, zero where the
+    mask is."""
+    from .normalize import obs_moments_numpy, obs_norm_finish_numpy
+    a = np.ascontiguousarray(adv, dtype=np.float32)
+    a2 = a[None] if a.ndim == 1 else a
+    T, N = a2.shape
+    chunk = default_chunk_rows(T, N) if chunk_rows is None else int(chunk_rows)
+    st = obs_moments_numpy(a2.reshape(T, N, 1), None if mask is None else np.asarray(mask).reshape(T, N), math.inf, chunk)
+    fin = obs_norm_finish_numpy(st, eps)
+    mean, scale = (np.float32(0.0), np.float32(1.0)) if fin is None else (fin[0][0], fin[1][0])
+    with np.errstate(all="ignore"):
+        out = ((a - mean).astype(np.float32) * scale).astype(np.float32)
+    if mask is not None:
+        out = np.where(np.asarray(mask).reshape(a.shape) != 0, out, np.float32(0.0)).astype(np.float32)
+    return out
+
+
+def normalize_advantages(adv, mask=None, eps: float = 1e-8, chunk_rows: Optional[int] = None):
+    """(adv - mean) * scale over the unmasked rows of adv, float32 [T, N] (or [R]) on the device, zero where mask is.
+    mean and scale = 1 / sqrt(var + eps) come from one wg_obs_moments call on adv viewed as [T, N, 1] with bound = +inf:
+    its ordered float64 sums over the rows that are unmasked and finite (a NaN or inf advantage never enters them).
+    There is no gather of the unmasked rows and nothing waits for the device; with no usable row mean = 0, scale = 1.
+    normalize_advantages_numpy restates it."""
+    import torch
+    who = "normalize_advantages"
+    if not isinstance(adv, torch.Tensor) or adv.dim() not in (1, 2) or adv.dtype != torch.float32 or not adv.is_cuda:
+        raise ValueError(f"{who}: adv must be a float32 device tensor [T, N] or [R]")
+    dv = adv.device
+    rows, T, N, a3, m3, _ = _rows_of(1, dv, adv.unsqueeze(-1), mask, who)
+    chunk = default_chunk_rows(T, N) if chunk_rows is None else int(chunk_rows)
+    L = _lib.load()
+    count = _lib.check(L.wg_obs_moments_workspace(rows, 1, chunk), "wg_obs_moments_workspace")
+    ws = torch.empty(int(count), dtype=torch.float64, device=dv)
+    state = torch.zeros(3, dtype=torch.float64, device=dv)
+    mean = torch.zeros(1, dtype=torch.float32, device=dv)
+    scale = torch.ones(1, dtype=torch.float32, device=dv)
+    p = _lib.ptr
+    _lib.check(L.wg_obs_moments(rows, 1, math.inf, chunk, p(ws), p(state), float(eps), p(mean), p(scale),
+                                torch.cuda.current_stream(dv).cuda_stream), "wg_obs_moments")
+    out = torch.mul(torch.sub(adv, mean), scale)
+    if mask is not None:
+        out = torch.where(mask.reshape(adv.shape) != 0, out, torch.zeros((), dtype=torch.float32, device=dv))
+    return out
